@@ -13,13 +13,23 @@ A "step" is one full iteration of train_seg_semisup_mask_mt.py:287-476 on synthe
 student fwd/bwd on the supervised batch, 2 teacher forwards, student fwd/bwd on the CutMix-mixed batch, fused masked
 consistency + CE losses, fused Adam + EMA, (N > 1) bucketed RCCL all-reduce of the flat gradient arena.
 
-Default run = BOTH shapes of the metric, one after the other, in ONE JSON line (rank 0):
+Plain run (no --full): the headline only -- set up, warm up, time the K steps, write the outputs of the last timed step if
+--dump-outputs DIR is given, print ONE JSON line (rank 0):
   headline `value`            BASELINE configs[1]: DeepLab v2 / ResNet-101, 10 x 3 x 321 x 321, 21 classes, bf16
+No event brackets in the timed region, no extra steps after it, no CPU baseline, no profiler passes, no detail file.
+
+--full: everything below as well (the default of earlier versions):
   `configs[1]` of the line    BASELINE configs[2]: 4 x 3 x 512 x 1024 per GPU, 19 classes, paired colour-aug layout
                               (also as `value_512x1024`); `--workload pascal|cityscapes|pascal_v3plus` runs one only.
+  `also`                      short runs of configs[3] (DeepLab v3+), configs[1] without --freeze_bn, configs[4] (VAT U-Net)
+  the objects listed next, and the complete result object in bench_detail.json.
 Weak scaling: the per-GPU batch is fixed.
 
-Extra objects per workload
+--dump-outputs DIR: what the timed path returned in its last timed step (sup_loss, consistency_loss, conf_rate) and a fixed,
+seeded sample of the student's and the teacher's parameters after it, as DIR/<name>.npy (float32, ~8 MB in all). The inputs
+(weights, images, labels, box masks) are seeded: the same arguments give the same inputs in every run.
+
+Extra objects per workload (--full)
   roofline      the dominant hand-written kernels of the step, the cms_conv_igemm launches (conv8_kernel + conv_igemm_*kernel;
                 bound: MFMA), timed live with HIP events
                 on its launch stream inside the timed region; algorithmic FLOPs per launch = 2 * pixels * Cout * Cin * taps.
@@ -153,6 +163,45 @@ def vat_denseunet_run(dev, warmup=6, steps=12):
     return {'name': 'VAT DenseNet-161 U-Net (BASELINE configs[4])', 'value': B / dt, 'unit': 'images/sec', 'ms_per_step': dt * 1e3,
             'steps': steps, 'warmup': warmup, 'config': {'workload': 'densenet161unet VAT mean-teacher iteration, 10x3x224x224, 2 classes, SGD',
                                                         'hipgraph_replay': bool(captured), 'sup_loss': float(r['sup_loss'])}}
+
+
+DUMP_SAMPLE = 1 << 20          # parameters sampled per network for --dump-outputs (4 MB of float32 each)
+DUMP_LIMIT = 64 << 20          # bytes of .npy payload --dump-outputs may write in all
+
+
+def dump_arrays(res, stu, tea, n=DUMP_SAMPLE, seed=0):
+    """The arrays a caller of the timed step receives (its returned scalars) and a fixed, seeded sample of both networks'
+    parameters after it (the update the step made), as float32 numpy arrays keyed by file name."""
+    import numpy as np
+    import torch
+    out = {}
+    for k in ('sup_loss', 'consistency_loss', 'conf_rate'):
+        if res.get(k) is not None:
+            out[k] = np.asarray(res[k].detach().float().cpu().numpy() if isinstance(res[k], torch.Tensor) else res[k],
+                                dtype=np.float32).reshape(1)
+    for name, net in (('student_params_sample', stu), ('teacher_params_sample', tea)):
+        flat = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, flat.numel(), (min(n, flat.numel()),), generator=g).sort().values
+        out[name] = flat[idx.to(flat.device)].cpu().numpy().astype(np.float32)
+        del flat
+    return out
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT):
+    """DIR/<name>.npy for every array (float32 or float64 only, at most `limit` bytes in all); returns the file names."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise ValueError('--dump-outputs: {} bytes exceed the {}-byte limit'.format(total, limit))
+    os.makedirs(path, exist_ok=True)
+    names = []
+    for name, a in sorted(arrays.items()):
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError('--dump-outputs: {} is {}, not float32 / float64'.format(name, a.dtype))
+        np.save(os.path.join(path, name + '.npy'), a)
+        names.append(name + '.npy')
+    return names
 
 
 def write_detail(full, path=None):
@@ -333,8 +382,9 @@ def dry_launch(args, world, rank):
         dist.destroy_process_group()
 
 
-def run_workload(key, args, world, rank, dev):
-    """Builds the networks of workload `key`, times K steps, returns the result object (meaningful on rank 0)."""
+def run_workload(key, args, world, rank, dev, dump=None):
+    """Builds the networks of workload `key`, times K steps, returns the result object (meaningful on rank 0). `dump`: a
+    directory for the outputs of the last timed step (write_outputs)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -651,6 +701,8 @@ def run_workload(key, args, world, rank, dev):
         last = {k: (None if v is None else float(v)) for k, v in res.items()}
         if not np.isfinite(last['sup_loss']):
             raise SystemExit('non-finite loss in the bench loop: {}'.format(last))
+        if dump and rank == 0:                       # the last timed step's outputs, before any extra step moves the weights
+            write_outputs(dump, dump_arrays(res, stu, tea))
 
         # Host cost of enqueueing ONE step with an empty launch queue (in the timed loop the enqueue call blocks on the
         # queue whenever the GPU is the limit, so `host_enqueue_ms_per_step` ~ `ms_per_step` says nothing about the host)
@@ -769,7 +821,8 @@ def run_workload(key, args, world, rank, dev):
                          'avg_launch_ms': ms_kernel,
                          'algorithmic_{}_per_launch'.format('flops' if roof['bound'] == 'mfma' else 'bytes'): per_launch,
                          'launches_timed': n_timed,
-                         'sampling': ('every launch' if args.roofline_sample <= 1 else
+                         'sampling': 'none: no event brackets in this run (--full arms them)' if args.no_roofline_events else
+                                     ('every launch' if args.roofline_sample <= 1 else
                                       'every {}th launch'.format(args.roofline_sample)) +
                                      ('' if args.roofline_steps_every <= 1 else
                                       ' of every {}th timed step'.format(args.roofline_steps_every))},
@@ -850,20 +903,21 @@ def run_workload(key, args, world, rank, dev):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--workload', choices=sorted(WORKLOADS) + ['both'], default='both',
-                    help='both = pascal (321x321, the headline value) then cityscapes (512x1024), one JSON line')
+    ap.add_argument('--workload', choices=sorted(WORKLOADS) + ['both'], default=None,
+                    help='both = pascal (321x321, the headline value) then cityscapes (512x1024), one JSON line '
+                         '(default: both with --full, pascal without)')
     ap.add_argument('--dtype', choices=['bf16', 'fp32'], default='bf16')
     ap.add_argument('--roofline_kernel', choices=['conv', 'adam_ema'], default=None,
                     help='default: conv (the MFMA convolution) for the DeepLab v2 workloads, adam_ema otherwise')
     ap.add_argument('--no_cpu_baseline', action='store_true')
-    ap.add_argument('--traffic', choices=['measure', 'omit'], default='measure',
+    ap.add_argument('--traffic', choices=['measure', 'omit'], default=None,
                     help='roofline.traffic: measure it now with two rocprofv3 --pmc passes of this script (single GPU, '
-                         'workload pascal; ~1.5 min), or leave it null')
+                         'workload pascal; ~1.5 min), or leave it null (default: measure with --full, omit without)')
     ap.add_argument('--no_fuse_batches', action='store_true')
     ap.add_argument('--no_freeze_bn', action='store_true',
                     help='BatchNorm on batch statistics (the reference CLI default; its experiment scripts pass --freeze_bn): '
@@ -897,7 +951,28 @@ def main():
                     help='also print the complete object as an earlier stdout line {"bench_detail": ...} (the last line stays compact)')
     ap.add_argument('--dry_launch', action='store_true',
                     help='launch-path check without a GPU: gloo group, count the ranks, print the JSON skeleton')
-    args = ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: the 512x1024 shape, the `also` runs, event-bracketed roofline figures, '
+                         'the single-stream and empty-queue steps after the timed region, the CPU baseline, the PMC traffic '
+                         'passes and bench_detail.json (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', default='', metavar='DIR',
+                    help='write the outputs of the last timed step of the headline workload as DIR/<name>.npy (float32)')
+    return resolve_args(ap.parse_args(argv))
+
+
+def resolve_args(args):
+    """The defaults that depend on --full: a plain run times the headline and nothing else."""
+    if args.workload is None:
+        args.workload = 'both' if args.full else 'pascal'
+    if args.traffic is None:
+        args.traffic = 'measure' if args.full else 'omit'
+    if not args.full:
+        args.no_cpu_baseline = args.no_also = args.timed_only = args.no_roofline_events = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)                          # does not return
@@ -946,7 +1021,7 @@ def main():
             with torch.cuda.stream(st_):
                 torch.zeros(1, device=dev)
     keys = ['pascal', 'cityscapes'] if args.workload == 'both' else [args.workload]
-    results = [run_workload(k, args, world, rank, dev) for k in keys]
+    results = [run_workload(k, args, world, rank, dev, dump=args.dump_outputs if i == 0 else None) for i, k in enumerate(keys)]
     also = []
     if args.workload == 'both' and world == 1 and not args.no_also:
         # Two more configurations in the SAME driver-run line (short runs, never the headline `value`): BASELINE configs[3]
@@ -1019,9 +1094,9 @@ def main():
             out['also'] = also
             for a_, k_ in zip(also, ('also_v3plus_513x513_img_s', 'also_no_freeze_bn_321x321_img_s', 'also_vat_denseunet_224x224_img_s')):
                 out['config'][k_] = a_.get('value')
-        # the complete object goes to bench_detail.json (and, with --detail_stdout, to an EARLIER stdout line); the LAST stdout
-        # line is the compact one the driver parses (<= LINE_LIMIT bytes)
-        dpath = write_detail(out, args.detail_path or None)
+        # the complete object goes to bench_detail.json (--full or --detail_path; with --detail_stdout also to an EARLIER stdout
+        # line); the LAST stdout line is the compact one the driver parses (<= LINE_LIMIT bytes)
+        dpath = write_detail(out, args.detail_path or None) if (args.full or args.detail_path) else None
         if dpath:
             out['detail'] = os.path.basename(dpath)
         if args.detail_stdout:

@@ -459,6 +459,56 @@ def gen_deeplab2():
         json.dump(sorted(network_architectures.seg.names()), f)
 
 
+def gen_deeplab2_f64():
+    """The frozen-BatchNorm forward / backward of gen_deeplab2 with the reference network in float64. The fp32 gradients of
+    the deep ResNet-101 layers move by more than the test's tolerance with the host's convolution kernels (summation order):
+    in float64 the values are the same on every host, and the oracle's float64 run is held to them."""
+    oracle_dl = _load_oracle('deeplab2')
+    out = {}
+    for tag, layers, C, inputs in (
+            ('tiny', [1, 1, 1, 1], 5, [(2, 33, 33), (1, 40, 57)]),
+            ('r101', [3, 4, 23, 3], 21, [(2, 33, 33), (1, 65, 97)])):
+        if tag == 'r101':
+            net = ref_deeplab2.resnet101_deeplab_imagenet(C, pretrained=False)
+        else:
+            net = ref_deeplab2.ResNetDeepLab(ref_deeplab2.Bottleneck, layers, C, np.array([0.485, 0.456, 0.406]),
+                                             np.array([0.229, 0.224, 0.225]))
+        net.load_state_dict(oracle_dl.closed_form_state(C, layers))
+        net.double()
+        net.train()
+        net.freeze_batchnorm()
+        for ii, (n, h, w) in enumerate(inputs):
+            x = _closed_form_input(n, h, w, 0.3 + ii).double()
+            feats = {}
+            hook = net.layer5.register_forward_hook(lambda m, i, o: feats.__setitem__('lo', o))
+            hook4 = net.layer4.register_forward_hook(lambda m, i, o: feats.__setitem__('l4', o))
+            net.zero_grad()
+            y = net(x)
+            hook.remove()
+            hook4.remove()
+            wsum = torch.cos(0.11 * torch.arange(y.numel(), dtype=torch.float64)).reshape(y.shape)
+            (y * wsum).sum().backward()
+            key = '{}__in{}'.format(tag, ii)
+            out[key + '__lowres'] = feats['lo'].detach().numpy()
+            out[key + '__full_sub4'] = y.detach().numpy()[:, :, ::4, ::4].copy()
+            out[key + '__l4_stats'] = np.array([float(feats['l4'].sum()), float((feats['l4'] ** 2).sum())])
+            named = dict(net.named_parameters())
+            for k in ['conv1.weight', 'layer1.0.conv2.weight', 'layer3.0.downsample.0.weight',
+                      'layer4.0.conv3.weight', 'layer5.conv2d_list.0.weight', 'layer5.conv2d_list.1.bias']:
+                out['{}__grad__{}'.format(key, k)] = named[k].grad.numpy().reshape(-1)[:4096].copy()
+        # the un-frozen (batch-statistics) forward of gen_deeplab2, tiny net only
+        if tag == 'tiny':
+            net.load_state_dict(oracle_dl.closed_form_state(C, layers))
+            net.train()
+            y = net(_closed_form_input(2, 33, 33, 0.3).double())
+            out['tiny__bnstat__full_sub4'] = y.detach().numpy()[:, :, ::4, ::4].copy()
+            sd = net.state_dict()
+            for k in ('bn1.running_mean', 'bn1.running_var', 'layer4.0.bn3.running_var',
+                      'layer2.0.downsample.1.running_mean'):
+                out['tiny__bnstat__' + k] = sd[k].numpy().copy()
+    save('deeplab2_f64', **out)
+
+
 # ----------------------------------------------------------------------------------------------------------
 # 7. Adam / SGD with the duplicated parameter list
 # ----------------------------------------------------------------------------------------------------------
@@ -658,6 +708,30 @@ def gen_checkpoint():
     print('wrote checkpoint_meta.json (loaded {} of {} keys, kept {})'.format(len(loaded), len(after), kept))
 
 
+def gen_checkpoint_load():
+    """The other direction: a checkpoint WRITTEN BY THIS BUILD (tests/test_checkpoint.py `_export_bytes`, run in a child
+    process with the repository on the path) loaded by the reference's classes and run in eval mode on the test's probe
+    input. Records the logits the reference computed and the digest of the checkpoint it loaded."""
+    import subprocess
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix='cms_ckpt_')
+    path = os.path.join(tmp, 'model.pth')
+    prog = ('import sys; sys.path[:0] = [{!r}, {!r}]\n'
+            'from test_checkpoint import _export_bytes, checkpoint_digest\n'
+            '_, raw = _export_bytes()\n'
+            'open({!r}, "wb").write(raw)\n'
+            'print(checkpoint_digest(raw))\n').format(REPO, os.path.join(REPO, 'tests'), path)
+    digest = subprocess.check_output([sys.executable, '-c', prog], cwd=tmp).decode().strip().splitlines()[-1]
+    net = torch.load(path, weights_only=False)
+    assert type(net) is ref_deeplab2.ResNetDeepLab, type(net)
+    net.eval()
+    idx = torch.arange(2 * 3 * 33 * 33, dtype=torch.float64)
+    x = torch.sin(0.3 + 0.61803398875 * idx).reshape(2, 3, 33, 33).float() * 1.5
+    with torch.no_grad():
+        y = net(x)
+    save('ref_loads_checkpoint', logits=y.numpy().astype(np.float32), checkpoint_digest=np.array(digest))
+
+
 # ----------------------------------------------------------------------------------------------------------
 # 12. rotate / scale crop: the affine matrices of SegCVTransformRandomCropRotateScale.transform_single
 #     (datapipe/seg_transforms_cv.py:331-358). The transform class itself imports cv2 (absent) at module level; the
@@ -780,7 +854,7 @@ def gen_gauss():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['boxmask', 'ema', 'evaluation', 'lr', 'losses', 'deeplab2', 'optim', 'step', 'cli', 'cli_vat',
-                             'checkpoint', 'affine', 'vat', 'gauss']
+    which = sys.argv[1:] or ['boxmask', 'ema', 'evaluation', 'lr', 'losses', 'deeplab2', 'deeplab2_f64', 'optim', 'step', 'cli', 'cli_vat',
+                             'checkpoint', 'checkpoint_load', 'affine', 'vat', 'gauss']
     for w in which:
         globals()['gen_' + w]()

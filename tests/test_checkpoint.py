@@ -7,21 +7,20 @@ CPU: reference-compatible checkpoint I/O (checkpoint.py).
   * `_load_state_into_model` has the reference's semantics on a state dict with a missing key, a wrong-shaped entry and a
     foreign key (architectures/deeplab2.py:310-322) -- outcome and verbose output recorded from the reference;
   * `save_model` writes a pickle that names only the reference's class paths and round-trips;
-  * (build container only, skipped elsewhere) the REFERENCE's own code loads a checkpoint written here and computes the
-    oracle's logits with it.
+  * the REFERENCE's own code loads a checkpoint written here and computes the oracle's logits with it: recorded once by
+    tests/golden/make_golden.py (gen_checkpoint_load: the logits it computed, the digest of the checkpoint it loaded) and
+    checked here against the checkpoint this build writes now.
 """
 import io
 import json
 import os
 import pickletools
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO, GOLDEN
+from conftest import GOLDEN
 
 META = json.load(open(os.path.join(GOLDEN, 'checkpoint_meta.json')))
 
@@ -99,40 +98,37 @@ def test_save_model_writes_a_clean_pickle_under_the_references_class_paths(tmp_p
         assert torch.equal(a, b) and b.is_contiguous(), k
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='needs the reference checkout (build container only)')
-def test_reference_code_loads_a_checkpoint_written_here(tmp_path):
-    from oracle import deeplab2 as odl
-    _, raw = _export_bytes()
-    path = tmp_path / 'model.pth'
-    path.write_bytes(raw)
-    prog = r'''
-import sys, types
-sys.dont_write_bytecode = True
-sys.path = [p for p in sys.path if p not in ('', %r)]
-sys.path.insert(0, '/root/reference')
-for name in ('torchvision', 'torchvision.models', 'torchvision.models.resnet'):
-    sys.modules[name] = types.ModuleType(name)
-import torch
-from architectures import deeplab2
-assert deeplab2.__file__.startswith('/root/reference')
-net = torch.load(%r, weights_only=False)
-assert type(net) is deeplab2.ResNetDeepLab, type(net)
-net.eval()
-idx = torch.arange(2 * 3 * 33 * 33, dtype=torch.float64)
-x = torch.sin(0.3 + 0.61803398875 * idx).reshape(2, 3, 33, 33).float() * 1.5
-with torch.no_grad():
-    y = net(x)
-torch.save(y, %r)
-''' % (REPO, str(path), str(tmp_path / 'y.pt'))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-    env.pop('PYTHONPATH', None)
-    r = subprocess.run([sys.executable, '-c', prog], cwd=str(tmp_path), env=env, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    y = torch.load(tmp_path / 'y.pt')
+def checkpoint_digest(raw):
+    """sha256 over the entries of a torch.save archive (name + bytes, archive order), without the per-save
+    `serialization_id`: equal digests = the same object graph, class paths and tensor bytes."""
+    import hashlib
+    import zipfile
+    h = hashlib.sha256()
+    with zipfile.ZipFile(io.BytesIO(raw)) as z:
+        for n in z.namelist():
+            if n.endswith('serialization_id'):
+                continue
+            h.update(n.split('/', 1)[-1].encode())
+            h.update(z.read(n))
+    return h.hexdigest()
+
+
+def checkpoint_probe_input():
     idx = torch.arange(2 * 3 * 33 * 33, dtype=torch.float64)
-    x = torch.sin(0.3 + 0.61803398875 * idx).reshape(2, 3, 33, 33).float() * 1.5
-    want = odl.forward(x, odl.closed_form_state(5, [1, 1, 1, 1]), [1, 1, 1, 1], frozen=True)
+    return torch.sin(0.3 + 0.61803398875 * idx).reshape(2, 3, 33, 33).float() * 1.5
+
+
+def test_reference_code_loads_a_checkpoint_written_here(golden):
+    """The reference's own classes unpickled the checkpoint `_export_bytes` writes and ran it in eval mode on
+    `checkpoint_probe_input()` (tests/golden/make_golden.py, gen_checkpoint_load): the checkpoint written now is that one,
+    byte for byte, and what the reference computed with it is the oracle's forward pass."""
+    from oracle import deeplab2 as odl
+    g = golden('ref_loads_checkpoint')
+    _, raw = _export_bytes()
+    assert checkpoint_digest(raw) == str(g['checkpoint_digest'])
+    y = torch.from_numpy(g['logits'])
+    want = odl.forward(checkpoint_probe_input(), odl.closed_form_state(5, [1, 1, 1, 1]), [1, 1, 1, 1], frozen=True)
+    assert y.shape == want.shape
     torch.testing.assert_close(y, want, rtol=1e-4, atol=1e-5)
 
 

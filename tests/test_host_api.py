@@ -568,6 +568,57 @@ def test_bench_final_line_is_compact_and_strict_json():
         assert len(l5) <= 4096 and json.loads(l5, parse_constant=strict)['value'] == pytest.approx(626.766, rel=1e-5)
 
 
+def test_bench_plain_run_times_the_headline_only_and_full_keeps_the_rest():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the 321 x 321 headline and nothing else; --full restores what the
+    default run did before (both shapes, the `also` runs, event brackets, extra steps, CPU baseline, PMC passes); explicit
+    options still win."""
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if repo not in sys.path:
+        sys.path.insert(0, repo)
+    import bench
+    plain = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (plain.steps, plain.warmup, plain.full, plain.dump_outputs) == (7, 2, False, '')
+    assert plain.workload == 'pascal' and plain.traffic == 'omit'
+    assert plain.no_cpu_baseline and plain.no_also and plain.timed_only and plain.no_roofline_events
+    full = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2', '--full'])
+    assert full.workload == 'both' and full.traffic == 'measure'
+    assert not (full.no_cpu_baseline or full.no_also or full.timed_only or full.no_roofline_events)
+    mixed = bench.parse_args(['--full', '--workload', 'pascal', '--traffic', 'omit', '--no_cpu_baseline', '--dump-outputs', 'd'])
+    assert mixed.workload == 'pascal' and mixed.traffic == 'omit' and mixed.no_cpu_baseline and not mixed.no_also
+    assert mixed.dump_outputs == 'd'
+
+
+def test_bench_dump_outputs_are_float_npy_files_within_the_limit(tmp_path):
+    """--dump-outputs: the step's returned scalars and a seeded sample of both networks' parameters, float32, the same sample
+    every time; anything but float32 / float64 or more than the byte limit is refused."""
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if repo not in sys.path:
+        sys.path.insert(0, repo)
+    import bench
+    torch.manual_seed(0)
+    stu, tea = torch.nn.Linear(300, 200), torch.nn.Linear(300, 200)
+    res = dict(sup_loss=torch.tensor(1.25), consistency_loss=torch.tensor(0.5), conf_rate=None)
+    a = bench.dump_arrays(res, stu, tea, n=1000)
+    b = bench.dump_arrays(res, stu, tea, n=1000)
+    assert sorted(a) == ['consistency_loss', 'student_params_sample', 'sup_loss', 'teacher_params_sample']
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    flat = torch.cat([p.detach().reshape(-1) for p in stu.parameters()]).numpy()
+    assert a['student_params_sample'].shape == (1000,) and np.isin(a['student_params_sample'], flat).all()
+    assert float(a['sup_loss'][0]) == 1.25
+    names = bench.write_outputs(str(tmp_path / 'out'), a)
+    assert sorted(names) == sorted(k + '.npy' for k in a)
+    for k in a:
+        assert np.array_equal(np.load(str(tmp_path / 'out' / (k + '.npy'))), a[k])
+    with pytest.raises(TypeError):
+        bench.write_outputs(str(tmp_path / 'bad'), {'i': np.zeros(3, np.int64)})
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / 'big'), {'x': np.zeros(1000, np.float32)}, limit=100)
+    assert bench.DUMP_SAMPLE * 4 * 2 < bench.DUMP_LIMIT
+
+
 def test_hipgraph_replay_is_chosen_for_layer_engine_networks_only(monkeypatch):
     """(round 6) The gradient passes are captured into a hipGraph and replayed where every launch goes through Python (the U-Nets:
     host-bound), not for the DeepLab networks whose passes are recorded programs; one process only; the environment switches force

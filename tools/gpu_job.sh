@@ -5,7 +5,7 @@
 #   smoke                       __graft_entry__.smoke()
 #   pytest:<expr>               python -m pytest tests -m gpu -k <expr> -s      (expr 'all' = the whole GPU suite)
 #   pyfile:<file>[:<expr>]      one test file (with -s, so PARITY / PER-BLOCK lines reach the log)
-#   bench[:<name>]:<ENV=V,...>:<bench args>     one bench.py run with environment overrides (A/B legs), e.g.
+#   bench[:<name>]:<ENV=V,...>:<bench args>     one bench.py --full run with environment overrides (A/B legs), e.g.
 #                               bench:plain0:CMS_CONV_PLAIN=0:--workload pascal --steps 30 --no_cpu_baseline
 #   rocprof:<bench args>        rocprofv3 --kernel-trace --stats of bench.py, summarised with tools/rocpd_summary.py
 #   pmc:<bench args>            TCC FETCH_SIZE / WRITE_SIZE passes (separate runs, kernel-trace only) -> per-kernel traffic
@@ -43,7 +43,7 @@ for step in "$@"; do
     bench)
       name=${rest%%:*}; rest=${rest#*:}; envs=${rest%%:*}; args=${rest#*:}
       ( IFS=','; for kv in $envs; do [ -n "$kv" ] && export "$kv"; done; unset IFS
-        timeout 900 python bench.py $args ) > $OUT/${TAG}_bench_$name.log 2> $OUT/${TAG}_bench_$name.err
+        timeout 900 python bench.py --full $args ) > $OUT/${TAG}_bench_$name.log 2> $OUT/${TAG}_bench_$name.err
       echo "bench[$name] rc=$?" | tee -a $SUM
       [ -f bench_detail.json ] && cp bench_detail.json $OUT/${TAG}_bench_${name}_detail.json
       grep '^{"metric"' $OUT/${TAG}_bench_$name.log | python -c "
