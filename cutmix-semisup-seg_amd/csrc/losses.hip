@@ -824,8 +824,11 @@ __global__ __launch_bounds__(256) void ce_fwd_tiled_kernel(CeArgs a, float* __re
 
 __global__ void ce_finalize_kernel(const double* __restrict__ stats, float weight, float* __restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    out[0] = (float)(stats[0] / stats[1]);
-    out[1] = (float)((double)weight / stats[1]);
+    out[0] = (float)(stats[0] / stats[1]);         // 0 / 0 = NaN when every label is ignored, as nn.CrossEntropyLoss gives
+    // the gradient factor: with no valid pixel no row received a gradient, and the factor is 0 rather than weight / 0 = inf --
+    // cms_scale_by_scalar behind the one-launch path would turn its all-zero rows into 0 * inf = NaN, where the forward /
+    // backward launch pair (which skips ignored pixels) and torch leave them zero
+    out[1] = stats[1] > 0.0 ? (float)((double)weight / stats[1]) : 0.0f;
 }
 
 template <int CT>

@@ -121,6 +121,15 @@ __global__ __launch_bounds__(256) void optim_ema_kernel(cms_optim_desc d) {
                         p[i] = p[i] - (coef.step_size[j] * m[i]) / denom;
                     }
                 } else {
+                    // torch.optim.SGD rounds every operation on its own: d = g + wd * p; buf = buf * momentum + d; p = p - lr * d
+                    // are each a product AND a sum (oracle/ema_opt.py:sgd_k_updates). Contraction is off for ALL THREE in this block,
+                    // so the update matches torch's rounding operation for operation. It matters for the buffer: a contracted
+                    // buf * momentum + d keeps the product unrounded -- half an ulp of the buffer's HISTORY per update, which a buffer
+                    // that cancels to near zero does not forgive (tests/test_gpu_stream_kernels.py: the 2048-element segment with
+                    // k = 4 missed rtol 3e-6 / atol 2e-7 on slot0). HBM-bound kernel: three more VALU instructions per element.
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
                     for (int j = 0; j < k; ++j) {
                         float dd = gi;
                         if (d.weight_decay != 0.0f) dd = gi + d.weight_decay * p[i];

@@ -23,16 +23,18 @@ __global__ __launch_bounds__(256) void upsample_fwd_kernel(const float* __restri
     }
 }
 
-// range of output indices whose taps can touch input index I (conservative; filtered exactly by the caller)
-__device__ __forceinline__ void footprint(int I, float s, int out_size, int& lo, int& hi) {
+// range of output indices whose taps can touch input index I (conservative; filtered exactly by the caller): output d reads
+// src = s * d (align_corners) or s * (d + 0.5) - 0.5, and touches I when I - 1 < src < I + 1. The half-pixel offset moves the
+// range by 0.5 / s - 0.5 outputs: more than the margin of 2 once the ratio exceeds 5, so it is part of the formula.
+__device__ __forceinline__ void footprint(int I, float s, int out_size, bool align, int& lo, int& hi) {
     if (s <= 0.0f) {
         lo = 0;
         hi = out_size - 1;
         return;
     }
-    const float inv = 1.0f / s;
-    lo = (int)floorf(((float)I - 1.0f) * inv) - 2;
-    hi = (int)ceilf(((float)I + 1.0f) * inv) + 2;
+    const float inv = 1.0f / s, off = align ? 0.0f : 0.5f;
+    lo = (int)floorf(((float)I - 1.0f + off) * inv - off) - 2;
+    hi = (int)ceilf(((float)I + 1.0f + off) * inv - off) + 2;
     lo = lo < 0 ? 0 : lo;
     hi = hi > out_size - 1 ? out_size - 1 : hi;
 }
@@ -47,8 +49,8 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
         const int Y = (int)(t % h);
         const size_t nc = t / h;
         int y_lo, y_hi, x_lo, x_hi;
-        footprint(Y, sy, H, y_lo, y_hi);
-        footprint(X, sx, W, x_lo, x_hi);
+        footprint(Y, sy, H, align != 0, y_lo, y_hi);
+        footprint(X, sx, W, align != 0, x_lo, x_hi);
         const float* src = ghi + nc * (size_t)H * W;
         float acc = 0.0f;
         for (int y = y_lo; y <= y_hi; ++y) {

@@ -3,9 +3,12 @@ GPU: the NHWC data-movement kernels of the DeepLab v3+ head (csrc/nhwc.hip) agai
 host -- values and every gradient: concat with a broadcast (N,1,1,C) input, bilinear upsample (align_corners False / True) into
 a channel slice, global average pool, k-way gradient fan-in.
 """
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import _stream_refs as R
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -53,10 +56,13 @@ def test_upsample_concat_vs_interpolate(dtype, align, geo):
     out.backward(dy.to(DEV))
     torch.testing.assert_close(out.detach().float().cpu(), ref.detach(), **_tol(dtype))
     torch.testing.assert_close(ld.grad.float().cpu(), lr.grad, **_tol(dtype))
-    tol = _tol(dtype)
     if dtype == torch.bfloat16:
-        tol = dict(rtol=3e-2, atol=6e-2)          # up to ~9 products summed, bf16 output
-    torch.testing.assert_close(xd.grad.float().cpu(), xr.grad, **tol)
+        # the derived bound on every element (tests/_stream_refs.py): fp32 accumulation of d products -- d = the number of output
+        # pixels whose taps touch the source pixel -- then one bf16 rounding
+        adj, A, d = R.upsample_bilinear_adjoint(dy[..., 48:].double().numpy(), (h, w), align, 'nhwc', np.float32)
+        R.assert_within(xd.grad.double().cpu().numpy(), adj, R.bound(A, d, adj, bf16_out=True), 'upsample_nhwc_adjoint bf16 (test_gpu_nhwc)')
+    else:
+        torch.testing.assert_close(xd.grad.float().cpu(), xr.grad, **_tol(dtype))
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['fp32', 'bf16'])

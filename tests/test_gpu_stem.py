@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _stream_refs as R
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
@@ -47,7 +49,17 @@ def test_stem_forward_pool_and_backward(ops, shape, dtype):
     # the pool is exact on whatever the stem produced
     assert torch.equal(p.float().permute(0, 3, 1, 2), F.max_pool2d(s.float().permute(0, 3, 1, 2), 3, 2, 1, ceil_mode=True))
     if dtype != torch.float32:
-        return          # (bf16 ties move the argmax; the backward is checked on the fp32 path, the kernels are shared)
+        # bf16 ties move the argmax away from the fp64 graph's: route dp by the kernel's OWN index map (tests/_stream_refs.py) --
+        # independent of the tie rule -- and gate by s > 0. <= 4 window gradients summed in fp32 (d = 3), one bf16 rounding.
+        dpn = dp.permute(0, 2, 3, 1).contiguous().to(dtype)
+        ds = ops.maxpool3x3s2_relu_backward(cu(dpn), idx, s)
+        sn, idn = s.float().cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+        val, inside = R.maxpool_window_value(sn, idn, True)
+        assert inside.all() and np.array_equal(val, p.float().cpu().numpy())
+        ref = R.maxpool3x3s2_relu_backward(dpn.double().numpy(), idn, sn)
+        A = R.maxpool3x3s2_relu_backward(dpn.double().abs().numpy(), idn, sn)
+        R.assert_within(ds.double().cpu().numpy(), ref, R.bound(A, 3, ref, bf16_out=True), 'maxpool_bwd bf16 (test_gpu_stem)')
+        return
     ds = ops.maxpool3x3s2_relu_backward(cu(dp.permute(0, 2, 3, 1).contiguous()), idx, s)
     # d loss / d (conv * scale + bias) from the reference graph
     ds_ref = torch.autograd.grad(p_ref, s_ref, dp.double(), retain_graph=True)[0] * (s_ref > 0)
