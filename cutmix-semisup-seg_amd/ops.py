@@ -114,6 +114,14 @@ class ConsistencyConfig(object):
         self.invert = bool(invert)
 
 
+def _nonempty_ranges(ranges):
+    """(N, 0, 4) -- no box at all -- as ONE empty box per sample: a tensor without elements has no address, and the library would
+    take the NULL pointer for "no ranges given". An empty box holds no pixel, so the parity of every pixel stays what zero boxes give."""
+    if ranges is not None and ranges.dim() == 3 and ranges.shape[1] == 0:
+        return torch.zeros((int(ranges.shape[0]), 1, 4), dtype=torch.int32, device=ranges.device)
+    return ranges
+
+
 def _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size):
     n, c, h, w = (int(s) for s in l_stu.shape)
     d = _lib.ConsistencyDesc()
@@ -152,6 +160,7 @@ def consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges=None, mask=
     _need_cuda(l_stu, l_tea0, l_tea1, ranges, mask, um0, um1)
     l_stu, l_tea0, l_tea1 = _f32c(l_stu), _f32c(l_tea0), _f32c(l_tea1)
     mask, um0, um1 = _f32c(mask), _f32c(um0), _f32c(um1)
+    ranges = _nonempty_ranges(ranges)
     if l_tea0.shape != l_stu.shape or (l_tea1 is not None and l_tea1.shape != l_stu.shape):
         raise ValueError('consistency: student / teacher logits shapes differ')
     d = _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size)
@@ -202,6 +211,7 @@ def consistency_fused(cfg, l_stu, l_tea0, l_tea1, out_size, grad_out, ranges=Non
     _need_cuda(l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, grad_out)
     l_stu, l_tea0, l_tea1 = _f32c(l_stu), _f32c(l_tea0), _f32c(l_tea1)
     mask, um0, um1 = _f32c(mask), _f32c(um0), _f32c(um1)
+    ranges = _nonempty_ranges(ranges)
     if l_tea0.shape != l_stu.shape or (l_tea1 is not None and l_tea1.shape != l_stu.shape):
         raise ValueError('consistency: student / teacher logits shapes differ')
     if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(l_stu.shape) or not grad_out.is_contiguous():
