@@ -305,7 +305,8 @@ class HipConvEngine(LayerEngine):
 
     def _frozen_affine(self, bn):
         """fp32 (scale, shift) of an eval-mode BatchNorm, cached per weight version of the network's arena (optimizer / EMA steps
-        `touch()` it; a capture into a hipGraph marks it stale first, so the refresh is part of the graph)."""
+        `touch()` it; a capture into a hipGraph marks it stale first, so the refresh is part of the graph, and again when the capture
+        fails: what the aborted capture cached was never written; graph_replay.GraphReplay.run)."""
         cache = self.__dict__.setdefault('_frozen_affines', {})
         hit = cache.get(id(bn))
         if hit is not None and hit[0] == self.arena.version:

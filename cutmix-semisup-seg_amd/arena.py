@@ -67,7 +67,8 @@ class ParamArena(object):
             off += (cnt + ALIGN - 1) // ALIGN * ALIGN
         self.total = off
         # bumped by everything of this package that writes the weights (fused optimizer / EMA steps, refresh_bf16 behind
-        # load_state_dict): derived operands cached per layer (zero-padded weights, transposed data-gradient operands of the general
+        # load_state_dict) and by graph_replay before a hipGraph capture and after a failed one (the refresh belongs inside the graph;
+        # what an aborted capture cached was never written): derived operands cached per layer (zero-padded weights, transposed data-gradient operands of the general
         # convolution path, backbone_hip._HipConvGeneralFn) are valid for one version
         self.version = 0
         self.derived = {}            # (key, what, dtype) -> (version, tensor)

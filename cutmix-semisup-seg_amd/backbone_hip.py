@@ -1523,7 +1523,7 @@ _INDEX_TENSORS = {}
 
 def _index_tensor(values, device):
     """A small int64 index tensor on the device, made ONCE per (values, device): a host -> device copy from pageable memory
-    synchronises, which a pass being captured into a hipGraph may not do (vat.VATMeanTeacherStep._graphed_grads)."""
+    synchronises, which a pass being captured into a hipGraph may not do (graph_replay.GraphReplay.run)."""
     key = (values, str(device))
     t = _INDEX_TENSORS.get(key)
     if t is None:

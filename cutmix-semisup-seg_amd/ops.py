@@ -531,7 +531,7 @@ _SIDE_ENABLED = True
 
 def set_side_streams_enabled(on):
     """Switch the layer engines' side streams (weight gradients, ASPP branches) on / off; -> the previous setting. Off while a pass
-    is captured into a hipGraph on ONE stream (vat.VATMeanTeacherStep._graphed_grads)."""
+    is captured into a hipGraph on ONE stream (graph_replay.GraphReplay.run)."""
     global _SIDE_ENABLED
     prev, _SIDE_ENABLED = _SIDE_ENABLED, bool(on)
     return prev

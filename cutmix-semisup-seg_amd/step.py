@@ -30,6 +30,7 @@ import os
 import torch
 
 from . import ops
+from .graph_replay import GraphReplay
 
 
 class StepConfig(object):
@@ -70,9 +71,6 @@ class StepConfig(object):
         self.overlap_losses = os.environ.get('CMS_OVERLAP_LOSSES', '1') != '0'
         # the teacher's stream forks at the head of the step instead of behind the paste / concatenation of the student's inputs (A/B)
         self.early_teacher_fork = os.environ.get('CMS_EARLY_TEACHER_FORK', '1') != '0'
-        # (measured: 626.1 vs 629.2 img/s at cfg 2, 134.2 vs 134.9 at cfg 3 WITHOUT it, profiles/r05f_*: the two halves slow each other
-        # and the cross entropy down by more than the overlap buys -- off; CMS_SPLIT_CONS_BWD=1 switches it on)
-        self.split_cons_bwd = os.environ.get('CMS_SPLIT_CONS_BWD', '0') not in ('0', '')
         # (round 6) each loss as ONE launch (forward + backward, the gradient's scalar factor applied afterwards: ops.consistency_fused
         # / ops.ce_fused) in the fused-batch step; CMS_FUSED_LOSSES=0 = the forward / backward launch pairs of rounds 1-5 (A/B)
         self.fused_losses = os.environ.get('CMS_FUSED_LOSSES', '1') != '0'
@@ -95,6 +93,31 @@ class UnsupBatch(object):
         self.x1_stu = x1_tea if x1_stu is None else x1_stu
         self.um0, self.um1 = um0, um1
         self.ranges = ranges
+
+
+# ---------------------------------------------------------------------------------------------- shared with the VAT step (vat.py)
+def world_size(group):
+    import torch.distributed as dist
+    return dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+
+
+def supervised_pass(student, sup_x, sup_y, out_size, align_corners, group):
+    """student(x_sup) -> CE(ignore 255) -> backward, train_seg_semisup_mask_mt.py:296-301. -> the CE scalars"""
+    lo = student.forward_lowres(sup_x)
+    ce_sc, ce_ctx = ops.ce_forward(lo.detach(), sup_y, out_size, 255, align_corners, group=group)
+    lo.backward(ops.ce_backward(ce_ctx, ce_sc).to(lo.dtype))
+    return ce_sc
+
+
+def step_result(ce_sc, cons_vals):
+    """Device scalars of an iteration: dict(sup_loss, consistency_loss, conf_rate), the latter two averaged over the unsupervised
+    batches (None when there are none)."""
+    res = dict(sup_loss=ce_sc[0], consistency_loss=None, conf_rate=None)
+    if cons_vals:
+        stacked = torch.stack(cons_vals)
+        res['consistency_loss'] = stacked[:, 0].mean()
+        res['conf_rate'] = stacked[:, 1].mean()
+    return res
 
 
 class GradBuckets(object):
@@ -186,14 +209,18 @@ class CutMixMeanTeacherStep(object):
             student_net.dist_group = teacher_net.dist_group = group
         self.align_corners = getattr(student_net, 'upsample_align_corners', True)
         cfg.cons.align_corners = self.align_corners
-        import torch.distributed as dist
-        self.world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+        self.world = world_size(group)
         self._nan_probe = None
         self._nan_event = None
         self._side = None
         self._buckets = None
         self._bucket_obj = None
+        self._bucket_hook = None            # (buckets, the executor's hook onto them)
         self._whole = None
+        self._opt_stream = None
+        self._early_armed = False           # early optimizer launches of this step are out on `_opt_stream`
+        self._coupling_modules = None
+        self._graphs = GraphReplay('the gradient passes of the step', 'CMS_STEP_GRAPH')
         self.time_buckets = False           # bench.py: keep a (bytes, issue-to-wait) record per gradient bucket
         if cfg.deterministic:
             ops.set_deterministic_wgrad(True)
@@ -219,15 +246,19 @@ class CutMixMeanTeacherStep(object):
         b = self._buckets if self._buckets is not None else self._whole
         return [] if b is None else b.read_timing()
 
+    def _student_executor(self):
+        """The student's recorded-program executor, or None when its body does not run on one."""
+        use_hip = getattr(self.student, '_use_hip_body', None)
+        return self.student.hip_executor() if use_hip is not None and use_hip() else None
+
     def _arm_buckets(self):
         """Overlap the gradient all-reduce with the (single) backward pass of the fused-batch step on the executor."""
         self._buckets = None
         if self.world <= 1 or not self.cfg.fuse_batches or not self.cfg.bucketed_allreduce:
             return None
-        use_hip = getattr(self.student, '_use_hip_body', None)
-        if use_hip is None or not use_hip():
+        ex = self._student_executor()
+        if ex is None:
             return None
-        ex = self.student.hip_executor()
         if self._bucket_obj is None:
             offs = ex.block_grad_offsets()
             # [layer4 + head], the two halves of layer3, [layer1 - layer2]: the executor orders its weight-gradient
@@ -237,8 +268,7 @@ class CutMixMeanTeacherStep(object):
         self._bucket_obj.timing = self.time_buckets
         self._buckets = self._bucket_obj
         self._buckets.begin()
-        hook = self._buckets.on_block
-        if self.__dict__.get('_bucket_hook') is None or self._bucket_hook[0] is not self._buckets:
+        if self._bucket_hook is None or self._bucket_hook[0] is not self._buckets:
             buckets = self._buckets
 
             def hook(bi):
@@ -253,15 +283,11 @@ class CutMixMeanTeacherStep(object):
         as soon as that slice's gradients are final -- [layer4 + head], the two halves of layer3, [layer1 - layer2], at the
         bottlenecks the data-parallel buckets close at -- instead of one 0.28 ms launch after the whole backward pass; the
         stem's slice follows in `student_optim.step()`. Same arithmetic per element, so the results are bit-identical."""
-        every = getattr(self.cfg, 'early_optimizer', False)
-        if self.world > 1 or not (every or getattr(self.cfg, 'tail_optimizer', False)) \
-                or not hasattr(self.student_optim, 'step_range'):
+        every = self.cfg.early_optimizer
+        if self.world > 1 or not (every or self.cfg.tail_optimizer) or not hasattr(self.student_optim, 'step_range'):
             return None
-        use_hip = getattr(self.student, '_use_hip_body', None)
-        if use_hip is None or not use_hip() or not hasattr(self.student.hip_executor(), 'block_grad_offsets'):
-            return None
-        ex = self.student.hip_executor()
-        if not ex.use_programs or not ex._want_w():
+        ex = self._student_executor()
+        if ex is None or not hasattr(ex, 'block_grad_offsets') or not ex.use_programs or not ex._want_w():
             return None
         opt = self.student_optim
         offs = ex.block_grad_offsets()
@@ -277,7 +303,7 @@ class CutMixMeanTeacherStep(object):
                 starts.add(ex.layer_first_blocks()[1 if cut == 'l2' else 2])
         state = {'hi': int(opt.arena.flat.numel())}
         opt.begin_ranged()
-        if self.__dict__.get('_opt_stream') is None:
+        if self._opt_stream is None:
             self._opt_stream = ops.pooled_stream(opt.arena.device, 'optimizer')
         side = self._opt_stream
 
@@ -298,12 +324,10 @@ class CutMixMeanTeacherStep(object):
         """Batches may only be concatenated when no layer couples the samples of a batch: every BatchNorm frozen and
         no active dropout, in BOTH networks (DeepLab v3+ keeps batch statistics and dropout in its head even under
         --freeze_bn, deeplab3plus.py:120-121 -> the reference's separate passes are kept for it)."""
-        mods = self.__dict__.get('_coupling_modules')
-        if mods is None:                  # (the module trees are static: collect the candidates once, test their flags per call)
-            mods = self.__dict__['_coupling_modules'] = [
-                m for net in (self.student, self.teacher) for m in net.modules()
-                if 'BatchNorm' in type(m).__name__ or 'Dropout' in type(m).__name__]
-        for m in mods:
+        if self._coupling_modules is None:    # (the module trees are static: collect the candidates once, test their flags per call)
+            self._coupling_modules = [m for net in (self.student, self.teacher) for m in net.modules()
+                                      if 'BatchNorm' in type(m).__name__ or 'Dropout' in type(m).__name__]
+        for m in self._coupling_modules:
             if m.training and ('BatchNorm' in type(m).__name__ or getattr(m, 'p', 0) > 0):
                 return False
         return True
@@ -361,20 +385,20 @@ class CutMixMeanTeacherStep(object):
         8 ms later, so it goes out on the FIRST WEIGHT-GRADIENT STREAM (idle during the forward passes) instead of in front of the
         paste / concatenation / stems of the main stream (round 6). Order: the fill waits for the main stream (last
         step's optimizer has read the gradients), the main stream waits for the fill right before the backward pass -- every
-        gradient writer forks from the main stream behind that point. CMS_ZERO_GRAD_SIDE=0: on the main stream, as in rounds 1-5."""
-        if not self.cfg.zero_grad_side or not torch.cuda.is_available():
+        gradient writer forks from the main stream behind that point. CMS_ZERO_GRAD_SIDE=0: on the main stream, as in rounds 1-5.
+        -> the event the main stream has to wait for, or None"""
+        wg = None
+        if self.cfg.zero_grad_side and torch.cuda.is_available():
+            wg = ops.pooled_stream(torch.cuda.current_device(), 'wgrad0')
+        if wg is None or wg is main:
             self.student_optim.zero_grad()
-            return
-        wg = ops.pooled_stream(torch.cuda.current_device(), 'wgrad0')
-        if wg is main:
-            self.student_optim.zero_grad()
-            return
+            return None
         wg.wait_stream(main)
         with torch.cuda.stream(wg):
             self.student_optim.zero_grad()
             ev = torch.cuda.Event()
             ev.record(wg)
-        self.__dict__['_zero_grad_event'] = ev
+        return ev
 
     def _student_inputs(self, ub):
         cfg = self.cfg
@@ -401,9 +425,7 @@ class CutMixMeanTeacherStep(object):
                 for ub in unsup_batches:
                     tea_out.append((self.teacher.forward_lowres(ub.x0_tea),
                                     self.teacher.forward_lowres(ub.x1_tea) if cfg.mix else None))
-        lo = self.student.forward_lowres(sup_x)
-        ce_sc, ce_ctx = ops.ce_forward(lo.detach(), sup_y, out_size, 255, self.align_corners, group=self.group)
-        lo.backward(ops.ce_backward(ce_ctx, ce_sc).to(lo.dtype))
+        ce_sc = supervised_pass(self.student, sup_x, sup_y, out_size, self.align_corners, self.group)
         cons_vals = []
         if use_unsup:
             for bi, ub in enumerate(unsup_batches):
@@ -436,76 +458,152 @@ class CutMixMeanTeacherStep(object):
 
     def _separate_or_graphed(self, sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup):
         """`_separate_passes`, or -- after two eager iterations of a (shapes, modes, ramp) signature -- its capture into ONE
-        torch.cuda.CUDAGraph over static input buffers, replayed (see vat.VATMeanTeacherStep._graphed_grads, whose rules apply:
-        weight-derived operands marked stale before the capture, one capture stream, no teacher side stream inside, dropout draws
-        from the default generator the graph registers; a ramp that still changes runs eagerly; an operation the capture cannot hold
-        -> warning + launches). Gradient exchange, optimizer, EMA and the NaN probe stay outside."""
+        torch.cuda.CUDAGraph over static input buffers, replayed (graph_replay.GraphReplay, whose rules apply: one capture stream for
+        the layer engines, dropout draws from the default generator the graph registers; a ramp that still changes runs eagerly; an
+        operation the capture cannot hold -> warning + launches). Gradient exchange, optimizer, EMA and the NaN probe stay outside."""
         cfg = self.cfg
         if not (sup_x.is_cuda and self._graph_wanted() and (cfg.rampup <= 0 or float(ramp) >= 1.0)):
             return self._separate_passes(sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup)
-        ubs = list(unsup_batches) if use_unsup else []
         flat = [sup_x, sup_y]
-        for u in ubs:
+        for u in (unsup_batches if use_unsup else ()):
             flat += [u.x0_tea, u.x1_tea, u.x0_stu, u.x1_stu, u.ranges, u.um0, u.um1]
-        sig = lambda t: None if t is None else (tuple(t.shape), t.dtype, t.device.index)
-        alias = tuple(next(j for j, q in enumerate(flat) if q is t) if t is not None else -1 for t in flat)   # which inputs are ONE tensor
-        key = (tuple(sig(t) for t in flat), alias, float(ramp), tuple(out_size), bool(use_unsup), self.student.training, self.teacher.training,
-               getattr(self.student, 'compute_dtype', None), getattr(self.teacher, 'compute_dtype', None))
-        store = self.__dict__.setdefault('_graphs', {})
-        ent = store.setdefault(key, {'seen': 0})
+        extra = (float(ramp), tuple(out_size), bool(use_unsup), self.student.training, self.teacher.training,
+                 getattr(self.student, 'compute_dtype', None), getattr(self.teacher, 'compute_dtype', None))
 
-        def rebuild(ts):
-            out, i = [], 2
-            for _ in ubs:
-                x0t, x1t, x0s, x1s, rg, m0, m1 = ts[i:i + 7]
-                out.append(UnsupBatch(x0t, rg, um0=m0, x1_tea=x1t, um1=m1, x0_stu=x0s, x1_stu=x1s))
-                i += 7
-            return out
+        def passes(ts, capturing):
+            ubs = [UnsupBatch(x0t, rg, um0=m0, x1_tea=x1t, um1=m1, x0_stu=x0s, x1_stu=x1s)
+                   for x0t, x1t, x0s, x1s, rg, m0, m1 in (ts[i:i + 7] for i in range(2, len(ts), 7))]
+            # the teacher's passes fork to their side stream inside the capture too (one fork, one join: 353 -> 413 img/s on the
+            # ResNet-50 U-Net, 119 -> 140 on the DenseNet-161 U-Net; CMS_STEP_GRAPH_OVERLAP=0: one stream)
+            overlap = not capturing or os.environ.get('CMS_STEP_GRAPH_OVERLAP', '1') != '0'
+            return self._separate_passes(ts[0], ts[1], ubs, ramp, out_size, use_unsup, allow_overlap=overlap)
 
-        if 'graph' not in ent:
-            ent['seen'] += 1
-            if ent['seen'] <= 2 or ent.get('failed'):
-                return self._separate_passes(sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup)
-            static = []
-            for j, t in enumerate(flat):
-                static.append(None if t is None else (static[alias[j]] if alias[j] != j else t.clone()))
-            for net in (self.student, self.teacher):
-                a = getattr(net, '_cms_arena', None)
-                if a is not None:
-                    a.touch()
-            # everything lazy that synchronises must have happened BEFORE the capture: the side-stream probe above all (a trainer whose
-            # eager iterations never asked for a pooled stream met it inside the capture: `operation not permitted when stream is capturing`)
-            ops.pooled_stream(sup_x.device, 'teacher')
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            prev = ops.set_side_streams_enabled(False)
-            try:
-                with torch.cuda.graph(g):
-                    # the teacher's passes fork to their side stream inside the capture too (one fork, one join: 353 -> 413 img/s on the
-                    # ResNet-50 U-Net, 119 -> 140 on the DenseNet-161 U-Net; CMS_STEP_GRAPH_OVERLAP=0: one stream)
-                    outs = self._separate_passes(static[0], static[1], rebuild(static), ramp, out_size, use_unsup,
-                                                 allow_overlap=os.environ.get('CMS_STEP_GRAPH_OVERLAP', '1') != '0')
-            except Exception as e:               # noqa: BLE001 -- nothing ran on the device
-                import warnings
-                warnings.warn('cutmix-semisup-seg_amd: the gradient passes of the step could not be captured into a hipGraph ({}: {}); '
-                              'this signature keeps running launch by launch'.format(type(e).__name__, str(e).splitlines()[0] if str(e) else ''),
-                              RuntimeWarning, stacklevel=2)
-                ent['failed'] = True
-                try:
-                    torch.cuda.synchronize()
-                except Exception as e2:          # noqa: BLE001 -- a forked stream is still inside the aborted capture: this process cannot launch any more
-                    raise RuntimeError('a failed hipGraph capture left the device in capture mode ({}); restart with {}=0 (launch by launch) '
-                                       'and report the operation named in the warning above'.format(e2, 'CMS_STEP_GRAPH')) from e
-                return self._separate_passes(sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup)
-            finally:
-                ops.set_side_streams_enabled(prev)
-            ent.update(graph=g, static=static, out=outs)
-        for j, (st, t) in enumerate(zip(ent['static'], flat)):
-            if t is not None and alias[j] == j:
-                st.copy_(t)
-        ent['graph'].replay()
-        ce_sc, cons_vals = ent['out']
-        return ce_sc.clone(), [c.clone() for c in cons_vals]
+        return self._graphs.run(flat, extra, passes, nets=(self.student, self.teacher), device=sup_x.device)
+
+    # ------------------------------------------------------------------------------------------ fused batches
+    def _fused_passes(self, sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup, independent, groups):
+        """ONE student pass over [x_sup; x_mix ...] beside ONE teacher pass over [x0; x1 ...] on its own stream, both losses, one
+        backward pass. -> (ce scalars, [consistency scalars])"""
+        cfg = self.cfg
+        n_sup = sup_x.shape[0]
+        stu_in = [sup_x]
+        tea_in = []
+        zev = None
+        if use_unsup:
+            # the teacher pass only meets the student at the loss: it runs on its own HIP stream, concurrently
+            # with the student's forward pass (the two fill each other's launch tails and memory stalls)
+            main = torch.cuda.current_stream()
+            # Pi model (teacher IS the student): one network, one executor -- its lazily refreshed operand tables
+            # (BN affine, ASPP weights) must not be rewritten on one stream while the other reads them
+            side = self._teacher_stream() if (cfg.overlap_teacher and self.teacher is not self.student) else main
+            early = side is not main and cfg.early_teacher_fork
+            if early:
+                # (round 5) the teacher's inputs are the caller's tensors: its stream forks HERE -- behind last step's optimizer /
+                # EMA writes, in front of this step's gradient clear, paste and concatenation on the main stream, which it does not need
+                side.wait_stream(main)
+            zev = self._zero_grad(main)
+            for ub in unsup_batches:
+                tea_in.append(ub.x0_tea)
+                if cfg.mix:
+                    tea_in.append(ub.x1_tea)
+            if early:
+                with torch.cuda.stream(side):
+                    x_tea = torch.cat(tea_in, dim=0) if len(tea_in) > 1 else tea_in[0]
+            for ub in unsup_batches:
+                stu_in.append(self._student_inputs(ub))
+            if not early:
+                x_tea = torch.cat(tea_in, dim=0) if len(tea_in) > 1 else tea_in[0]
+                if side is not main:
+                    side.wait_stream(main)              # inputs (and last step's optimizer / EMA writes) are ready
+        else:
+            self.student_optim.zero_grad()
+        x_stu = torch.cat(stu_in, dim=0) if len(stu_in) > 1 else stu_in[0]
+        if use_unsup and side is not main and self._both_on_executor():
+            # both bodies on the MFMA executor: issue them interleaved, bottleneck by bottleneck
+            from .backbone_hip import run_body_pair
+            with torch.cuda.stream(side), torch.no_grad():
+                xt = self.teacher.stem_nhwc(x_tea)
+            xs = self.student.stem_nhwc(x_stu)
+            stu_lo, tea_lo = run_body_pair(self.student.hip_executor(), xs, self.teacher.hip_executor(), xt, side)
+        else:
+            if use_unsup:
+                with torch.cuda.stream(side), torch.no_grad():
+                    tea_lo = self.teacher.forward_lowres(x_tea)
+            stu_lo = self.student.forward_lowres(x_stu)
+        # dense NCHW scratch for the loss kernels (stu_lo itself may be channels-last strided)
+        grad_lo = torch.zeros(stu_lo.shape, dtype=torch.float32, device=stu_lo.device)
+        lo_det = stu_lo.detach()
+        # the supervised loss needs nothing from the teacher: its kernels are issued BEFORE the join and overlap the tail
+        # of the teacher's pass on the other stream
+        # Two independent branches between the forward passes and the backward pass: the supervised loss (student logits
+        # only) and the consistency loss (student + teacher logits). Each is a forward + backward kernel pair that is
+        # latency-bound on a few MB (DESIGN 4.3) -- they write disjoint slices of grad_lo and run CONCURRENTLY: the
+        # consistency branch on the teacher's stream (behind the teacher's pass, where its second operand comes from),
+        # the cross entropy on the main stream.
+        split = use_unsup and side is not main and cfg.overlap_losses
+        if split:
+            side.wait_stream(main)                  # the student's logits (and grad_lo's zero fill)
+        else:
+            if use_unsup and side is not main:
+                main.wait_stream(side)
+        cons_vals = []
+
+        def consistency_branch():
+            s_off, t_off = n_sup, 0
+            for ub in unsup_batches:
+                n = ub.x0_tea.shape[0]
+                l0 = tea_lo[t_off:t_off + n]
+                l1 = tea_lo[t_off + n:t_off + 2 * n] if cfg.mix else None
+                t_off += 2 * n if cfg.mix else n
+                if cfg.fused_losses:
+                    # (round 6) loss + gradient in ONE launch; grad_lo's rows are zero here (filled above, disjoint per branch)
+                    sc = ops.consistency_fused(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size, grad_lo[s_off:s_off + n],
+                                               ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
+                                               cons_weight=cfg.cons_weight, group=self.group)
+                else:
+                    sc, cctx = ops.consistency_forward(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size,
+                                                       ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
+                                                       cons_weight=cfg.cons_weight, group=self.group)
+                    ops.consistency_backward(cctx, sc, grad_lo[s_off:s_off + n])
+                s_off += n
+                if split and isinstance(sc, torch.Tensor):
+                    sc.record_stream(main)          # allocated on the teacher's stream, read (and freed) on the main one
+                cons_vals.append(sc)
+        if split:
+            with torch.cuda.stream(side):
+                consistency_branch()
+        if cfg.fused_losses:
+            ce_sc = ops.ce_fused(lo_det[:n_sup], sup_y, grad_lo[:n_sup], out_size, 255, self.align_corners, group=self.group)
+        else:
+            ce_sc, ce_ctx = ops.ce_forward(lo_det[:n_sup], sup_y, out_size, 255, self.align_corners, group=self.group)
+            ops.ce_backward(ce_ctx, ce_sc, grad_lo[:n_sup])
+        sex = self._student_executor()
+        if split:
+            # the re-pack of the data-gradient operands (one HBM-bound launch, ~0.12 ms, needs only the weights) is due in
+            # front of the backward pass: issued HERE it runs beside the consistency kernels of the other stream instead
+            # of alone behind the join
+            if independent and groups is None and sex is not None and hasattr(sex, '_refresh_for_backward'):
+                sex._refresh_for_backward()          # (frozen-statistics passes: the chain that uses these operands)
+            main.wait_stream(side)
+        elif use_unsup:
+            consistency_branch()
+        ex = self._arm_buckets() or self._arm_early_optimizer()
+        # the join of the weight-gradient stream moves from the end of the body's backward to where the gradients are next
+        # touched (exchange / optimizer, below): the stem's backward overlaps the last weight gradients
+        dex = sex if sex is not None and hasattr(sex, 'join_wgrad') else None
+        if dex is not None:
+            dex.defer_wgrad_join = cfg.defer_wgrad_join
+        if zev is not None:
+            main.wait_event(zev)                    # the gradient clear issued on the weight-gradient stream at the head of the step
+        try:
+            stu_lo.backward(grad_lo.to(stu_lo.dtype))
+        finally:
+            if ex is not None:
+                ex.grad_hook = None
+            if dex is not None:
+                dex.defer_wgrad_join = False
+                dex.join_wgrad()
+        return ce_sc, cons_vals
 
     # ------------------------------------------------------------------------------------------ the iteration
     def __call__(self, sup_x, sup_y, unsup_batches, ramp_val=1.0):
@@ -518,181 +616,31 @@ class CutMixMeanTeacherStep(object):
         cfg = self.cfg
         out_size = sup_x.shape[2:4]
         use_unsup = cfg.cons_weight > 0.0 and len(unsup_batches) > 0
-        n_sup = sup_x.shape[0]
         ramp = ramp_val if cfg.rampup > 0 else 1.0
 
         independent = self._samples_independent()
-        groups = None if (independent or not cfg.fuse_batches) else self._sample_groups(n_sup, unsup_batches, use_unsup)
-        if cfg.fuse_batches and (independent or groups is not None):
-            if groups is not None:
-                self.student.set_sample_groups(groups[0])
-                if use_unsup:
-                    self.teacher.set_sample_groups(groups[1])
-            self.__dict__['_groups_armed'] = groups is not None      # restored by _fused_iteration_done, whatever raises
+        groups = None if (independent or not cfg.fuse_batches) else self._sample_groups(sup_x.shape[0], unsup_batches, use_unsup)
+        if groups is not None:
+            self.student.set_sample_groups(groups[0])
+            if use_unsup:
+                self.teacher.set_sample_groups(groups[1])
         try:
-            return self._train_step_body(sup_x, sup_y, unsup_batches, ramp_val, groups, independent, use_unsup, n_sup, ramp,
-                                         out_size)
+            if cfg.fuse_batches and (independent or groups is not None):
+                ce_sc, cons_vals = self._fused_passes(sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup, independent, groups)
+            else:
+                ce_sc, cons_vals = self._separate_or_graphed(sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup)
+
+            ops.join_side_streams()           # weight gradients the layer engines issued on side streams (ops.layer_wgrad_stream)
+            self._allreduce_grads()
+            if self._early_armed:
+                self._early_armed = False
+                torch.cuda.current_stream().wait_stream(self._opt_stream)       # the early slices of this step's update
+            self.student_optim.step()
+            if self.teacher_optim is not None:
+                self.teacher_optim.step()
+            self._post_nan_probe(ce_sc[0])
+            return step_result(ce_sc, cons_vals)
         finally:
-            if self.__dict__.pop('_groups_armed', False):
+            if groups is not None:            # whatever raises
                 self.student.set_sample_groups(1)
                 self.teacher.set_sample_groups(1)
-
-    def _train_step_body(self, sup_x, sup_y, unsup_batches, ramp_val, groups, independent, use_unsup, n_sup, ramp, out_size):
-        cfg = self.cfg
-        if cfg.fuse_batches and (independent or groups is not None):
-            stu_in = [sup_x]
-            tea_in = []
-            if use_unsup:
-                # the teacher pass only meets the student at the loss: it runs on its own HIP stream, concurrently
-                # with the student's forward pass (the two fill each other's launch tails and memory stalls)
-                main = torch.cuda.current_stream()
-                # Pi model (teacher IS the student): one network, one executor -- its lazily refreshed operand tables
-                # (BN affine, ASPP weights) must not be rewritten on one stream while the other reads them
-                side = self._teacher_stream() if (cfg.overlap_teacher and self.teacher is not self.student) else main
-                early = side is not main and cfg.early_teacher_fork
-                if early:
-                    # (round 5) the teacher's inputs are the caller's tensors: its stream forks HERE -- behind last step's optimizer /
-                    # EMA writes, in front of this step's gradient clear, paste and concatenation on the main stream, which it does not need
-                    side.wait_stream(main)
-                self._zero_grad(main)
-                for ub in unsup_batches:
-                    tea_in.append(ub.x0_tea)
-                    if cfg.mix:
-                        tea_in.append(ub.x1_tea)
-                if early:
-                    with torch.cuda.stream(side):
-                        x_tea = torch.cat(tea_in, dim=0) if len(tea_in) > 1 else tea_in[0]
-                for ub in unsup_batches:
-                    stu_in.append(self._student_inputs(ub))
-                if not early:
-                    x_tea = torch.cat(tea_in, dim=0) if len(tea_in) > 1 else tea_in[0]
-                    if side is not main:
-                        side.wait_stream(main)              # inputs (and last step's optimizer / EMA writes) are ready
-            else:
-                self.student_optim.zero_grad()
-            x_stu = torch.cat(stu_in, dim=0) if len(stu_in) > 1 else stu_in[0]
-            if use_unsup and side is not main and self._both_on_executor():
-                # both bodies on the MFMA executor: issue them interleaved, bottleneck by bottleneck
-                from .backbone_hip import run_body_pair
-                with torch.cuda.stream(side), torch.no_grad():
-                    xt = self.teacher.stem_nhwc(x_tea)
-                xs = self.student.stem_nhwc(x_stu)
-                stu_lo, tea_lo = run_body_pair(self.student.hip_executor(), xs, self.teacher.hip_executor(), xt, side)
-            else:
-                if use_unsup:
-                    with torch.cuda.stream(side), torch.no_grad():
-                        tea_lo = self.teacher.forward_lowres(x_tea)
-                stu_lo = self.student.forward_lowres(x_stu)
-            # dense NCHW scratch for the loss kernels (stu_lo itself may be channels-last strided)
-            grad_lo = torch.zeros(stu_lo.shape, dtype=torch.float32, device=stu_lo.device)
-            lo_det = stu_lo.detach()
-            # the supervised loss needs nothing from the teacher: its kernels are issued BEFORE the join and overlap the tail
-            # of the teacher's pass on the other stream
-            # Two independent branches between the forward passes and the backward pass: the supervised loss (student logits
-            # only) and the consistency loss (student + teacher logits). Each is a forward + backward kernel pair that is
-            # latency-bound on a few MB -- they write disjoint slices of grad_lo and run CONCURRENTLY: the
-            # consistency branch on the teacher's stream (behind the teacher's pass, where its second operand comes from),
-            # the cross entropy on the main stream.
-            split = use_unsup and side is not main and cfg.overlap_losses
-            if split:
-                side.wait_stream(main)                  # the student's logits (and grad_lo's zero fill)
-            else:
-                if use_unsup and side is not main:
-                    main.wait_stream(side)
-            cons_vals = []
-            # (round 5) the consistency branch is the longer of the two (forward 0.12 + backward 0.17 ms against 0.05 + 0.10 for the
-            # cross entropy): when the branches run on two streams, the SECOND half of the samples of its backward is issued on the main
-            # stream behind the cross entropy (per-pixel work, independent between samples; it only needs the finalised scalars).
-            # Measured slower (StepConfig.split_cons_bwd): off by default
-            deferred = []                   # (context, scalars, grad rows, (s0, s1), event): backward halves the main stream takes
-
-            def consistency_branch():
-                s_off, t_off = n_sup, 0
-                for ub in unsup_batches:
-                    n = ub.x0_tea.shape[0]
-                    l0 = tea_lo[t_off:t_off + n]
-                    l1 = tea_lo[t_off + n:t_off + 2 * n] if cfg.mix else None
-                    t_off += 2 * n if cfg.mix else n
-                    if self.cfg.fused_losses and not (split and self.cfg.split_cons_bwd and n >= 2):
-                        # (round 6) loss + gradient in ONE launch; grad_lo's rows are zero here (filled above, disjoint per branch)
-                        sc = ops.consistency_fused(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size, grad_lo[s_off:s_off + n],
-                                                   ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
-                                                   cons_weight=cfg.cons_weight, group=self.group)
-                        s_off += n
-                        if split and isinstance(sc, torch.Tensor):
-                            sc.record_stream(main)
-                        cons_vals.append(sc)
-                        continue
-                    sc, cctx = ops.consistency_forward(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size,
-                                                       ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
-                                                       cons_weight=cfg.cons_weight, group=self.group)
-                    if split and self.cfg.split_cons_bwd and n >= 2:
-                        ev = torch.cuda.Event()
-                        ev.record()                                       # scalars final on the teacher's stream
-                        ops.consistency_backward(cctx, sc, grad_lo[s_off:s_off + n], samples=(0, n // 2))
-                        deferred.append((cctx, sc, grad_lo[s_off:s_off + n], (n // 2, n), ev))
-                    else:
-                        ops.consistency_backward(cctx, sc, grad_lo[s_off:s_off + n])
-                    s_off += n
-                    if split and isinstance(sc, torch.Tensor):
-                        sc.record_stream(main)          # allocated on the teacher's stream, read (and freed) on the main one
-                    cons_vals.append(sc)
-            if split:
-                with torch.cuda.stream(side):
-                    consistency_branch()
-            if self.cfg.fused_losses:
-                ce_sc = ops.ce_fused(lo_det[:n_sup], sup_y, grad_lo[:n_sup], out_size, 255, self.align_corners, group=self.group)
-            else:
-                ce_sc, ce_ctx = ops.ce_forward(lo_det[:n_sup], sup_y, out_size, 255, self.align_corners, group=self.group)
-                ops.ce_backward(ce_ctx, ce_sc, grad_lo[:n_sup])
-            for cctx, sc, rows, rng_, ev in deferred:
-                main.wait_event(ev)
-                ops.consistency_backward(cctx, sc, rows, samples=rng_)
-            if split:
-                # the re-pack of the data-gradient operands (one HBM-bound launch, ~0.12 ms, needs only the weights) is due in
-                # front of the backward pass: issued HERE it runs beside the consistency kernels of the other stream instead
-                # of alone behind the join
-                pre = getattr(self.student, 'hip_executor', None)
-                if independent and groups is None and pre is not None and getattr(self.student, '_use_hip_body', None) \
-                        and self.student._use_hip_body() and hasattr(pre(), '_refresh_for_backward'):
-                    pre()._refresh_for_backward()        # (frozen-statistics passes: the chain that uses these operands)
-                main.wait_stream(side)
-            elif use_unsup:
-                consistency_branch()
-            ex = self._arm_buckets() or self._arm_early_optimizer()
-            # the join of the weight-gradient stream moves from the end of the body's backward to where the gradients are next
-            # touched (exchange / optimizer, below): the stem's backward overlaps the last weight gradients
-            dex = self.student.hip_executor() if (getattr(self.student, '_use_hip_body', None) and self.student._use_hip_body()
-                                                  and hasattr(self.student.hip_executor(), 'join_wgrad')) else None
-            if dex is not None:
-                dex.defer_wgrad_join = self.cfg.defer_wgrad_join
-            zev = self.__dict__.pop('_zero_grad_event', None)
-            if zev is not None:
-                main.wait_event(zev)                    # the gradient clear issued on the weight-gradient stream at the head of the step
-            try:
-                stu_lo.backward(grad_lo.to(stu_lo.dtype))
-            finally:
-                if ex is not None:
-                    ex.grad_hook = None
-                if dex is not None:
-                    dex.defer_wgrad_join = False
-                    dex.join_wgrad()
-        else:
-            ce_sc, cons_vals = self._separate_or_graphed(sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup)
-
-        ops.join_side_streams()           # weight gradients the layer engines issued on side streams (ops.layer_wgrad_stream)
-        self._allreduce_grads()
-        if self.__dict__.pop('_early_armed', False):
-            torch.cuda.current_stream().wait_stream(self._opt_stream)       # the early slices of this step's update
-        self.student_optim.step()
-        if self.teacher_optim is not None:
-            self.teacher_optim.step()
-
-        sup_loss = ce_sc[0]
-        self._post_nan_probe(sup_loss)
-        res = dict(sup_loss=sup_loss, consistency_loss=None, conf_rate=None)
-        if cons_vals:
-            stacked = torch.stack(cons_vals)
-            res['consistency_loss'] = stacked[:, 0].mean()
-            res['conf_rate'] = stacked[:, 1].mean()
-        return res

@@ -30,6 +30,8 @@ import os
 import torch
 
 from . import ops
+from .graph_replay import GraphReplay
+from .step import step_result, supervised_pass, world_size
 
 
 def normalize_eps(x):
@@ -148,8 +150,7 @@ class VATMeanTeacherStep(object):
         self.generator = generator
         self.align_corners = getattr(student_net, 'upsample_align_corners', True)
         cfg.cons.align_corners = self.align_corners
-        import torch.distributed as dist
-        self.world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+        self.world = world_size(group)
         # (round 6) the gradient passes as one hipGraph launch (see _graphed_grads)
         # Default ('auto'): ON for networks that run layer by layer through the Python layer engines (the U-Nets: 51.7 -> 76.4 img/s on
         # the DenseNet-161 U-Net, 185.8 -> 209.4 on the ResNet-50 U-Net, profiles/r06bc_*), OFF for the DeepLab networks, whose passes
@@ -158,7 +159,7 @@ class VATMeanTeacherStep(object):
         layerwise = not any(hasattr(student_net, a) for a in ('_use_hip_body', '_use_hip_backbone'))
         self.use_graph = env == '1' or (env not in ('0', '1') and layerwise)
         self.graph_warmup = 2
-        self._graphs = {}
+        self._graphs = GraphReplay('the VAT gradient passes', 'CMS_VAT_GRAPH')
 
     # ------------------------------------------------------------------------------------------ the gradient passes
     def _grads(self, sup_x, sup_y, unsup_batches, ramp, eps0, teacher_early=False):
@@ -189,9 +190,7 @@ class VATMeanTeacherStep(object):
                             x_perturb, _ = vat_perturbation(self.vat_dir_net, ub.x_tea, ub.x_stu, cfg.vat_radius, cfg.adaptive,
                                                             cfg.cons_loss_fn, eps0=eps0, generator=self.generator)
                             adv_early.append((ub.x_stu.float() + x_perturb).to(ub.x_stu.dtype))
-        lo = self.student.forward_lowres(sup_x)
-        ce_sc, ce_ctx = ops.ce_forward(lo.detach(), sup_y, out_size, 255, self.align_corners, group=self.group)
-        lo.backward(ops.ce_backward(ce_ctx, ce_sc).to(lo.dtype))
+        ce_sc = supervised_pass(self.student, sup_x, sup_y, out_size, self.align_corners, self.group)
         cons_vals = []
         if cfg.cons_weight > 0.0:
             if adv_early is not None:
@@ -220,15 +219,8 @@ class VATMeanTeacherStep(object):
         return ce_sc, cons_vals
 
     # ------------------------------------------------------------------------------------------ hipGraph replay (round 6)
-    def _graph_key(self, sup_x, sup_y, unsup_batches, ramp, eps0):
-        def sig(t):
-            return None if t is None else (tuple(t.shape), t.dtype, t.device.index)
-        return (sig(sup_x), sig(sup_y), tuple((sig(u.x_tea), sig(u.x_stu), sig(u.um), u.x_stu is u.x_tea) for u in unsup_batches),
-                float(ramp), sig(eps0), self.student.training, self.teacher.training, self.vat_dir_net.training,
-                getattr(self.student, 'compute_dtype', None), getattr(self.teacher, 'compute_dtype', None))
-
     def _graphed_grads(self, sup_x, sup_y, unsup_batches, ramp, eps0):
-        """The gradient passes as ONE hipGraph launch. The layer engines of the U-Nets issue ~9 000 launches per VAT iteration
+        """The gradient passes as ONE hipGraph launch (the protocol: graph_replay.GraphReplay). The layer engines of the U-Nets issue ~9 000 launches per VAT iteration
         through Python autograd: 169 ms of host work per 213 ms step of the DenseNet-161 U-Net (profiles/r06i_*) -- the GPU waits
         for the host. After `graph_warmup` eager iterations of a (shapes, modes, ramp) signature (lazy initialisation, stream probe,
         BatchNorm modes settled: the direction network goes to eval() in its first iteration and stays there, :237) the passes
@@ -237,68 +229,20 @@ class VATMeanTeacherStep(object):
         gradients into the arena -- is device work of the same kernels. Outside the graph: gradient exchange, optimizer, EMA.
         Not captured: a ramp that still changes (`rampup > 0` while ramp < 1 would need a graph per value: those iterations run
         eagerly), data parallelism (SyncBN host operations)."""
-        key = self._graph_key(sup_x, sup_y, unsup_batches, ramp, eps0)
-        ent = self._graphs.get(key)
-        if ent is None:
-            ent = self._graphs[key] = {'seen': 0}
-        if 'graph' not in ent:
-            ent['seen'] += 1
-            if ent['seen'] <= self.graph_warmup or ent.get('failed'):
-                return self._grads(sup_x, sup_y, unsup_batches, ramp, eps0)
-            # static inputs
-            st = {'sup_x': sup_x.clone(), 'sup_y': sup_y.clone(), 'eps0': None if eps0 is None else eps0.clone(), 'ubs': []}
-            for u in unsup_batches:
-                xt = u.x_tea.clone()
-                xs = xt if u.x_stu is u.x_tea else u.x_stu.clone()
-                st['ubs'].append(VATUnsupBatch(xt, xs, None if u.um is None else u.um.clone()))
-            # operands derived from the weights (padded / transposed copies) are cached per weight version by the eager path: the
-            # capture must contain their refresh, so both arenas are marked stale first
-            for net in (self.student, self.teacher):
-                a = getattr(net, '_cms_arena', None)
-                if a is not None:
-                    a.touch()
-            # everything lazy that synchronises must have happened BEFORE the capture: the side-stream probe above all (a trainer whose
-            # eager iterations never asked for a pooled stream met it inside the capture: `operation not permitted when stream is capturing`)
-            ops.pooled_stream(sup_x.device, 'teacher')
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            if self.generator is not None and hasattr(g, 'register_generator_state'):
-                g.register_generator_state(self.generator)
-            # one capture stream by default; CMS_VAT_GRAPH_SIDE=1: the layer engines' side streams fork / join inside the capture
-            prev = ops.set_side_streams_enabled(os.environ.get('CMS_VAT_GRAPH_SIDE', '0') == '1')
-            try:
-                with torch.cuda.graph(g):
-                    ce_sc, cons_vals = self._grads(st['sup_x'], st['sup_y'], st['ubs'], ramp, st['eps0'],
-                                                   teacher_early=os.environ.get('CMS_VAT_GRAPH_TEACHER_EARLY', '1') != '0')
-            except Exception as e:               # noqa: BLE001 -- an operation the capture cannot hold (nothing ran on the device)
-                import warnings
-                warnings.warn('cutmix-semisup-seg_amd: the VAT gradient passes could not be captured into a hipGraph ({}: {}); this '
-                              'signature keeps running launch by launch'.format(type(e).__name__, str(e).splitlines()[0] if str(e) else ''),
-                              RuntimeWarning, stacklevel=2)
-                ent['failed'] = True
-                try:
-                    torch.cuda.synchronize()
-                except Exception as e2:          # noqa: BLE001 -- a forked stream is still inside the aborted capture: this process cannot launch any more
-                    raise RuntimeError('a failed hipGraph capture left the device in capture mode ({}); restart with {}=0 (launch by launch) '
-                                       'and report the operation named in the warning above'.format(e2, 'CMS_VAT_GRAPH')) from e
-                return self._grads(sup_x, sup_y, unsup_batches, ramp, eps0)
-            finally:
-                ops.set_side_streams_enabled(prev)
-            ent.update(graph=g, static=st, out=(ce_sc, cons_vals))
-        st = ent['static']
-        st['sup_x'].copy_(sup_x)
-        st['sup_y'].copy_(sup_y)
-        if eps0 is not None:
-            st['eps0'].copy_(eps0)
-        for su, u in zip(st['ubs'], unsup_batches):
-            su.x_tea.copy_(u.x_tea)
-            if su.x_stu is not su.x_tea:
-                su.x_stu.copy_(u.x_stu)
-            if u.um is not None:
-                su.um.copy_(u.um)
-        ent['graph'].replay()
-        ce_sc, cons_vals = ent['out']
-        return ce_sc.clone(), [c.clone() for c in cons_vals]
+        flat = [sup_x, sup_y, eps0]
+        for u in unsup_batches:
+            flat += [u.x_tea, u.x_stu, u.um]
+        extra = (float(ramp), self.student.training, self.teacher.training, self.vat_dir_net.training,
+                 getattr(self.student, 'compute_dtype', None), getattr(self.teacher, 'compute_dtype', None))
+
+        def passes(ts, capturing):
+            ubs = [VATUnsupBatch(*ts[i:i + 3]) for i in range(3, len(ts), 3)]
+            early = capturing and os.environ.get('CMS_VAT_GRAPH_TEACHER_EARLY', '1') != '0'
+            return self._grads(ts[0], ts[1], ubs, ramp, ts[2], teacher_early=early)
+
+        # one capture stream by default; CMS_VAT_GRAPH_SIDE=1: the layer engines' side streams fork / join inside the capture
+        return self._graphs.run(flat, extra, passes, nets=(self.student, self.teacher), device=sup_x.device, generator=self.generator,
+                                side_streams=os.environ.get('CMS_VAT_GRAPH_SIDE', '0') == '1', warmup=self.graph_warmup)
 
     def __call__(self, sup_x, sup_y, unsup_batches, ramp_val=1.0, eps0=None):
         cfg = self.cfg
@@ -315,9 +259,4 @@ class VATMeanTeacherStep(object):
         self.student_optim.step()
         if self.teacher_optim is not None:
             self.teacher_optim.step()
-        res = dict(sup_loss=ce_sc[0], consistency_loss=None, conf_rate=None)
-        if cons_vals:
-            stacked = torch.stack(cons_vals)
-            res['consistency_loss'] = stacked[:, 0].mean()
-            res['conf_rate'] = stacked[:, 1].mean()
-        return res
+        return step_result(ce_sc, cons_vals)
