@@ -25,7 +25,6 @@ samples of a batch are not independent, so the training step keeps the reference
 (step.py: fuse_batches=False). The backbone on the hand-written MFMA convolution kernels is the next step for this
 row.
 """
-import os
 
 import numpy as np
 import torch
@@ -130,9 +129,8 @@ class ASPP(nn.Module):
         dilated 3 x 3 over 2048 channels is ONE 85-tile launch on 256 CUs (0.9 ms each, forward; 0.65 ms its data gradient): two of
         the three heavy branches run on the pooled weight-gradient streams (idle in a forward pass), forked from the current
         stream and joined before the concat. autograd runs a node's backward on the stream its forward ran on, so the branches'
-        backward chains overlap the same way. CMS_ASPP_STREAMS=0: one after the other on the current stream (rounds 1-5)."""
-        import os
-        if not on_device or os.environ.get('CMS_ASPP_STREAMS', '1') == '0' or ops._REC is not None or not ops.side_streams_enabled() or len(convs) < 3:
+        backward chains overlap the same way."""
+        if not on_device or ops._REC is not None or not ops.side_streams_enabled() or len(convs) < 3:
             return [eng.conv_bn_act(xi, m[0], m[1], relu=True) for xi, m in zip(xs, convs)]
         cur = torch.cuda.current_stream()
         sides = [ops.pooled_stream(xs[0].device, 'wgrad0'), ops.pooled_stream(xs[0].device, 'wgrad1')]
@@ -288,8 +286,7 @@ class HipConvEngine(LayerEngine):
         if bn is not None and bn.training:
             self.__dict__.get('_frozen_affines', {}).pop(id(bn), None)      # (its running statistics move: a cached affine is stale)
         if (bn is not None and not bn.training and y.is_cuda and y.shape[1] % 8 == 0 and not bn.weight.requires_grad
-                and not bn.bias.requires_grad and bn.running_mean is not None and y.dtype in (torch.bfloat16, torch.float32)
-                and os.environ.get('CMS_FROZEN_BN_FUSED', '1') != '0'):
+                and not bn.bias.requires_grad and bn.running_mean is not None and y.dtype in (torch.bfloat16, torch.float32)):
             # (round 6) eval-mode BatchNorm with a non-trainable affine (the teacher of the VAT trainer: three passes over ~170 such
             # layers per iteration of the DenseNet-161 U-Net) as ONE launch: the tensor-op form below is ~9 launches forward (rsqrt,
             # two multiplies, subtract, two casts, addcmul, add, ReLU) and 4 backward. scale / shift: once per weight version.

@@ -105,6 +105,17 @@ class DeepLabHipExecutor(object):
         self._bn_idx = None
         self._side = None
         self._pack_plan = None
+        # created on first use (each by the method that reads it)
+        self._pack_plan_bn = None       # `_refresh_backward_weights_bn`
+        self._wT_raw_version = -1       # weight version the batch-statistics dgrad operands were packed for
+        self._bn_modules = {}           # BatchNorm prefix -> module (`_bn_module`)
+        self._stem_param = None         # the stem's weight parameter (`stem`)
+        self._sentinel = None           # `_grad_sentinel`
+        self._seen_shapes = {}          # gradient-free shapes seen once (`_eager_this_time`)
+        self._wscratch_buf = None       # `_wscratch`
+        self._wfinish_pending = []      # convolutions whose gradient waits in the scratch tensor (`_wfinish_flush`)
+        self._wfinish_ok = {}           # `_wfinish_takes`
+        self._pending_keep = None       # `_retire_keep`
         self.grad_hook = None      # callable(block_index): weight gradients of that bottleneck are enqueued
         self.data_grad_only = False   # backward computes d/d input only (VAT direction: torch.autograd.grad wrt eps)
         self.overlap_wgrad = True
@@ -113,16 +124,9 @@ class DeepLabHipExecutor(object):
         # data-gradient chain was enough (profiles/r02f_wgrad_streams.txt: 1 -> 443-445 img/s, 2 -> 433, 3 -> 443). The
         # eight-phase 256 x 256 kernel (csrc/wgrad8.hip) puts ~56 workgroups = 56 CUs behind a launch: TWO streams of them
         # fill the ~124 CUs the data-gradient convolution (132 tiles, one per CU) leaves free (profiles/r04ag-ai_*: 1 stream
-        # 561 img/s at its best split, 2 streams 575-601, 3 streams 500-563). CMS_WGRAD_STREAMS overrides (A/B switch).
-        self.wgrad_streams = int(os.environ.get('CMS_WGRAD_STREAMS', '2' if os.environ.get('CMS_WGRAD8', '1') != '0' else '1'))
-        # Weight gradients of this many consecutive bottlenecks go out as ONE grouped launch per kind (ops.conv_wgrad_group)
-        # on the weight-gradient stream, behind the data-gradient chain of the stretch; 0 = one launch per layer (round 1-3).
-        # CMS_WGRAD_GROUP sets it (A/B switch, read once).
-        self.wgrad_group_blocks = int(os.environ.get('CMS_WGRAD_GROUP', '0'))
-        # ReLU masks of the block outputs as bits (written by the expansion's epilogue, read by the data gradients that need the
-        # activation only for its sign); CMS_RELU_BITS=0 switches them off (A/B)
-        self.relu_bits = os.environ.get('CMS_RELU_BITS', '1') != '0'
-        self.relu_bits_inner = os.environ.get('CMS_RELU_BITS_INNER', '1') != '0'     # ... of a1 / a2 as well (round 5; A/B)
+        # 561 img/s at its best split, 2 streams 575-601, 3 streams 500-563).
+        # (grouped launches over several bottlenecks, ops.conv_wgrad_group: measured, not adopted -- see docs/DESIGN_HISTORY.md)
+        self.wgrad_streams = 2 if os.environ.get('CMS_WGRAD8', '1') != '0' else 1
         # The backward pass normally ends with the main stream waiting for the weight-gradient stream(s): whoever reads a
         # gradient afterwards finds it complete. A caller that knows where it next touches the gradients (the training step:
         # at the gradient exchange / optimizer) sets this and calls `join_wgrad()` there instead -- what follows the body's
@@ -130,11 +134,6 @@ class DeepLabHipExecutor(object):
         # gradients (0.37 ms of small launches, profiles/r04n_step_timeline.txt) instead of waiting for it.
         self.defer_wgrad_join = False
         self._pending_join = None
-        self.head_wgrad_side = os.environ.get('CMS_HEAD_WGRAD_SIDE', '1') != '0'
-        # EXPERIMENT (round 5, CMS_FWD_SPLIT bit 0: trainable network, bit 1: network without gradients): a recorded frozen-BN forward
-        # pass issues every convolution as TWO launches over the halves of the batch on two streams (samples are independent; both
-        # halves write slices of the same buffers, so the backward pass is unchanged): more, smaller launches in flight
-        self.fwd_split = int(os.environ.get('CMS_FWD_SPLIT', '0'))
         self._sides = []
         self.conv_tile = 0         # experiment knob: force a tile shape on the 128-multiple layers (tools, bench)
         self.tile_rules = {}       # output channels -> tile code (per-layer choice against the workgroup-count staircase)
@@ -278,25 +277,14 @@ class DeepLabHipExecutor(object):
     def _out_hw(h, w, stride):
         return (h - 1) // stride + 1, (w - 1) // stride + 1
 
-    def _fwd(self, x, c, relu, res=None, bits=False, halves=None):
+    def _fwd(self, x, c, relu, res=None, bits=False):
         """`bits`: also write the ReLU mask of the output as bits (cms_conv_desc.mask_bits_out) and hang them on the returned
-        tensor (`_cms_relu_bits`): the data gradient that needs this activation only for its sign reads 1/16 of the bytes.
-        `halves`: two streams -- the launch goes out as two, over the two halves of the batch (see `fwd_split`)."""
+        tensor (`_cms_relu_bits`): the data gradient that needs this activation only for its sign reads 1/16 of the bytes."""
         n, h, w, _ = x.shape
         ho, wo = self._out_hw(h, w, c.stride)
         mb = None
-        if bits and relu and self.relu_bits and self.dtype == torch.bfloat16 and c.cout % 32 == 0:
+        if bits and relu and self.dtype == torch.bfloat16 and c.cout % 32 == 0:
             mb = torch.empty((n, ho, wo, c.cout // 8), dtype=torch.uint8, device=x.device)
-        if halves is not None:
-            y = torch.empty((n, ho, wo, c.cout), dtype=x.dtype, device=x.device)
-            for hi, (s0, s1) in enumerate(((0, n // 2), (n // 2, n))):
-                with torch.cuda.stream(halves[hi]):
-                    ops.conv_igemm(x[s0:s1], self._w(c), c.taps, stride=c.stride, out_hw=(ho, wo), scale=c.scale, bias=c.bias,
-                                   res=None if res is None else res[s0:s1], relu=relu, tile=self._tile(c.cout),
-                                   mask_bits_out=None if mb is None else mb[s0:s1], out=y[s0:s1])
-            if mb is not None:
-                y._cms_relu_bits = mb
-            return y
         y = ops.conv_igemm(x, self._w(c), c.taps, stride=c.stride, out_hw=(ho, wo), scale=c.scale, bias=c.bias,
                            res=res, relu=relu, tile=self._tile(c.cout), mask_bits_out=mb)
         if mb is not None:
@@ -326,12 +314,11 @@ class DeepLabHipExecutor(object):
         b, cur = self.blocks[bi], st['cur']
         # (round 5) a1 / a2 get mask bits too: both kernels of cms_conv_igemm write and read them (the library alone decides
         # which one runs a launch), so the data gradients of conv2 / conv3 no longer re-read these activations for their sign
-        inner = st['saved'] is not None and self.relu_bits_inner
-        hv = st.get('halves')
-        a1 = self._fwd(cur, b.c1, True, bits=inner, halves=hv)
-        a2 = self._fwd(a1, b.c2, True, bits=inner, halves=hv)
-        res = cur if b.cd is None else self._fwd(cur, b.cd, False, halves=hv)
-        st['cur'] = self._fwd(a2, b.c3, True, res=res, bits=st['saved'] is not None, halves=hv)
+        bits = st['saved'] is not None
+        a1 = self._fwd(cur, b.c1, True, bits=bits)
+        a2 = self._fwd(a1, b.c2, True, bits=bits)
+        res = cur if b.cd is None else self._fwd(cur, b.cd, False)
+        st['cur'] = self._fwd(a2, b.c3, True, res=res, bits=bits)
         if st['saved'] is not None:
             st['saved'].append((cur, a1, a2))
 
@@ -368,17 +355,16 @@ class DeepLabHipExecutor(object):
         return getattr(self.net, 'dist_group', None)
 
     def _bn_module(self, c):
-        mods = self.__dict__.setdefault('_bn_modules', {})
-        m = mods.get(c.bn)
+        m = self._bn_modules.get(c.bn)
         if m is None:
-            m = mods[c.bn] = self.net.get_submodule(c.bn)
+            m = self._bn_modules[c.bn] = self.net.get_submodule(c.bn)
         return m
 
     def _fwd_unit_bn(self, x, c, relu, res=None, save=True, groups=1):
         """y = relu(batch_norm(conv(x)) (+ res)) as THREE launches on persistent buffers: raw convolution (round 5: its epilogue
         leaves per-tile channel sums), statistics (round 5: adds the tile sums and finalises -- scale / shift, running statistics,
         batch counter; under data parallelism or in fp32: the atomics-free reduction over u of rounds 3-4), normalise + residual +
-        ReLU (+ the ReLU mask as bits). -> (y, saved), saved = (u, mask bits or y or None, mean, rstd, backward sums, workspace,
+        ReLU (+ the ReLU mask as bits). -> (y, saved), saved = (u, mask bits or None, mean, rstd, backward sums, workspace,
         groups) for `_bwd_unit_bn`. (/root/reference/architectures/deeplab2.py:72-84 in training mode.)"""
         n, h, w, _ = x.shape
         ho, wo = self._out_hw(h, w, c.stride)
@@ -388,7 +374,7 @@ class DeepLabHipExecutor(object):
         # (round 5) single process, bf16: the convolution's epilogue leaves per-tile channel sums of what it stores and the
         # statistics launch only adds those up -- the pass over u it used to be is gone (cms_conv_desc.stats_out)
         # (round 6) under data parallelism too: the tile sums become the per-group sums the ranks all-reduce (below)
-        st = {'groups': G} if (self.dtype == torch.bfloat16 and _fused_bn_stats()) else None
+        st = {'groups': G} if self.dtype == torch.bfloat16 else None
         u = ops.conv_igemm(x, self._w(c), c.taps, stride=c.stride, out_hw=(ho, wo), tile=self._tile(c.cout), stats=st)
         a, bn, C = self.arena, self._bn_module(c), c.cout
         npix = n * ho * wo
@@ -428,39 +414,33 @@ class DeepLabHipExecutor(object):
                       counter=bn.num_batches_tracked)
         y = torch.empty_like(u)
         # (round 5) the ReLU mask of the backward passes as BITS beside y: they then stream u, dy and 1/16 of a tensor instead of y
-        bits = torch.empty(npix * C // 8, dtype=torch.uint8, device=dev) if (relu and save and _bn_mask_bits()) else None
+        bits = torch.empty(npix * C // 8, dtype=torch.uint8, device=dev) if (relu and save) else None
         ops.bn_op('apply', c=C, dtype=self.dtype, n_pixels=npix, groups=G, relu=relu, x=u, res=res, y=y, scale=scale,
                   shift=shift, mask_bits=bits)
-        return y, (u, (y if bits is None else bits) if relu else None, mean, rstd, bsums, ws, G)
+        return y, (u, bits, mean, rstd, bsums, ws, G)
 
-    def _bstats(self, s, unit):
-        """Descriptor of a unit's backward statistics for the data-gradient launch that writes the gradient of its output
-        (`ops.conv_igemm(..., mode=1, stats=...)`, cms_conv_desc.bstats_*), or None: `s` = the unit's saved tuple, `unit` = 1 / 2 / 3.
-        CMS_BN_BWD_STATS (read per recording): 0 = off, 3 = the wide unit 3 only (default: 329.8 -> 335.1 img/s; every unit: 333 -- for the
-        narrow units the finalising launch costs what the reduction it replaces did, profiles/r05u_*), 1 = every unit."""
-        mode = os.environ.get('CMS_BN_BWD_STATS', '3')
-        # (round 6: under data parallelism too -- xhat uses the unit's GLOBAL mean / rstd, the per-tile sums are local and the
-        # per-group sums they add up to are all-reduced like the reduction kernel's, `_bwd_unit_bn`)
-        if mode == '0' or (mode == '3' and unit != 3) or self.dtype != torch.bfloat16:
+    def _bstats(self, s3):
+        """Descriptor of the backward statistics of a block's unit 3 for the data-gradient launch that writes the gradient of its output
+        (`ops.conv_igemm(..., mode=1, stats=...)`, cms_conv_desc.bstats_*), or None: `s3` = the unit's saved tuple. The wide unit 3 only
+        (329.8 -> 335.1 img/s; every unit: 333 -- for the narrow units the finalising launch costs what the reduction it replaces did,
+        profiles/r05u_*).
+        (round 6: under data parallelism too -- xhat uses the unit's GLOBAL mean / rstd, the per-tile sums are local and the
+        per-group sums they add up to are all-reduced like the reduction kernel's, `_bwd_unit_bn`)"""
+        if self.dtype != torch.bfloat16:
             return None
-        u, yb, mean, rstd, _sums, _ws, G = s
-        if yb is not None and yb.dtype != torch.uint8:
-            return None                         # the mask is the stored activation (CMS_BN_MASK_BITS=0): the reduction kernel reads it
-        return {'groups': G, 'u': u, 'mean': mean, 'rstd': rstd, 'bits': yb}
+        u, bits, mean, rstd, _sums, _ws, G = s3
+        return {'groups': G, 'u': u, 'mean': mean, 'rstd': rstd, 'bits': bits}
 
     def _bwd_unit_bn(self, dy, saved, c, want_res, dy_bits=None, tile_stats=None):
         """Backward of the normalisation of one unit: dy (gradient wrt y) -> (du = gradient wrt the convolution output,
-        dres = gradient wrt the residual input or None). The ReLU mask comes from the stored y."""
-        u, y, mean, rstd, sums, ws, G = saved   # `sums` is overwritten by the reduction; `ws`: the unit's workspace
+        dres = gradient wrt the residual input or None). The ReLU mask comes from the stored bits."""
+        u, bits, mean, rstd, sums, ws, G = saved   # `sums` is overwritten by the reduction; `ws`: the unit's workspace
         C = c.cout
         npix = u.numel() // C
-        bits = None
-        if y is not None and y.dtype == torch.uint8:        # the mask as bits (`_fwd_unit_bn`)
-            bits, y = y, None
         if dy_bits is not None:
             # `dy` arrives UNMASKED with the mask of the tensor it is the gradient of (the downsample unit behind a block output
             # whose masked gradient `dres` is no longer materialised): this unit has no ReLU of its own, the bits take its place
-            assert y is None and bits is None
+            assert bits is None
             bits = dy_bits
         if tile_stats is not None and tile_stats.get('tile_rows', 0) > 0:
             # (round 5) the launch that wrote dy left per-tile (sum d, sum d xhat): no pass over u, dy and the mask
@@ -468,7 +448,7 @@ class DeepLabHipExecutor(object):
             ops.bn_op('sums_tiles', c=C, dtype=self.dtype, n_pixels=npix, groups=G, tile_rows=tile_stats['tile_rows'],
                       ws=tile_stats['tile_sums'], sums=sums)
         else:
-            ops.bn_op('reduce_bwd', c=C, dtype=self.dtype, n_pixels=npix, groups=G, x=u, dy=dy, y=y, mean=mean, rstd=rstd, sums=sums,
+            ops.bn_op('reduce_bwd', c=C, dtype=self.dtype, n_pixels=npix, groups=G, x=u, dy=dy, mean=mean, rstd=rstd, sums=sums,
                       ws=ws, mask_bits=bits)
         grp = self._dist_group()
         world = ops._world(grp)
@@ -476,9 +456,8 @@ class DeepLabHipExecutor(object):
             ops.host_call(lambda t=sums, g_=grp: ops._allreduce_sum(t, g_))
         du = torch.empty_like(u)
         dres = torch.empty_like(u) if want_res else None
-        ops.bn_op('bwd_apply', c=C, dtype=self.dtype, n_pixels=npix, groups=G, count=(npix // G) * world, x=u, dy=dy, y=y, dx=du, dres=dres,
-                  mask_bits=bits, mean=mean,
-                  rstd=rstd, gamma=self.arena.view(c.bn + '.weight'), sums=sums)
+        ops.bn_op('bwd_apply', c=C, dtype=self.dtype, n_pixels=npix, groups=G, count=(npix // G) * world, x=u, dy=dy, dx=du, dres=dres,
+                  mask_bits=bits, mean=mean, rstd=rstd, gamma=self.arena.view(c.bn + '.weight'), sums=sums)
         return du, dres
 
     def _fwd_block_bn(self, st, bi):
@@ -499,7 +478,7 @@ class DeepLabHipExecutor(object):
     def _refresh_backward_weights_bn(self):
         """dgrad operands wT[tap][ci][co] = w^T (NO BatchNorm scale: the normalisation has its own backward) of all body
         convolutions + the head: one launch."""
-        if self.__dict__.get('_pack_plan_bn') is None:
+        if self._pack_plan_bn is None:
             triples = []
             for c in self._all_convs():
                 w = self._w(c)
@@ -538,7 +517,7 @@ class DeepLabHipExecutor(object):
                 box['dwall'] = dwall
         # gradient wrt the block OUTPUT: bn3 applies its mask. `pend`: the backward statistics of that unit 3, left by the launch
         # that writes the gradient (`_bstats`)
-        pend = self._bstats(saved[len(self.blocks) - 1][5], 3)
+        pend = self._bstats(saved[len(self.blocks) - 1][5])
         dOut = ops.conv_igemm(d, self.aspp_wallT, [(0, 0)], mode=1, stats=pend)
         keep = []
         closes = set(self.bucket_starts())
@@ -550,39 +529,23 @@ class DeepLabHipExecutor(object):
             # never written: the identity shortcut adds (bit ? dOut : 0) in conv1's data-gradient epilogue, the downsample unit's
             # backward passes read dOut through the same bits
             # (the gated shortcut `mask_gates_res` exists in the bf16 data-gradient kernels only: an fp32 identity block keeps `dres`)
-            bits3 = s3[1] if (s3[1] is not None and s3[1].dtype == torch.uint8 and _bn_gate_shortcut()
-                              and (b.cd is not None or (b.c1.stride == 1 and self.dtype == torch.bfloat16))) else None
+            bits3 = s3[1] if (b.cd is not None or (b.c1.stride == 1 and self.dtype == torch.bfloat16)) else None
             du3, dres = self._bwd_unit_bn(dOut, s3, b.c3, bits3 is None, tile_stats=pend)
-            st2 = self._bstats(s2, 2)
-            da2 = self._dgrad_raw(du3, b.c3, bstats=st2)
-            du2, _ = self._bwd_unit_bn(da2, s2, b.c2, False, tile_stats=st2)
-            st1 = self._bstats(s1, 1)
-            da1 = self._dgrad_raw(du2, b.c2, bstats=st1)
-            du1, _ = self._bwd_unit_bn(da1, s1, b.c1, False, tile_stats=st1)
+            da2 = self._dgrad_raw(du3, b.c3)
+            du2, _ = self._bwd_unit_bn(da2, s2, b.c2, False)
+            da1 = self._dgrad_raw(du2, b.c2)
+            du1, _ = self._bwd_unit_bn(da1, s1, b.c1, False)
             dud = None
             if b.cd is not None:
                 dud, _ = self._bwd_unit_bn(dres if bits3 is None else dOut, sd, b.cd, False, dy_bits=bits3)
             if want_w:
-                jobs = [(du3, a2, b.c3), (du2, a1, b.c2)] + ([(dud, xin, b.cd)] if b.cd is not None else []) + [(du1, xin, b.c1)]
-                if sides:
-                    for sd_ in sides:
-                        ops.stream_wait(sd_, main)
-                    keep.append((du3, du2, du1, dud))
-                    for ji, (du_, x_, c_) in enumerate(jobs):
-                        with torch.cuda.stream(sides[ji % len(sides)]):
-                            self._wgrad_raw(du_, x_, c_)
-                    if len(sides) > 1 and bi in closes:
-                        for sd_ in sides[1:]:
-                            ops.stream_wait(sides[0], sd_)
-                    with torch.cuda.stream(sides[0]):
-                        hook(bi)
-                else:
-                    for du_, x_, c_ in jobs:
-                        self._wgrad_raw(du_, x_, c_)
+                self._issue_wgrads(self._block_jobs(b, du3, du2, dud, du1, xin, a1, a2), sides, main, keep, bi in closes,
+                                   wgrad=self._wgrad_raw)
+                with torch.cuda.stream(sides[0] if sides else main):
                     hook(bi)
             # the launch that completes the gradient wrt this block's input = the previous block's output also takes that
             # block's unit-3 backward statistics
-            pend = self._bstats(saved[bi - 1][5], 3) if (bi > 0 and b.c1.stride == 1) else None
+            pend = self._bstats(saved[bi - 1][5]) if (bi > 0 and b.c1.stride == 1) else None
             if b.cd is None and bits3 is not None:
                 dOut = self._dgrad_raw(du1, b.c1, res=dOut, in_hw=in_hw, res_bits=bits3, bstats=pend)
             else:
@@ -606,13 +569,12 @@ class DeepLabHipExecutor(object):
         """(N, 3, H, W) image batch -> NHWC (N, hp, wp, 64) input of the body: 7x7/2 convolution + frozen BatchNorm +
         ReLU + max-pool (deeplab2.py:183-186) on csrc/stem.hip, with its own backward pass (weight gradient into the
         arena; image gradient only when the input asks for one: VAT)."""
-        w = self.__dict__.get('_stem_param')
-        if w is None:                     # (a walk over all named parameters: once, not per pass)
-            w = self.__dict__['_stem_param'] = dict(self.net.named_parameters())[self.stem_wkey]
+        if self._stem_param is None:      # (a walk over all named parameters: once, not per pass)
+            self._stem_param = dict(self.net.named_parameters())[self.stem_wkey]
         # `save` of the body pass this stem feeds (run_body / run_body_pair decide the same way): its recorded program's input buffer
-        # is where the pooled map is written (CMS_STEM_DIRECT=0: a new tensor + a copy, as in rounds 2-5)
-        save = (torch.is_grad_enabled() and (self.trainable or x.requires_grad)) if (self.use_programs and _stem_direct()) else None
-        return _StemFn.apply(x.contiguous(), w, self, save)
+        # is where the pooled map is written
+        save = (torch.is_grad_enabled() and (self.trainable or x.requires_grad)) if self.use_programs else None
+        return _StemFn.apply(x.contiguous(), self._stem_param, self, save)
 
     def _stem_destination(self, shape, save):
         """Input buffer of the CACHED forward program for a body input of `shape` (N, h, w, 64), or None (not recorded yet, or a
@@ -658,7 +620,7 @@ class DeepLabHipExecutor(object):
         key = (kind, tuple(int(v) for v in shape), False, self._tile_key()) + ((self._bn_key(),) if kind == 'fwd' else ())
         if key in self._programs:
             return False
-        seen = self.__dict__.setdefault('_seen_shapes', {})
+        seen = self._seen_shapes
         n = seen.get(key, 0) + 1
         if len(seen) > 256:
             seen.clear()
@@ -674,22 +636,13 @@ class DeepLabHipExecutor(object):
             self._prepare_forward()
             prog = ops.Program()
             x_in = torch.empty(tuple(shape), dtype=self.dtype, device=self.arena.device)
-            main = torch.cuda.current_stream()
-            split = (self.fwd_split >> (0 if self.trainable else 1)) & 1
-            extra = [self._fwd_side_stream()] if (split and not key[-1] and int(shape[0]) >= 2 and int(shape[0]) % 2 == 0) else []
-            with ops.recording(prog, [main] + extra):
+            with ops.recording(prog, [torch.cuda.current_stream()]):
                 st = self.fwd_begin(x_in, save)
-                if extra:
-                    st['halves'] = [main, extra[0]]
-                    ops.stream_wait(extra[0], main)          # the input buffer (and whatever the caller enqueued before the pass)
                 for bi in range(len(self.blocks)):
                     prog.group = bi
                     self.fwd_block(st, bi)
                 prog.group = len(self.blocks)
-                if extra:
-                    ops.stream_wait(main, extra[0])          # the head runs over the whole batch on the first stream
                 logits, saved = self.fwd_end(st)
-            prog.extra_streams = extra
             prog.x_in, prog.logits, prog.saved = x_in, logits, saved
             prog.bn = bool(key[-1])
             prog.bwd = {}
@@ -745,7 +698,7 @@ class DeepLabHipExecutor(object):
         self._prepare_forward()
         if x.data_ptr() != prog.x_in.data_ptr():
             prog.x_in.copy_(x)
-        prog.run([torch.cuda.current_stream()] + list(getattr(prog, 'extra_streams', [])))
+        prog.run([torch.cuda.current_stream()])
         self._stamp(prog)
         # the logits buffer belongs to the program (the next pass of this shape overwrites it): hand out a copy
         return prog.logits.clone(), ((prog, prog.generation) if save else None)
@@ -777,22 +730,17 @@ class DeepLabHipExecutor(object):
 
     # ---- trainable BatchNorm affine on the eight-phase weight-gradient kernel (round 6)
     def _wscratch(self):
-        t = self.__dict__.get('_wscratch_buf')
-        if t is None:
-            t = self.__dict__['_wscratch_buf'] = torch.zeros_like(self.arena.grad)     # cleared again by every finishing launch
-        return t
-
-    @property
-    def _wfinish_pending(self):
-        return self.__dict__.setdefault('_wfinish_list', [])
+        if self._wscratch_buf is None:
+            self._wscratch_buf = torch.zeros_like(self.arena.grad)     # cleared again by every finishing launch
+        return self._wscratch_buf
 
     def _wfinish_takes(self, du, x, c):
         """bf16, atomics mode, and the launch WITHOUT side outputs would run on csrc/wgrad8.hip (Cout, Cin multiples of 256, enough
-        pixels). CMS_V3_WGRAD8=0 keeps the side-output kernel everywhere (A/B)."""
-        if self.dtype != torch.bfloat16 or ops.deterministic_wgrad() or os.environ.get('CMS_V3_WGRAD8', '1') == '0':
+        pixels)."""
+        if self.dtype != torch.bfloat16 or ops.deterministic_wgrad():
             return False
         key = (c.wkey, tuple(du.shape), tuple(x.shape))
-        hit = self.__dict__.setdefault('_wfinish_ok', {}).get(key)
+        hit = self._wfinish_ok.get(key)
         if hit is None:
             hit = self._wfinish_ok[key] = bool(ops.conv_wgrad(du, x, c.taps, self.arena.packed(c.wkey, self._wscratch()),
                                                               stride=c.stride, scale=None, wg_target=self._wg_target(),
@@ -814,17 +762,12 @@ class DeepLabHipExecutor(object):
         `wgrad_streams` side streams beside the data-gradient chain, whose eight-phase convolutions hold 132 CUs."""
         if not self.overlap_wgrad:
             return 0
-        t = os.environ.get('CMS_WG_TARGET')             # experiment: CUs a weight-gradient launch aims at
-        if t:
-            return int(t)
         return 56 if self.wgrad_streams >= 2 else 112
 
     def _dgrad(self, du, c, res=None, mask=None, in_hw=None):
         """gradient wrt the input of conv `c`; `in_hw` = spatial size of that input (needed for stride 2)."""
         n, ho, wo, _ = du.shape
         mb = getattr(mask, '_cms_relu_bits', None) if mask is not None else None
-        if mb is not None and not self.relu_bits:
-            mb = None
         if mb is not None:
             mask = None                      # the bits the producing launch wrote instead of the activation itself
         if c.stride == 1:
@@ -833,7 +776,7 @@ class DeepLabHipExecutor(object):
                               out_stride=c.stride, out_full_hw=in_hw, tile=self._tile(c.cin), mask_bits=mb)
 
     def _grad_sentinel(self):
-        if getattr(self, '_sentinel', None) is None:
+        if self._sentinel is None:
             self._sentinel = dict(self.net.named_parameters())[self.blocks[-1].c3.wkey]
         return self._sentinel
 
@@ -878,8 +821,7 @@ class DeepLabHipExecutor(object):
         """Bottleneck indices at which a gradient bucket of the data-parallel all-reduce closes (step.GradBuckets):
         [layer4 + head], the two halves of layer3, [layer1 - layer2]; the stem's slice follows the autograd backward."""
         l2, l3, l4 = self._layer_first[1], self._layer_first[2], self._layer_first[3]
-        # (round 5: layer2's first bottleneck closes a slice too -- the weight-gradient streams meet there, which is what an early
-        # optimizer launch over [layer2 .. head] needs, step._arm_early_optimizer with CMS_TAIL_OPT_CUT=l2)
+        # (layer2's first bottleneck closes a slice too: the weight-gradient streams meet there)
         return sorted(set([0, l2, l3, (l3 + l4 + 1) // 2, l4]))
 
     def _backward_chain(self, saved, dlg, want_w, sides, hook, box=None):
@@ -897,8 +839,8 @@ class DeepLabHipExecutor(object):
         if want_w:
             dwall = torch.empty((1, self.aspp_zc, 2048), dtype=torch.float32, device=d.device)
             # (round 5) the head's weight gradient (91 us at cfg 2) feeds nothing but the optimizer: on the first weight-gradient
-            # stream, like every other weight gradient, instead of in front of the data-gradient chain; CMS_HEAD_WGRAD_SIDE=0: A/B
-            hs = sides[0] if (sides and self.head_wgrad_side) else None
+            # stream, like every other weight gradient, instead of in front of the data-gradient chain
+            hs = sides[0] if sides else None
             if hs is not None:
                 ops.stream_wait(hs, main)
                 keep.append((d, dwall))
@@ -907,11 +849,10 @@ class DeepLabHipExecutor(object):
                 ops.conv_wgrad(d, x4, [(0, 0)], dwall)
             if box is not None:
                 box['dwall'] = dwall
-        x4b = getattr(x4, '_cms_relu_bits', None) if self.relu_bits else None
+        x4b = getattr(x4, '_cms_relu_bits', None)
         dC = ops.conv_igemm(d, self.aspp_wallT, [(0, 0)], mode=1, mask_src=None if x4b is not None else x4, mask_bits=x4b)
         capture = getattr(self, 'debug_capture', None)
         closes = set(self.bucket_starts())
-        pending, pending_blocks = [], []
         for bi in range(len(self.blocks) - 1, -1, -1):
             if capture is not None:
                 capture[bi] = dC
@@ -920,42 +861,10 @@ class DeepLabHipExecutor(object):
             in_hw = (xin.shape[1], xin.shape[2])
             dU2 = self._dgrad(dC, b.c3, mask=a2)
             dU1 = self._dgrad(dU2, b.c2, mask=a1)
-            if not want_w:
-                pass
-            elif sides and self.wgrad_group_blocks > 0 and self.dtype == torch.bfloat16:
-                # grouped: collect the launches of this bottleneck; the group goes out behind the data gradients of its LAST
-                # bottleneck (a gradient bucket closing here ends the group too)
-                keep.append((dC, dU2, dU1))
-                pending_blocks.append(bi)
-                pending += [(dC, a2, b.c3), (dU2, a1, b.c2)] + ([(dC, xin, b.cd)] if b.cd is not None else []) + [(dU1, xin, b.c1)]
-                if len(pending_blocks) >= self.wgrad_group_blocks or bi in closes or bi == 0:
-                    ops.stream_wait(sides[0], main)
-                    with torch.cuda.stream(sides[0]):
-                        grouped = [(du_, x_, c_.taps, self.arena.packed(c_.wkey, self.arena.grad), c_.stride, c_.scale)
-                                   for du_, x_, c_ in pending if c_.wdot is None]
-                        ops.conv_wgrad_group(grouped)
-                        for du_, x_, c_ in pending:
-                            if c_.wdot is not None:
-                                self._wgrad(du_, x_, c_)
-                        for pb in pending_blocks:
-                            hook(pb)
-                    pending, pending_blocks = [], []
-            elif sides:
-                for sd in sides:
-                    ops.stream_wait(sd, main)
-                keep.append((dC, dU2, dU1))
-                jobs = [(dC, a2, b.c3), (dU2, a1, b.c2)] + ([(dC, xin, b.cd)] if b.cd is not None else []) + [(dU1, xin, b.c1)]
-                for ji, (du_, x_, c_) in enumerate(jobs):
-                    with torch.cuda.stream(sides[ji % len(sides)]):
-                        self._wgrad(du_, x_, c_)
-                if len(sides) > 1 and bi in closes:
-                    for sd in sides[1:]:                      # a bucket closes here: stream 0 must have seen every stream
-                        ops.stream_wait(sides[0], sd)
-                with torch.cuda.stream(sides[0]):
+            if want_w:
+                self._issue_wgrads(self._block_jobs(b, dC, dU2, dC, dU1, xin, a1, a2), sides, main, keep, bi in closes)
+                with torch.cuda.stream(sides[0] if sides else main):
                     hook(bi)
-            else:
-                self._block_wgrads(b, dC, dU2, dU1, xin, a1, a2)
-                hook(bi)
             dres = dC if b.cd is None else self._dgrad(dC, b.cd, in_hw=in_hw)
             dC = self._dgrad(dU1, b.c1, res=dres, mask=None if bi == 0 else xin, in_hw=in_hw)
         if not self.defer_wgrad_join:
@@ -971,7 +880,7 @@ class DeepLabHipExecutor(object):
               else len(token[0]) == 7)
         chain = self._backward_chain_bn if bn else self._backward_chain
         if bn:
-            if self.__dict__.get('_wT_raw_version', -1) != self.version or self.blocks[0].c1.wT_raw is None:
+            if self._wT_raw_version != self.version or self.blocks[0].c1.wT_raw is None:
                 self._refresh_aspp_fwd()
                 self._refresh_backward_weights_bn()
                 self._wT_raw_version = self.version
@@ -983,7 +892,7 @@ class DeepLabHipExecutor(object):
         n, _, h, w = dlogits.shape
         main = torch.cuda.current_stream()
         sides = self._side_streams(self.wgrad_streams) if (self.overlap_wgrad and want_w) else []
-        hside = sides[0] if (sides and self.head_wgrad_side and not bn) else None     # where the head's gradients are formed
+        hside = sides[0] if (sides and not bn) else None     # where the head's gradients are formed
         if not self.use_programs:
             if self.defer_wgrad_join and sides:
                 self._pending_join = list(sides)
@@ -1059,7 +968,7 @@ class DeepLabHipExecutor(object):
         max-pool / stem backward that follows on the main stream; they stay alive until `join_wgrad()` has made the main
         stream wait for the side streams."""
         if keep and self.defer_wgrad_join and ops._REC is None:
-            self._pending_keep = (self.__dict__.get('_pending_keep') or []) + [keep]
+            self._pending_keep = (self._pending_keep or []) + [keep]
 
     def join_wgrad(self):
         """The current stream waits for the weight-gradient stream(s) of the last backward pass (see `defer_wgrad_join`)."""
@@ -1070,23 +979,33 @@ class DeepLabHipExecutor(object):
                 main.wait_stream(sd)
         self._pending_keep = None          # (after the waits: frees are ordered behind the side streams' reads)
 
-    def _block_wgrads(self, b, dC, dU2, dU1, xin, a1, a2):
-        self._wgrad(dC, a2, b.c3)
-        self._wgrad(dU2, a1, b.c2)
-        if b.cd is not None:
-            self._wgrad(dC, xin, b.cd)
-        self._wgrad(dU1, xin, b.c1)
+    @staticmethod
+    def _block_jobs(b, d3, d2, dd, d1, xin, a1, a2):
+        """Weight-gradient jobs (output gradient, input activation, convolution) of one bottleneck, in issue order."""
+        return [(d3, a2, b.c3), (d2, a1, b.c2)] + ([(dd, xin, b.cd)] if b.cd is not None else []) + [(d1, xin, b.c1)]
+
+    def _issue_wgrads(self, jobs, sides, main, keep, closes, first=0, wgrad=None):
+        """Issue the weight-gradient `jobs` of one bottleneck: on the side streams `sides`, which wait for `main` here (job j on stream
+        (first + j) % len(sides); `keep` holds the tensors they read until the chain ends), or on the current stream when there are
+        none. `closes`: a gradient bucket closes at this bottleneck -- stream 0 must have seen every stream. -> first + len(jobs)"""
+        wgrad = wgrad or self._wgrad
+        for sd in sides:
+            ops.stream_wait(sd, main)
+        if sides:
+            keep.append(jobs)
+        for ji, (du_, x_, c_) in enumerate(jobs, first):
+            with torch.cuda.stream(sides[ji % len(sides)] if sides else main):
+                wgrad(du_, x_, c_)
+        if closes:
+            for sd in sides[1:]:
+                ops.stream_wait(sides[0], sd)
+        return first + len(jobs)
 
     def _side_streams(self, k):
         k = max(1, min(int(k), 3))
         while len(self._sides) < k:
             self._sides.append(ops.pooled_stream(self.arena.device, 'wgrad{}'.format(len(self._sides))))
         return self._sides[:k]
-
-    def _fwd_side_stream(self):
-        if self.__dict__.get('_fwd_side') is None:
-            self._fwd_side = ops.pooled_stream(self.arena.device, 'fwd_half_{}'.format('s' if self.trainable else 't'))
-        return self._fwd_side
 
     def _side_stream(self):
         if self._side is None:
@@ -1209,7 +1128,7 @@ class DeepLabV3PlusBackboneExecutor(DeepLabHipExecutor):
                                out_full_hw=(H, W), out_pixel_offset=py * W + px)
         return dx
 
-    def _taps_chain(self, saved, dC, d_low, track_bn, side, rec):
+    def _taps_chain(self, saved, dC, d_low, track_bn, sides, rec):
         """The launches of the backward pass (recordable). `dC`: gradient wrt the layer4 output, already masked with its
         ReLU. `d_low`: gradient wrt the layer1 tap or None; while recording it is added between two program segments
         (`rec.dres` is the buffer it goes into, the segment boundary is marked 'dlow')."""
@@ -1233,27 +1152,10 @@ class DeepLabV3PlusBackboneExecutor(DeepLabHipExecutor):
                 dU1 = self._dgrad_strided(dU2, b.c2, a1, (a1.shape[1], a1.shape[2]))
             if capture is not None:
                 capture[bi] = (dC, dU2, dU1)
-            if isinstance(side, (list, tuple)) and len(side) > 1 and os.environ.get('CMS_V3_WGRAD_PER_JOB', '1') != '0':
-                # (round 6) two weight-gradient streams, the JOBS alternating over them with a counter that runs across the
-                # blocks: per-block alternation left one stream 2.4 ms behind the other at the end of the pass (layer 1's three
-                # blocks at 129 x 129: two of them on one stream) with the main stream idle behind both (profiles/r06al_*)
-                for sd in side:
-                    ops.stream_wait(sd, main)
-                keep.append((dC, dU2, dU1))
-                jobs = [(dC, a2, b.c3), (dU2, a1, b.c2)] + ([(dC, xin, b.cd)] if b.cd is not None else []) + [(dU1, xin, b.c1)]
-                for du_, x_, c_ in jobs:
-                    with torch.cuda.stream(side[wjob % len(side)]):
-                        self._wgrad(du_, x_, c_)
-                    wjob += 1
-            elif side is not None:
-                # `side`: one stream, or a list the blocks alternate over (CMS_V3_WGRAD_PER_JOB=0)
-                sd = side[bi % len(side)] if isinstance(side, (list, tuple)) else side
-                ops.stream_wait(sd, main)
-                keep.append((dC, dU2, dU1))
-                with torch.cuda.stream(sd):
-                    self._block_wgrads(b, dC, dU2, dU1, xin, a1, a2)
-            else:
-                self._block_wgrads(b, dC, dU2, dU1, xin, a1, a2)
+            # (round 6) the JOBS alternate over the weight-gradient streams with a counter that runs across the blocks:
+            # per-block alternation left one stream 2.4 ms behind the other at the end of the pass (layer 1's three blocks at
+            # 129 x 129: two of them on one stream) with the main stream idle behind both (profiles/r06al_*)
+            wjob = self._issue_wgrads(self._block_jobs(b, dC, dU2, dC, dU1, xin, a1, a2), sides, main, keep, False, first=wjob)
             dres = dC if b.cd is None else self._dgrad(dC, b.cd, in_hw=in_hw)
             if bi == self.tap_low + 1 and d_low is not None:
                 # second gradient into the layer1 output (masked with it just below). layer2.0 has a downsample
@@ -1266,17 +1168,12 @@ class DeepLabV3PlusBackboneExecutor(DeepLabHipExecutor):
                 else:
                     dres.add_(d_low)
             dC = self._dgrad(dU1, b.c1, res=dres, mask=None if bi == 0 else xin, in_hw=in_hw)
-        if side is not None:
-            sds = list(side) if isinstance(side, (list, tuple)) else [side]
-            for sd in sds[1:]:
-                ops.stream_wait(sds[0], sd)
-            with torch.cuda.stream(sds[0]):
-                self._wfinish_flush()
-            for sd in sds:
-                ops.stream_wait(main, sd)
-        else:
+        for sd in sides[1:]:
+            ops.stream_wait(sides[0], sd)
+        with torch.cuda.stream(sides[0] if sides else main):
             self._wfinish_flush()
-        del keep
+        for sd in sides:
+            ops.stream_wait(main, sd)
         return dC
 
     def backward_taps(self, saved, d_low, d_out):
@@ -1287,22 +1184,20 @@ class DeepLabV3PlusBackboneExecutor(DeepLabHipExecutor):
             self._wT_version = self.version
         track_bn = self.bn_trainable
         main = torch.cuda.current_stream()
-        side = self._side_stream() if self.overlap_wgrad else None
-        # (round 6) TWO weight-gradient streams, the blocks alternating over them: with the wide layers on the eight-phase kernel
-        # (`_wfinish_takes`: ~56 workgroups per launch) one stream leaves half the machine idle beside the data-gradient chain --
-        # 148 img/s on one stream, 174 on two, 157.5 with the side-output kernel on one (cfg 4, profiles/r06aj_*). With the side-output
-        # kernel everywhere (CMS_V3_WGRAD8=0) two streams lose (152.8 vs 154.7, profiles/r06o_*): one stream then. CMS_V3_WGRAD_STREAMS overrides.
-        two = self.dtype == torch.bfloat16 and not ops.deterministic_wgrad() and os.environ.get('CMS_V3_WGRAD8', '1') != '0'
-        nws = os.environ.get('CMS_V3_WGRAD_STREAMS', '2' if two else '1')
-        if side is not None and nws in ('2', '3'):
-            side = [side] + [ops.pooled_stream(self.arena.device, 'wgrad{}'.format(i)) for i in range(1, int(nws))]
+        sides = [self._side_stream()] if self.overlap_wgrad else []
+        # (round 6) TWO weight-gradient streams where the wide layers run on the eight-phase kernel (`_wfinish_takes`: ~56 workgroups
+        # per launch): one stream leaves half the machine idle beside the data-gradient chain -- 148 img/s on one stream, 174 on two,
+        # 157.5 with the side-output kernel on one (cfg 4, profiles/r06aj_*). With the side-output kernel everywhere (fp32,
+        # deterministic weight gradients) two streams lose (152.8 vs 154.7, profiles/r06o_*): one stream then.
+        if sides and self.dtype == torch.bfloat16 and not ops.deterministic_wgrad():
+            sides.append(ops.pooled_stream(self.arena.device, 'wgrad1'))
         recorded = isinstance(saved, tuple) and len(saved) == 2 and isinstance(saved[0], ops.Program)
         if not recorded:
             x4 = saved[-1]
             if d_out is None:
                 d_out = torch.zeros_like(x4)
             dC = (d_out * (x4 > 0)).contiguous()
-            dx = self._taps_chain(saved, dC, d_low, track_bn, side, None)
+            dx = self._taps_chain(saved, dC, d_low, track_bn, sides, None)
         else:
             fprog, gen = saved
             if fprog.generation != gen:
@@ -1310,16 +1205,16 @@ class DeepLabV3PlusBackboneExecutor(DeepLabHipExecutor):
                                    'same shape through the same executor (programs keep ONE set of buffers per shape): '
                                    'run backward before the next forward, or set executor.use_programs = False')
             x4 = fprog.saved[-1]
-            key = (d_low is not None, track_bn, side is not None, isinstance(side, list))
+            key = (d_low is not None, track_bn, len(sides))
             prog = fprog.bwd.get(key)
-            streams = [main] + (list(side) if isinstance(side, list) else ([side] if side is not None else []))
+            streams = [main] + sides
             if prog is None:
                 prog = ops.Program()
                 prog.dC_in = torch.empty_like(x4)
                 prog.dlow_in = torch.empty_like(fprog.low) if d_low is not None else None
                 prog.dres = None
                 with ops.recording(prog, streams):
-                    prog.dx = self._taps_chain(fprog.saved, prog.dC_in, prog.dlow_in, track_bn, side, prog)
+                    prog.dx = self._taps_chain(fprog.saved, prog.dC_in, prog.dlow_in, track_bn, sides, prog)
                 fprog.bwd[key] = prog
             if d_out is None:
                 prog.dC_in.zero_()
@@ -1605,28 +1500,6 @@ def hip_conv2d(x, conv, arena, key, dtype=torch.bfloat16):
     return _HipConvGeneralFn.apply(x, conv.weight, arena, key, geom, dtype)
 
 
-def _fused_bn_stats():
-    """CMS_BN_FUSED_STATS (default 1; A/B switch, read per recording): batch-statistics units take their statistics from the tile
-    sums the convolution's epilogue writes (`_fwd_unit_bn`); 0 = the round-3/4 pass over the convolution output."""
-    return os.environ.get('CMS_BN_FUSED_STATS', '1') != '0'
-
-
-def _stem_direct():
-    """CMS_STEM_DIRECT (default 1; A/B switch): the stem's max-pool writes into the recorded body pass's input buffer."""
-    return os.environ.get('CMS_STEM_DIRECT', '1') != '0'
-
-
-def _bn_mask_bits():
-    """CMS_BN_MASK_BITS (default 1; A/B switch, read per recording): the normalising launch of a batch-statistics unit writes its
-    ReLU mask as bits and the unit's backward passes read those instead of y."""
-    return os.environ.get('CMS_BN_MASK_BITS', '1') != '0'
-
-
-def _bn_gate_shortcut():
-    """CMS_BN_GATE_SHORTCUT (default 1; A/B switch): batch-statistics backward without the `dres` tensor (`_backward_chain_bn`)."""
-    return os.environ.get('CMS_BN_GATE_SHORTCUT', '1') != '0'
-
-
 def hip_conv2d_eligible(x, conv, dtype=torch.bfloat16):
     """True when the hand-written general path (`hip_conv2d`) can express this convolution: any ungrouped square-kernel convolution
     with symmetric stride / padding / dilation (strided layers as phases, 7 x 7 stems as tap chunks, narrow / odd channel counts
@@ -1723,10 +1596,10 @@ class _BodyPairFn(torch.autograd.Function):
                 # SyncBN all-reduces between the launches: the native interleave cannot stop for them -- one pass after the
                 # other (each on its stream; they still overlap where the host runs ahead)
                 with torch.cuda.stream(side):
-                    pt.run([side] + list(getattr(pt, 'extra_streams', [])))
-                ps.run([main] + list(getattr(ps, 'extra_streams', [])))
+                    pt.run([side])
+                ps.run([main])
             else:
-                ops.run_pair(ps, [main] + list(getattr(ps, 'extra_streams', [])), pt, [side] + list(getattr(pt, 'extra_streams', [])))
+                ops.run_pair(ps, [main], pt, [side])
             ex_stu._stamp(ps)
             ex_tea._stamp(pt)
             logits_s = ps.logits.clone()

@@ -1246,37 +1246,18 @@ extern "C" int cms_conv_set_trace(void* buf, int workgroups) {
     return 0;
 }
 
-// A/B switch for whole-step measurements (bench.py under CMS_CONV_DEFAULT_VARIANT=43 etc.): the variant used by
-// descriptors that ask for 0 = auto. Diagnostic only; read once.
-static int conv_default_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CMS_CONV_DEFAULT_VARIANT");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
-// The eight-phase 256 x 256 kernel (csrc/conv8.hip) takes the wide, K-deep layers. CMS_CONV8 (read once): 0 = never,
+// The eight-phase 256 x 256 kernel (csrc/conv8.hip) takes the wide, K-deep layers: 16 or more 64-deep K tiles per output tile
+// (the expansions on it, 4 or 8 K tiles: measured, not adopted -- profiles/r06b_*). CMS_CONV8 (read once): 0 = never,
 // 1 = one whole tile per workgroup (default: +3.5 / +5 % on the two-stream step at 321 x 321 / 512 x 1024, profiles/r04d_*),
 // 2 = persistent launch with a stream-K round where the descriptor carries a workspace (slower: the 256 KB partial tiles
-// move at the ~10 B/clk a CU gets from memory), CMS_CONV8_MIN_KT = fewest 64-deep K tiles per output tile it is used for
-// (default 16), CMS_CONV8_GRID = workgroup cap of mode 2, CMS_CONV8_PASSES = bit 0 forward / bit 1 data-gradient launches.
-static int conv8_env(int which) {
-    static int mode = -1, min_kt = 0, grid = 0, passes = 3, min_tiles = 0;
+// move at the ~10 B/clk a CU gets from memory).
+static int conv8_env() {
+    static int mode = -1;
     if (mode < 0) {
-        const char* mt = getenv("CMS_CONV8_MIN_TILES");        // fewest 256 x 256 output tiles of a launch it is used for (round 6)
-        min_tiles = mt ? atoi(mt) : 0;
         const char* e = getenv("CMS_CONV8");
-        const char* k = getenv("CMS_CONV8_MIN_KT");
-        const char* g = getenv("CMS_CONV8_GRID");
-        const char* p = getenv("CMS_CONV8_PASSES");            // bit 0: forward epilogue launches, bit 1: data gradients
-        min_kt = k ? atoi(k) : 16;
-        grid = g ? atoi(g) : 0;
-        passes = p ? atoi(p) : 3;
         mode = e ? atoi(e) : 1;
     }
-    return which == 0 ? mode : (which == 1 ? min_kt : (which == 2 ? grid : (which == 3 ? passes : min_tiles)));
+    return mode;
 }
 
 extern "C" long long cms_conv_igemm_workspace_bytes(void) {
@@ -1287,20 +1268,9 @@ extern "C" long long cms_conv_igemm_workspace_bytes(void) {
 
 // Would the default dispatch (variant 0, tile 0) send this launch to the eight-phase kernel?
 static bool conv_takes_conv8(const cms_conv_desc* d) {
-    return d->variant == 0 && d->tile == 0 && conv8_env(0) > 0 && cms::conv8_supported(d) &&
-           ((d->mask_bits == nullptr && d->mask_bits_out == nullptr) || conv8_env(0) == 1) &&     // (bits: whole tiles only)
-           d->ntaps * (d->cin / 64) >= conv8_env(1) && conv_default_variant() == 0 &&
-           ((conv8_env(3) >> (d->mode == 0 ? 0 : 1)) & 1) &&
-           (conv8_env(4) <= 0 || (long long)((d->n * d->ho * d->wo + 255) / 256) * (d->cout / 256) >= conv8_env(4));
-}
-
-static int conv_mixed_env() {                       // balanced launch; CMS_CONV_MIXED=0 switches it off (A/B, read once)
-    static int env_mixed = -1;
-    if (env_mixed < 0) {
-        const char* e = getenv("CMS_CONV_MIXED");
-        env_mixed = e ? atoi(e) : 1;
-    }
-    return env_mixed;
+    return d->variant == 0 && d->tile == 0 && conv8_env() > 0 && cms::conv8_supported(d) &&
+           ((d->mask_bits == nullptr && d->mask_bits_out == nullptr) || conv8_env() == 1) &&     // (bits: whole tiles only)
+           d->ntaps * (d->cin / 64) >= 16;
 }
 
 // Which kernel cms_conv_igemm runs a descriptor on (measurement tooling: per-kernel algorithmic bytes beside the PMC
@@ -1310,7 +1280,7 @@ static int conv_mixed_env() {                       // balanced launch; CMS_CONV
 extern "C" int cms_conv_igemm_route(const cms_conv_desc* d) {
     int rc = conv_check(d);
     if (rc) return rc;
-    if (d->variant != 0 || d->tile != 0 || conv_default_variant() != 0) return CMS_ROUTE_OTHER;
+    if (d->variant != 0 || d->tile != 0) return CMS_ROUTE_OTHER;
     if (conv_takes_conv8(d)) return CMS_ROUTE_CONV8;
     if (d->cout % 128 == 0) {
         const bool small = (size_t)d->n * d->h * d->w_in * d->cin * 2 < (1ull << 31) &&
@@ -1318,7 +1288,7 @@ extern "C" int cms_conv_igemm_route(const cms_conv_desc* d) {
         const int M = d->n * d->ho * d->wo;
         const int ntn = d->cout / 128, mtiles = (M + 127) / 128, total = mtiles * ntn;
         const int rounds = total / 256, rem = total % 256;
-        if (conv_mixed_env() != 0 && d->zeros != nullptr && small && d->ksplit <= 1 && 256 % ntn == 0 && rounds >= 1 && rounds <= 9 &&
+        if (d->zeros != nullptr && small && d->ksplit <= 1 && 256 % ntn == 0 && rounds >= 1 && rounds <= 9 &&
             rem > 0 && rem <= 100)
             return CMS_ROUTE_MIXED;
         return CMS_ROUTE_TILE128;
@@ -1336,7 +1306,7 @@ extern "C" int cms_conv_igemm_stats_tile_rows(const cms_conv_desc* d) {
     if (d->mode == 0 ? d->bstats_u != nullptr : (d->bstats_u == nullptr || d->bstats_mean == nullptr || d->bstats_rstd == nullptr)) return 0;
     const int route = cms_conv_igemm_route(d);
     if (route < 0) return route;
-    if (route == CMS_ROUTE_CONV8 && conv8_env(0) != 1) return 0;        // (whole tiles per workgroup only, not the stream-K launch)
+    if (route == CMS_ROUTE_CONV8 && conv8_env() != 1) return 0;        // (whole tiles per workgroup only, not the stream-K launch)
     const int rows = route == CMS_ROUTE_CONV8 ? 256 : (route == CMS_ROUTE_OTHER ? 0 : 128);
     if (rows == 0) return 0;
     const long long M = (long long)d->n * d->ho * d->wo;
@@ -1349,7 +1319,7 @@ extern "C" int cms_conv_igemm(const cms_conv_desc* d_in, void* stream) {
     int rc = conv_check(d_in);
     if (rc) return rc;
     if (d_in->variant >= 90 && d_in->variant <= 93)     // 92 / 93: 90 / 91 with cycle stamps into the cms_conv_set_trace buffer
-        return cms::conv8_launch(d_in, (hipStream_t)stream, (d_in->variant - 90) & 1, conv8_env(2),
+        return cms::conv8_launch(d_in, (hipStream_t)stream, (d_in->variant - 90) & 1, 0,
                                  d_in->variant >= 92 ? g_conv_trace : nullptr, g_conv_trace_wgs);
     cms_conv_desc d_no8;
     if (d_in->variant == 99) {                 // the 128 x 128 family, whatever CMS_CONV8 says (reference of the conv8 tests)
@@ -1357,23 +1327,8 @@ extern "C" int cms_conv_igemm(const cms_conv_desc* d_in, void* stream) {
         d_no8.variant = 0;
         d_in = &d_no8;
     } else if (conv_takes_conv8(d_in))
-        return cms::conv8_launch(d_in, (hipStream_t)stream, conv8_env(0) - 1, conv8_env(2), nullptr, 0);
-    cms_conv_desc d_copy;
+        return cms::conv8_launch(d_in, (hipStream_t)stream, conv8_env() - 1, 0, nullptr, 0);
     const cms_conv_desc* d = d_in;
-    if (d_in->variant == 0 && conv_default_variant() != 0) {
-        const int v = conv_default_variant();
-        // ring variants exist for the 128-channel tile of the bf16 output only
-        const bool ring = (v >= 10 && v <= 14) || (v >= 50 && v <= 54) || (v >= 60 && v <= 85);
-        const int need = (v >= 70 && v <= 85) ? 256 : 128;
-        const bool small_ok = (size_t)d_in->n * d_in->h * d_in->w_in * d_in->cin * 2 < (1ull << 31) &&
-                              (size_t)d_in->ntaps * d_in->cout * d_in->cin * 2 < (1ull << 31);
-        if (!ring || (d_in->cout % need == 0 && (d_in->tile == 0 || d_in->tile == 128) && d_in->zeros != nullptr && small_ok &&
-                      d_in->y != nullptr && (d_in->ksplit <= 1))) {
-            d_copy = *d_in;
-            d_copy.variant = v;
-            d = &d_copy;
-        }
-    }
     ConvArgs a;
     a.x = (const uint16_t*)d->x; a.w = (const uint16_t*)d->w; a.y = (uint16_t*)d->y; a.y32 = d->y32;
     a.scale = d->scale; a.bias = d->bias; a.res = (const uint16_t*)d->res; a.mask_src = (const uint16_t*)d->mask_src;
@@ -1415,19 +1370,14 @@ extern "C" int cms_conv_igemm(const cms_conv_desc* d_in, void* stream) {
     a.krot = d->variant == 20 ? 1 : (d->variant == 21 ? 3 : (d->variant == 22 ? 5 : (d->variant == 23 ? 11 : (d->variant == 25 ? 3 : 0))));
     a.stagger = (d->variant == 24 || d->variant == 25) ? 1 : 0;
     a.n_main = 0; a.rem_tile_base = 0;
-    // pointwise fast path of the prologue (conv_body: `plain`); CMS_CONV_PLAIN=0 switches it off (A/B, read once)
-    static int env_plain = -1;
-    if (env_plain < 0) {
-        const char* e = getenv("CMS_CONV_PLAIN");
-        env_plain = e ? atoi(e) : 1;
-    }
     static int env_nt = -1;
     if (env_nt < 0) {
         const char* e = getenv("CMS_CONV_NT");          // A/B switch, read once
         env_nt = e ? atoi(e) : 0;
     }
     a.nt_store = env_nt;
-    a.plain = (env_plain != 0 && d->ntaps == 1 && d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->stride == 1 && d->h == d->ho &&
+    // pointwise fast path of the prologue (conv_body: `plain`)
+    a.plain = (d->ntaps == 1 && d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->stride == 1 && d->h == d->ho &&
                d->w_in == d->wo && d->out_stride == 1 && d->out_h == d->ho && d->out_w == d->wo && a.ksplit == 1 && a.krot == 0 &&
                (size_t)a.M * d->cin * 2 < (1ull << 31)) ? 1 : 0;
     // 30: the default kernel with per-workgroup cycle stamps into the buffer given to cms_conv_set_trace
@@ -1539,11 +1489,10 @@ extern "C" int cms_conv_igemm(const cms_conv_desc* d_in, void* stream) {
         // the DeepLab v2 layer shapes and no better end to end, tools/conv_ablate.py)
         CMS_REQUIRE(d->cout % 128 == 0, "conv: tile 128 needs Cout %% 128 == 0");
         // balanced launch (conv_igemm_mixed_kernel): when the 128 x 128 grid is a few workgroups more than a multiple of
-        // the 256 CUs, those few are cut into 32-channel slices. CMS_CONV_MIXED=0 switches it off (A/B).
-        const int env_mixed = conv_mixed_env();
+        // the 256 CUs, those few are cut into 32-channel slices.
         const int ntn = d->cout / 128, mtiles = (a.M + 127) / 128, total = mtiles * ntn;
         const int rounds = total / 256, rem = total % 256;
-        if (env_mixed != 0 && tile == 0 && d->variant == 0 && (glds == 4 || glds == 1) && a.ksplit == 1 && 256 % ntn == 0 &&
+        if (tile == 0 && d->variant == 0 && (glds == 4 || glds == 1) && a.ksplit == 1 && 256 % ntn == 0 &&
             rounds >= 1 && rounds <= 9 && rem > 0 && rem <= 100) {
             a.n_main = rounds * 256;
             a.rem_tile_base = a.n_main / ntn;

@@ -97,9 +97,9 @@ struct cms_program {
     long acc_launches = 0;
     long last_head = -1;       // index into `timed` of the head GEMM bracket the next gather op extends
     int last_head_stream = -1;
-    hipEvent_t prev_sync_ev = nullptr;   // the event the PREVIOUS issued op recorded, if that op was a sync from `prev_sync_from`:
-    void* prev_sync_from = nullptr;      // consecutive syncs from one stream (both weight-gradient streams waiting for the main
-                                         // stream, once per bottleneck) share ONE event record (round 5)
+    void* prev_sync_from = nullptr;      // the stream the PREVIOUS issued op, a flag sync, was waiting for: consecutive syncs from one
+                                         // stream (both weight-gradient streams waiting for the main stream, once per bottleneck)
+                                         // share ONE setter. (One shared EVENT record: measured, not adopted -- profiles/r05p_*)
     int n_syncs = 0;
     int* flags = nullptr;                // caller-owned, zero-initialised device words: one per sync op + the timeout counter
     int n_flags = 0;
@@ -115,17 +115,6 @@ static int issue(cms_program* p, Op& o, void* const* streams, int n_streams) {
     CMS_REQUIRE(o.stream >= 0 && o.stream < n_streams, "program: op on stream %d but only %d streams given", o.stream,
                 n_streams);
     hipStream_t s = (hipStream_t)streams[o.stream];
-    hipEvent_t shared_ev = nullptr;
-    static int share_events = -1;
-    if (share_events < 0) {
-        // A/B switch, read once. OFF by default: measured SLOWER (629.3 / 630.8 against 634.9 / 635.9 img/s at cfg 2,
-        // profiles/r05p_*) -- with one record both weight-gradient streams are released at the same instant
-        const char* e = getenv("CMS_PROG_SHARE_EVENTS");
-        share_events = e ? atoi(e) : 0;
-    }
-    if (share_events && o.kind == OP_SYNC && p->prev_sync_ev != nullptr && o.from >= 0 && o.from < n_streams &&
-        p->prev_sync_from == streams[o.from])
-        shared_ev = p->prev_sync_ev;         // nothing was issued since that record: the same point of the `from` stream
     static int share_flags = -1;
     if (share_flags < 0) {
         const char* e = getenv("CMS_PROG_FLAG_SHARE");      // A/B switch, read once: 0 = every waiter gets its own setter
@@ -133,7 +122,6 @@ static int issue(cms_program* p, Op& o, void* const* streams, int n_streams) {
     }
     const int shared_slot = (share_flags && o.kind == OP_SYNC && p->prev_flag_slot >= 0 && o.from >= 0 && o.from < n_streams &&
                              p->prev_sync_from == streams[o.from]) ? p->prev_flag_slot : -1;
-    p->prev_sync_ev = nullptr;
     p->prev_flag_slot = -1;
     switch (o.kind) {
     case OP_CONV: {
@@ -238,22 +226,11 @@ static int issue(cms_program* p, Op& o, void* const* streams, int n_streams) {
             p->prev_sync_from = streams[o.from];
             return launch_status("program: flag sync");
         }
-        if (shared_ev != nullptr) {
-            if (hipStreamWaitEvent(s, shared_ev, 0) != hipSuccess) {
-                set_error("program: event wait failed");
-                return CMS_ELAUNCH;
-            }
-            p->prev_sync_ev = shared_ev;
-            p->prev_sync_from = streams[o.from];
-            return CMS_OK;
-        }
         if (hipEventRecord(o.ev, (hipStream_t)streams[o.from]) != hipSuccess ||
             hipStreamWaitEvent(s, o.ev, 0) != hipSuccess) {
             set_error("program: event record / wait failed");
             return CMS_ELAUNCH;
         }
-        p->prev_sync_ev = o.ev;
-        p->prev_sync_from = streams[o.from];
         return CMS_OK;
     }
     }
@@ -419,8 +396,7 @@ static void begin_replay(cms_program* p, void* const* streams) {
         const char* e = getenv("CMS_PROG_FLAG_SYNC");
         flag_sync = e ? atoi(e) : 1;        // (the Python side only hands flags over with CMS_PROG_FLAG_SYNC=1: measured slower)
     }
-    p->prev_sync_ev = nullptr;               // (the host may have enqueued anything since the last call)
-    p->prev_flag_slot = -1;
+    p->prev_flag_slot = -1;                  // (the host may have enqueued anything since the last call)
     p->use_flags = false;
     if (flag_sync != 0 && p->flags != nullptr && p->n_syncs > 0) {
         hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -452,24 +428,7 @@ extern "C" int cms_program_run_pair(cms_program* a, void* const* streams_a, int 
     CMS_REQUIRE(a && b && streams_a && streams_b && na > 0 && nb > 0, "program_run_pair: NULL program / streams");
     size_t ia = 0, ib = 0;
     const size_t ea = a->ops.size(), eb = b->ops.size();
-    // EXPERIMENT (round 6, CMS_PAIR_SYNC=k, read once; 0 = off, the default): every k-th group boundary the FIRST streams of the
-    // two programs wait for each other -- the two passes then walk their bottlenecks in phase (conv1 || conv1, conv2 || conv2,
-    // expansion || expansion: launches of one kind share the machine better than a whole-CU eight-phase launch beside a
-    // four-per-CU expansion). Events come from a small static pool (the pair is issued from one host thread).
-    static int pair_sync = -1;
-    static hipEvent_t sync_ev[64][2];
-    static bool sync_ev_made = false;
-    if (pair_sync < 0) {
-        const char* e = getenv("CMS_PAIR_SYNC");
-        pair_sync = e ? atoi(e) : 0;
-    }
-    if (pair_sync > 0 && !sync_ev_made) {
-        for (auto& pr : sync_ev)
-            for (auto& ev : pr)
-                if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { set_error("program_run_pair: event"); return CMS_ELAUNCH; }
-        sync_ev_made = true;
-    }
-    int groups_done = 0, ev_slot = 0;
+    // (the two passes forced into phase at group boundaries: measured, not adopted -- DESIGN 4.1 round 6)
     begin_replay(a, streams_a);
     begin_replay(b, streams_b);
     while (ia < ea || ib < eb) {
@@ -477,27 +436,15 @@ extern "C" int cms_program_run_pair(cms_program* a, void* const* streams_a, int 
         const int ga = ia < ea ? a->ops[ia].group : 0x7fffffff;
         const int gb = ib < eb ? b->ops[ib].group : 0x7fffffff;
         const int g = ga < gb ? ga : gb;
-        a->prev_sync_ev = nullptr;           // (the other program's ops were issued in between, possibly on shared streams)
-        a->prev_flag_slot = -1;
+        a->prev_flag_slot = -1;              // (the other program's ops were issued in between, possibly on shared streams)
         while (ia < ea && a->ops[ia].group <= g) {
             const int rc = issue(a, a->ops[ia++], streams_a, na);
             if (rc != CMS_OK) return rc;
         }
-        b->prev_sync_ev = nullptr;
         b->prev_flag_slot = -1;
         while (ib < eb && b->ops[ib].group <= g) {
             const int rc = issue(b, b->ops[ib++], streams_b, nb);
             if (rc != CMS_OK) return rc;
-        }
-        if (pair_sync > 0 && (++groups_done % pair_sync) == 0 && ia < ea && ib < eb) {
-            hipStream_t sa = (hipStream_t)streams_a[0], sb = (hipStream_t)streams_b[0];
-            hipEvent_t* ev = sync_ev[ev_slot];
-            ev_slot = (ev_slot + 1) % 64;
-            if (hipEventRecord(ev[0], sa) != hipSuccess || hipEventRecord(ev[1], sb) != hipSuccess ||
-                hipStreamWaitEvent(sa, ev[1], 0) != hipSuccess || hipStreamWaitEvent(sb, ev[0], 0) != hipSuccess) {
-                set_error("program_run_pair: cross-stream sync failed");
-                return CMS_ELAUNCH;
-            }
         }
     }
     return CMS_OK;

@@ -45,11 +45,11 @@ class GraphReplay(dict):
         super(GraphReplay, self).__init__()
         self.what, self.env = what, env
 
-    def run(self, tensors, extra, fn, nets, device, generator=None, side_streams=False, warmup=2):
+    def run(self, tensors, extra, fn, nets, device, generator=None, warmup=2):
         """`fn(tensors, capturing=False)` launch by launch for the first `warmup` calls of a signature (and for ever after a failed
         capture), then `fn(static tensors, capturing=True)` captured once and replayed. `fn` -> (ce scalars, [consistency scalars]).
         `nets`: the networks whose weight arenas (`_cms_arena`) the passes read; `generator`: a CUDA generator the passes draw from
-        (registered with the graph); `side_streams`: whether the layer engines' side streams fork / join inside the capture."""
+        (registered with the graph). The layer engines' side streams do not fork / join inside the capture."""
         key = signature(tensors, extra)
         alias = key[1]
         ent = self.setdefault(key, {'seen': 0})
@@ -68,7 +68,7 @@ class GraphReplay(dict):
             g = torch.cuda.CUDAGraph()
             if generator is not None and hasattr(g, 'register_generator_state'):
                 g.register_generator_state(generator)
-            prev = ops.set_side_streams_enabled(side_streams)
+            prev = ops.set_side_streams_enabled(False)
             try:
                 with torch.cuda.graph(g):
                     out = fn(static, capturing=True)

@@ -417,7 +417,7 @@ def upsample_bilinear(x, size, align_corners=True):
 _STREAM_POOL = {}
 
 
-_ROLE_ALIASES = {'1': {'wgrad0': 'teacher', 'optimizer': 'wgrad1'}, 'opt': {'optimizer': 'wgrad1'}, 'tea': {'wgrad0': 'teacher'}, '0': {}}
+_ROLE_ALIASES = {'optimizer': 'wgrad1'}      # roles that are never busy at the same time share one stream
 _GOOD_STREAMS = {}          # device index -> candidate side streams that run CONCURRENTLY with the default stream (probed once)
 _STREAM_PROBE_LOG = []
 
@@ -603,32 +603,22 @@ def pooled_stream(device, role):
     built on (configs[1] without --freeze_bn as the fourth workload of one process: 277 img/s against 312 alone,
     profiles/r03also_*). Objects that need a side stream take it from here instead of creating their own.
     Round 5: (i) the streams come from a PROBED set that does not share the default stream's hardware queue (`_probe_side_streams`);
-    (ii) roles that are never busy at the same time may share one stream (CMS_STREAM_ALIAS: '1' teacher = first weight-gradient stream and
-    optimizer behind the second, 'opt' / 'tea' one of the two, '0' none), so that the step needs fewer queues of its own."""
+    (ii) roles that are never busy at the same time share one stream (`_ROLE_ALIASES`: the optimizer's early launch goes behind the
+    second weight-gradient stream), so that the step needs fewer queues of its own."""
     dev = torch.device(device)
     if dev.index is None:
         dev = torch.device('cuda', torch.cuda.current_device())
-    role = _ROLE_ALIASES.get(_os.environ.get('CMS_STREAM_ALIAS', 'opt'), {}).get(str(role), str(role))
+    role = _ROLE_ALIASES.get(str(role), str(role))
     key = (dev.index, str(role))
     st = _STREAM_POOL.get(key)
     if st is None:
-        # CMS_STREAM_PRIO="wgrad=-1+teacher=-1" (experiment, read at creation): -1 = high priority for roles with that prefix
-        prio = 0
-        for item in _os.environ.get('CMS_STREAM_PRIO', '').split('+'):
-            if '=' in item and str(role).startswith(item.split('=')[0]):
-                prio = int(item.split('=')[1])
-        if prio != 0:
-            st = torch.cuda.Stream(device=dev, priority=prio)
-        else:
-            # slot of a role among the probed streams: roles that run side by side sit on different slots -- teacher | first
-            # weight-gradient stream (DeepLab v3+'s single one: 'side') | second weight-gradient stream (+ the optimizer's early launch)
-            good = _probe_side_streams(dev)
-            slot = {'teacher': 0, 'wgrad0': 1, 'side': 1, 'wgrad1': 2, 'optimizer': 2, 'wgrad2': 0, 'fwd_half_s': 1,
-                    'fwd_half_t': 2}.get(str(role))
-            if slot is None:
-                slot = sum(1 for k in _STREAM_POOL if k[0] == dev.index)
-            st = good[slot % len(good)]
-        _STREAM_POOL[key] = st
+        # slot of a role among the probed streams: roles that run side by side sit on different slots -- teacher | first
+        # weight-gradient stream (DeepLab v3+'s single one: 'side') | second weight-gradient stream (+ the optimizer's early launch)
+        good = _probe_side_streams(dev)
+        slot = {'teacher': 0, 'wgrad0': 1, 'side': 1, 'wgrad1': 2, 'wgrad2': 0}.get(role)
+        if slot is None:
+            slot = sum(1 for k in _STREAM_POOL if k[0] == dev.index)
+        st = _STREAM_POOL[key] = good[slot % len(good)]
     return st
 
 

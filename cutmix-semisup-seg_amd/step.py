@@ -59,23 +59,6 @@ class StepConfig(object):
         # measured: no gain (507 / 509 vs 507 / 505 img/s, profiles/r03eo_*) -- the 0.28 ms HBM-bound update only trades bandwidth
         # with the convolutions it overlaps -- so it is off by default
         self.early_optimizer = bool(early_optimizer)
-        # (round 5) the TAIL version of it: ONE early launch, for everything but the stem's slice, on a third stream as soon as the
-        # body's last weight gradient is enqueued -- the 0.3 ms HBM-bound update then runs beside the max-pool / stem backward
-        # (MFMA / LDS-bound, 0.2 ms) instead of alone behind them; CMS_TAIL_OPT=0 switches it off (A/B)
-        self.tail_optimizer = os.environ.get('CMS_TAIL_OPT', '1') != '0'
-        # fused-batch step on the executor: the main stream joins the weight-gradient stream at the optimizer instead of at the
-        # end of the body's backward pass (the stem's backward then overlaps layer1's last weight gradients); CMS_DEFER_JOIN=0
-        # switches it off (A/B)
-        self.defer_wgrad_join = os.environ.get('CMS_DEFER_JOIN', '1') != '0'
-        # the consistency branch of the loss on the teacher's stream, concurrently with the cross entropy on the main stream
-        self.overlap_losses = os.environ.get('CMS_OVERLAP_LOSSES', '1') != '0'
-        # the teacher's stream forks at the head of the step instead of behind the paste / concatenation of the student's inputs (A/B)
-        self.early_teacher_fork = os.environ.get('CMS_EARLY_TEACHER_FORK', '1') != '0'
-        # (round 6) each loss as ONE launch (forward + backward, the gradient's scalar factor applied afterwards: ops.consistency_fused
-        # / ops.ce_fused) in the fused-batch step; CMS_FUSED_LOSSES=0 = the forward / backward launch pairs of rounds 1-5 (A/B)
-        self.fused_losses = os.environ.get('CMS_FUSED_LOSSES', '1') != '0'
-        # (round 6) the step's gradient clear on the first weight-gradient stream instead of at the head of the main stream (A/B)
-        self.zero_grad_side = os.environ.get('CMS_ZERO_GRAD_SIDE', '1') != '0'
         self.compute_dtype = compute_dtype
         self.cons = ops.ConsistencyConfig(mode='mix' if self.mix else 'cut', loss_fn=cons_loss_fn,
                                           conf_thresh=conf_thresh, conf_per_pixel=conf_per_pixel, invert=invert)
@@ -283,24 +266,17 @@ class CutMixMeanTeacherStep(object):
         as soon as that slice's gradients are final -- [layer4 + head], the two halves of layer3, [layer1 - layer2], at the
         bottlenecks the data-parallel buckets close at -- instead of one 0.28 ms launch after the whole backward pass; the
         stem's slice follows in `student_optim.step()`. Same arithmetic per element, so the results are bit-identical."""
-        every = self.cfg.early_optimizer
-        if self.world > 1 or not (every or self.cfg.tail_optimizer) or not hasattr(self.student_optim, 'step_range'):
+        if self.world > 1 or not hasattr(self.student_optim, 'step_range'):
             return None
         ex = self._student_executor()
         if ex is None or not hasattr(ex, 'block_grad_offsets') or not ex.use_programs or not ex._want_w():
             return None
         opt = self.student_optim
         offs = ex.block_grad_offsets()
-        if every:
-            starts = set(ex.bucket_starts())
-        else:
-            # where the early launch(es) go. 'l1' (default): one launch behind the LAST weight gradient, beside the stem's backward.
-            # 'l2': behind the first bottleneck of layer2 -- 99 % of the parameters (layer2 .. head) are final there and the update
-            # runs beside layer1's backward (HBM-heavy itself); layer1's slice follows at the end. CMS_TAIL_OPT_CUT: A/B switch
-            cut = os.environ.get('CMS_TAIL_OPT_CUT', 'l1')
-            starts = {0}
-            if cut in ('l2', 'l3') and hasattr(ex, 'layer_first_blocks'):
-                starts.add(ex.layer_first_blocks()[1 if cut == 'l2' else 2])
+        # `early_optimizer`: a launch per finished slice. Otherwise the TAIL version (round 5): ONE early launch, for everything but the
+        # stem's slice, as soon as the body's last weight gradient is enqueued -- the 0.3 ms HBM-bound update then runs beside the
+        # max-pool / stem backward (MFMA / LDS-bound, 0.2 ms) instead of alone behind them (profiles/r05a_*)
+        starts = set(ex.bucket_starts()) if self.cfg.early_optimizer else {0}
         state = {'hi': int(opt.arena.flat.numel())}
         opt.begin_ranged()
         if self._opt_stream is None:
@@ -385,11 +361,9 @@ class CutMixMeanTeacherStep(object):
         8 ms later, so it goes out on the FIRST WEIGHT-GRADIENT STREAM (idle during the forward passes) instead of in front of the
         paste / concatenation / stems of the main stream (round 6). Order: the fill waits for the main stream (last
         step's optimizer has read the gradients), the main stream waits for the fill right before the backward pass -- every
-        gradient writer forks from the main stream behind that point. CMS_ZERO_GRAD_SIDE=0: on the main stream, as in rounds 1-5.
+        gradient writer forks from the main stream behind that point.
         -> the event the main stream has to wait for, or None"""
-        wg = None
-        if self.cfg.zero_grad_side and torch.cuda.is_available():
-            wg = ops.pooled_stream(torch.cuda.current_device(), 'wgrad0')
+        wg = ops.pooled_stream(torch.cuda.current_device(), 'wgrad0') if torch.cuda.is_available() else None
         if wg is None or wg is main:
             self.student_optim.zero_grad()
             return None
@@ -496,8 +470,7 @@ class CutMixMeanTeacherStep(object):
             # Pi model (teacher IS the student): one network, one executor -- its lazily refreshed operand tables
             # (BN affine, ASPP weights) must not be rewritten on one stream while the other reads them
             side = self._teacher_stream() if (cfg.overlap_teacher and self.teacher is not self.student) else main
-            early = side is not main and cfg.early_teacher_fork
-            if early:
+            if side is not main:
                 # (round 5) the teacher's inputs are the caller's tensors: its stream forks HERE -- behind last step's optimizer /
                 # EMA writes, in front of this step's gradient clear, paste and concatenation on the main stream, which it does not need
                 side.wait_stream(main)
@@ -506,15 +479,10 @@ class CutMixMeanTeacherStep(object):
                 tea_in.append(ub.x0_tea)
                 if cfg.mix:
                     tea_in.append(ub.x1_tea)
-            if early:
-                with torch.cuda.stream(side):
-                    x_tea = torch.cat(tea_in, dim=0) if len(tea_in) > 1 else tea_in[0]
+            with torch.cuda.stream(side):
+                x_tea = torch.cat(tea_in, dim=0) if len(tea_in) > 1 else tea_in[0]
             for ub in unsup_batches:
                 stu_in.append(self._student_inputs(ub))
-            if not early:
-                x_tea = torch.cat(tea_in, dim=0) if len(tea_in) > 1 else tea_in[0]
-                if side is not main:
-                    side.wait_stream(main)              # inputs (and last step's optimizer / EMA writes) are ready
         else:
             self.student_optim.zero_grad()
         x_stu = torch.cat(stu_in, dim=0) if len(stu_in) > 1 else stu_in[0]
@@ -536,16 +504,13 @@ class CutMixMeanTeacherStep(object):
         # the supervised loss needs nothing from the teacher: its kernels are issued BEFORE the join and overlap the tail
         # of the teacher's pass on the other stream
         # Two independent branches between the forward passes and the backward pass: the supervised loss (student logits
-        # only) and the consistency loss (student + teacher logits). Each is a forward + backward kernel pair that is
-        # latency-bound on a few MB -- they write disjoint slices of grad_lo and run CONCURRENTLY: the
-        # consistency branch on the teacher's stream (behind the teacher's pass, where its second operand comes from),
-        # the cross entropy on the main stream.
-        split = use_unsup and side is not main and cfg.overlap_losses
+        # only) and the consistency loss (student + teacher logits). Each is ONE launch (loss + gradient, the gradient's scalar
+        # factor applied afterwards: ops.ce_fused / ops.consistency_fused) that is latency-bound on a few MB -- they
+        # write disjoint slices of grad_lo and run CONCURRENTLY: the consistency branch on the teacher's stream (behind the
+        # teacher's pass, where its second operand comes from), the cross entropy on the main stream.
+        split = use_unsup and side is not main
         if split:
             side.wait_stream(main)                  # the student's logits (and grad_lo's zero fill)
-        else:
-            if use_unsup and side is not main:
-                main.wait_stream(side)
         cons_vals = []
 
         def consistency_branch():
@@ -555,16 +520,10 @@ class CutMixMeanTeacherStep(object):
                 l0 = tea_lo[t_off:t_off + n]
                 l1 = tea_lo[t_off + n:t_off + 2 * n] if cfg.mix else None
                 t_off += 2 * n if cfg.mix else n
-                if cfg.fused_losses:
-                    # (round 6) loss + gradient in ONE launch; grad_lo's rows are zero here (filled above, disjoint per branch)
-                    sc = ops.consistency_fused(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size, grad_lo[s_off:s_off + n],
-                                               ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
-                                               cons_weight=cfg.cons_weight, group=self.group)
-                else:
-                    sc, cctx = ops.consistency_forward(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size,
-                                                       ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
-                                                       cons_weight=cfg.cons_weight, group=self.group)
-                    ops.consistency_backward(cctx, sc, grad_lo[s_off:s_off + n])
+                # grad_lo's rows are zero here (filled above, disjoint per branch)
+                sc = ops.consistency_fused(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size, grad_lo[s_off:s_off + n],
+                                           ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
+                                           cons_weight=cfg.cons_weight, group=self.group)
                 s_off += n
                 if split and isinstance(sc, torch.Tensor):
                     sc.record_stream(main)          # allocated on the teacher's stream, read (and freed) on the main one
@@ -572,11 +531,7 @@ class CutMixMeanTeacherStep(object):
         if split:
             with torch.cuda.stream(side):
                 consistency_branch()
-        if cfg.fused_losses:
-            ce_sc = ops.ce_fused(lo_det[:n_sup], sup_y, grad_lo[:n_sup], out_size, 255, self.align_corners, group=self.group)
-        else:
-            ce_sc, ce_ctx = ops.ce_forward(lo_det[:n_sup], sup_y, out_size, 255, self.align_corners, group=self.group)
-            ops.ce_backward(ce_ctx, ce_sc, grad_lo[:n_sup])
+        ce_sc = ops.ce_fused(lo_det[:n_sup], sup_y, grad_lo[:n_sup], out_size, 255, self.align_corners, group=self.group)
         sex = self._student_executor()
         if split:
             # the re-pack of the data-gradient operands (one HBM-bound launch, ~0.12 ms, needs only the weights) is due in
@@ -592,7 +547,7 @@ class CutMixMeanTeacherStep(object):
         # touched (exchange / optimizer, below): the stem's backward overlaps the last weight gradients
         dex = sex if sex is not None and hasattr(sex, 'join_wgrad') else None
         if dex is not None:
-            dex.defer_wgrad_join = cfg.defer_wgrad_join
+            dex.defer_wgrad_join = True
         if zev is not None:
             main.wait_event(zev)                    # the gradient clear issued on the weight-gradient stream at the head of the step
         try:

@@ -182,8 +182,7 @@ class VATMeanTeacherStep(object):
                     early = [self.teacher.forward_lowres(ub.x_tea) for ub in unsup_batches]
                 # ... and when the direction comes from the teacher too (the default, :102-105), the whole VAT direction pass goes with
                 # it: nothing on that stream touches the student, whose supervised forward / backward runs beside it on the main stream
-                # (CMS_VAT_GRAPH_DIR_SIDE=0: the direction stays on the main stream)
-                if self.vat_dir_net is self.teacher and os.environ.get('CMS_VAT_GRAPH_DIR_SIDE', '1') != '0':
+                if self.vat_dir_net is self.teacher:
                     with torch.cuda.stream(side):
                         adv_early = []
                         for ub in unsup_batches:
@@ -237,12 +236,10 @@ class VATMeanTeacherStep(object):
 
         def passes(ts, capturing):
             ubs = [VATUnsupBatch(*ts[i:i + 3]) for i in range(3, len(ts), 3)]
-            early = capturing and os.environ.get('CMS_VAT_GRAPH_TEACHER_EARLY', '1') != '0'
-            return self._grads(ts[0], ts[1], ubs, ramp, ts[2], teacher_early=early)
+            return self._grads(ts[0], ts[1], ubs, ramp, ts[2], teacher_early=capturing)
 
-        # one capture stream by default; CMS_VAT_GRAPH_SIDE=1: the layer engines' side streams fork / join inside the capture
         return self._graphs.run(flat, extra, passes, nets=(self.student, self.teacher), device=sup_x.device, generator=self.generator,
-                                side_streams=os.environ.get('CMS_VAT_GRAPH_SIDE', '0') == '1', warmup=self.graph_warmup)
+                                warmup=self.graph_warmup)
 
     def __call__(self, sup_x, sup_y, unsup_batches, ramp_val=1.0, eps0=None):
         cfg = self.cfg

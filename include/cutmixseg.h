@@ -329,7 +329,7 @@ typedef struct cms_conv_desc {
 
 int cms_conv_igemm(const cms_conv_desc* d, void* stream);
 /* Which kernel cms_conv_igemm runs this descriptor on (measurement tooling: algorithmic bytes per KERNEL beside the PMC
- * counters; the choice depends on the geometry and on the CMS_CONV8 / CMS_CONV_MIXED switches of the process). */
+ * counters; the choice depends on the geometry and on the CMS_CONV8 switch of the process). */
 #define CMS_ROUTE_OTHER 0     /* an explicit variant / tile request */
 #define CMS_ROUTE_TILE128 1   /* conv_igemm_kernel, 128 channels x 128 pixels */
 #define CMS_ROUTE_MIXED 2     /* conv_igemm_mixed_kernel: the balanced 128 x 128 launch */

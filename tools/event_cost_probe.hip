@@ -5,7 +5,7 @@
 //   0  nothing
 //   1  hipEventRecord(e, M); hipStreamWaitEvent(S1, e); kernel on S1
 //   2  the same for two waiting streams with an event record each          (what csrc/program.hip does today)
-//   3  ONE record, both streams wait for it                                 (CMS_PROG_SHARE_EVENTS=1)
+//   3  ONE record, both streams wait for it                                 (measured in the step, not adopted: profiles/r05p_*)
 //   4  no record: the producing kernel is launched with hipExtLaunchKernelGGL(..., stopEvent = e), both streams wait for e
 //   6  a one-wave setter kernel on M behind the producer, a one-wave waiter kernel on S1 / S2 in front of the consumer
 //   5  as 2, the records issued BEHIND the next kernel of M is not possible (the event would cover it) -- instead: the waiting

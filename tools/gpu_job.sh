@@ -6,7 +6,7 @@
 #   pytest:<expr>               python -m pytest tests -m gpu -k <expr> -s      (expr 'all' = the whole GPU suite)
 #   pyfile:<file>[:<expr>]      one test file (with -s, so PARITY / PER-BLOCK lines reach the log)
 #   bench[:<name>]:<ENV=V,...>:<bench args>     one bench.py --full run with environment overrides (A/B legs), e.g.
-#                               bench:plain0:CMS_CONV_PLAIN=0:--workload pascal --steps 30 --no_cpu_baseline
+#                               bench:conv8off:CMS_CONV8=0:--workload pascal --steps 30 --no_cpu_baseline
 #   rocprof:<bench args>        rocprofv3 --kernel-trace --stats of bench.py, summarised with tools/rocpd_summary.py
 #   pmc:<bench args>            TCC FETCH_SIZE / WRITE_SIZE passes (separate runs, kernel-trace only) -> per-kernel traffic
 #   mfma:<bench args>           one --pmc pass (SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE, kernel-trace only) -> MFMA utilisation per kernel
