@@ -21,6 +21,8 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 
 F32, BF16 = 0, 1
+(BN_REDUCE, BN_FINALIZE, BN_APPLY, BN_REDUCE_BWD, BN_BWD_APPLY, BN_COUNT, BN_STATS, BN_FINALIZE_TILES,
+ BN_BWD_SUMS_TILES) = range(9)      # enum cms_bn_what
 LABEL_U8, LABEL_I64 = 0, 1
 LOSS_IDS = {'var': 0, 'logits_var': 1, 'logits_smoothl1': 2, 'bce': 3, 'kld': 4}
 MODE_MIX, MODE_CUT = 0, 1
@@ -85,7 +87,7 @@ class BnOp(C.Structure):
                 ('sums', c_void_p), ('gamma', c_void_p), ('beta', c_void_p), ('mean', c_void_p), ('rstd', c_void_p),
                 ('scale', c_void_p), ('shift', c_void_p), ('running_mean', c_void_p), ('running_var', c_void_p),
                 ('counter', c_void_p), ('clear_a', c_void_p), ('clear_b', c_void_p), ('ws', c_void_p), ('count', C.c_double), ('n_pixels', C.c_ulonglong), ('eps', c_float),
-                ('momentum', c_float), ('groups', c_int), ('reserved', c_int), ('mask_bits', c_void_p)]
+                ('momentum', c_float), ('groups', c_int), ('tile_rows', c_int), ('mask_bits', c_void_p)]
 
 
 class AugmentDesc(C.Structure):
@@ -154,16 +156,7 @@ PROTOTYPES = {
     'cms_conv_igemm_workspace_bytes': (C.c_longlong, []),
     'cms_conv_igemm_route': (c_int, [_P(ConvDesc)]),
     'cms_conv_igemm_stats_tile_rows': (c_int, [_P(ConvDesc)]),
-    'cms_bn_finalize_tiles': (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'cms_frozen_bn_act_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
-    'cms_bn_apply_groups_bits': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_size_t, c_int, c_int,
-                                         c_void_p, c_void_p]),
-    'cms_bn_reduce_ws_bits': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
-                                      c_void_p, c_void_p]),
-    'cms_bn_bwd_apply_groups_bits': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                             c_void_p, c_void_p, C.c_double, c_size_t, c_int, c_int, c_void_p]),
-    'cms_bn_bwd_sums_tiles': (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p]),
     'cms_conv_set_trace': (c_int, [c_void_p, c_int]),
     'cms_conv_set_wgrad8': (c_int, [c_int]),
     'cms_loss_set_deterministic': (c_int, [c_int]),
@@ -179,24 +172,8 @@ PROTOTYPES = {
     'cms_conv_pack_transpose_batch64': (c_int, [c_void_p, c_int, c_int, c_void_p]),
     'cms_augment_batch': (c_int, [_P(AugmentDesc), c_void_p]),
     'cms_augment_luma': (c_int, [_P(AugmentDesc), c_void_p, c_void_p]),
-    'cms_bn_reduce': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
-                              c_void_p]),
-    'cms_bn_finalize': (c_int, [c_void_p, C.c_double, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    'cms_bn_finalize_ex': (c_int, [c_void_p, C.c_double, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'cms_bn_workspace_bytes': (c_size_t, [c_size_t, c_int, c_int]),
-    'cms_bn_reduce_ws': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
-                                 c_int, c_void_p, c_void_p]),
-    'cms_bn_stats': (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'cms_bn_apply_groups': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_size_t, c_int, c_int,
-                                    c_void_p]),
-    'cms_bn_bwd_apply_groups': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, C.c_double, c_size_t, c_int, c_int, c_void_p]),
-    'cms_bn_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_size_t, c_int, c_void_p]),
-    'cms_bn_bwd_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, C.c_double, c_size_t, c_int, c_void_p]),
+    'cms_bn_run': (c_int, [_P(BnOp), c_void_p]),
     'cms_channel_copy': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_size_t, c_void_p]),
     'cms_add_n': (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     'cms_channel_sum': (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p]),

@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     mean += (size_t)blockIdx.y * C;
     rstd += (size_t)blockIdx.y * C;
     sums += (size_t)blockIdx.y * 2 * C;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;          // multiple of CG (cms_bn_bwd_apply)
+    const size_t stride = (size_t)gridDim.x * blockDim.x;          // multiple of CG (bn_bwd_apply)
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int cg = (int)(i % CG);
     float mu[8], rs[8], grs[8], m1[8], m2[8];
@@ -520,8 +520,8 @@ using namespace cms;
 
 static int bn_geo_ok(size_t p, int c) { return p > 0 && c > 0 && c % 8 == 0; }
 
-extern "C" int cms_bn_reduce(const void* x, const void* dy, const void* y, int dtype, const float* mean, const float* rstd,
-                             double* sums, size_t n_pixels, int c, int mode, void* stream) {
+static int bn_reduce(const void* x, const void* dy, const void* y, int dtype, const float* mean, const float* rstd, double* sums,
+                     size_t n_pixels, int c, int mode, void* stream) {
     CMS_REQUIRE(x && sums, "bn_reduce: NULL pointer");
     CMS_REQUIRE(dtype == CMS_F32 || dtype == CMS_BF16, "bn_reduce: bad dtype");
     CMS_REQUIRE(bn_geo_ok(n_pixels, c), "bn_reduce: bad geometry (channels %% 8 == 0)");
@@ -619,8 +619,8 @@ static int bn_reduce_tiled(const void* x, const void* dy, const void* y, int dty
     return 0;
 }
 
-extern "C" int cms_bn_reduce_ws(const void* x, const void* dy, const void* y, int dtype, const float* mean, const float* rstd,
-                                double* sums, size_t n_pixels, int c, int groups, int mode, void* ws, void* stream) {
+static int bn_reduce_ws(const void* x, const void* dy, const void* y, int dtype, const float* mean, const float* rstd, double* sums,
+                        size_t n_pixels, int c, int groups, int mode, void* ws, void* stream) {
     CMS_REQUIRE(x && sums && ws, "bn_reduce_ws: NULL pointer");
     CMS_REQUIRE(dtype == CMS_F32 || dtype == CMS_BF16, "bn_reduce_ws: bad dtype");
     CMS_REQUIRE(bn_geo_ok(n_pixels, c), "bn_reduce_ws: bad geometry (channels %% 8 == 0)");
@@ -630,8 +630,8 @@ extern "C" int cms_bn_reduce_ws(const void* x, const void* dy, const void* y, in
     return launch_status("cms_bn_reduce_ws");
 }
 
-extern "C" int cms_bn_reduce_ws_bits(const void* x, const void* dy, const uint8_t* mask_bits, int dtype, const float* mean,
-                                     const float* rstd, double* sums, size_t n_pixels, int c, int groups, void* ws, void* stream) {
+static int bn_reduce_ws_bits(const void* x, const void* dy, const uint8_t* mask_bits, int dtype, const float* mean,
+                             const float* rstd, double* sums, size_t n_pixels, int c, int groups, void* ws, void* stream) {
     CMS_REQUIRE(x && dy && mask_bits && mean && rstd && sums && ws, "bn_reduce_ws_bits: NULL pointer");
     CMS_REQUIRE(dtype == CMS_F32 || dtype == CMS_BF16, "bn_reduce_ws_bits: bad dtype");
     CMS_REQUIRE(bn_geo_ok(n_pixels, c), "bn_reduce_ws_bits: bad geometry (channels %% 8 == 0)");
@@ -640,9 +640,9 @@ extern "C" int cms_bn_reduce_ws_bits(const void* x, const void* dy, const uint8_
     return launch_status("cms_bn_reduce_ws_bits");
 }
 
-extern "C" int cms_bn_stats(const void* x, int dtype, size_t n_pixels, int c, int groups, const float* gamma, const float* beta,
-                            float eps, float momentum, float* mean, float* rstd, float* scale, float* shift,
-                            float* running_mean, float* running_var, long long* counter, double* sums, void* ws, void* stream) {
+static int bn_stats(const void* x, int dtype, size_t n_pixels, int c, int groups, const float* gamma, const float* beta, float eps,
+                    float momentum, float* mean, float* rstd, float* scale, float* shift, float* running_mean, float* running_var,
+                    long long* counter, double* sums, void* ws, void* stream) {
     CMS_REQUIRE(x && ws && mean && rstd && scale && shift, "bn_stats: NULL pointer");
     CMS_REQUIRE(dtype == CMS_F32 || dtype == CMS_BF16, "bn_stats: bad dtype");
     CMS_REQUIRE(bn_geo_ok(n_pixels, c), "bn_stats: bad geometry (channels %% 8 == 0)");
@@ -732,7 +732,7 @@ __global__ __launch_bounds__(BNT_CH * BNT_LANES) void bn_finalize_tiles_kernel(c
             double a0 = 0.0, a1 = 0.0;
 #pragma unroll
             for (int w = 0; w < BNT_LANES / 4; ++w) { a0 += red[w][cl]; a1 += red[w][BNT_CH + cl]; }
-            if (sums_out) {                                 // backward statistics: the sums themselves, [G][2][C] (cms_bn_bwd_sums_tiles)
+            if (sums_out) {                                 // backward statistics: the sums themselves, [G][2][C] (bn_bwd_sums_tiles)
                 sums_out[(size_t)g * 2 * C + c] = a0;
                 sums_out[(size_t)g * 2 * C + C + c] = a1;
             } else {
@@ -745,9 +745,9 @@ __global__ __launch_bounds__(BNT_CH * BNT_LANES) void bn_finalize_tiles_kernel(c
     if (blockIdx.x == 0 && tid == 0 && fin.counter) *fin.counter += G;
 }
 
-extern "C" int cms_bn_finalize_tiles(const float* tile_sums, int tile_rows, size_t n_pixels, int c, int groups, const float* gamma,
-                                     const float* beta, float eps, float momentum, float* mean, float* rstd, float* scale,
-                                     float* shift, float* running_mean, float* running_var, long long* counter, void* stream) {
+static int bn_finalize_tiles(const float* tile_sums, int tile_rows, size_t n_pixels, int c, int groups, const float* gamma,
+                             const float* beta, float eps, float momentum, float* mean, float* rstd, float* scale, float* shift,
+                             float* running_mean, float* running_var, long long* counter, void* stream) {
     CMS_REQUIRE(tile_sums && mean && rstd && scale && shift, "bn_finalize_tiles: NULL pointer");
     CMS_REQUIRE(n_pixels > 0 && c > 0 && tile_rows > 0, "bn_finalize_tiles: bad geometry");
     CMS_REQUIRE(n_pixels + (size_t)tile_rows < (1ull << 31), "bn_finalize_tiles: more than 2^31 pixel rows");
@@ -764,9 +764,8 @@ extern "C" int cms_bn_finalize_tiles(const float* tile_sums, int tile_rows, size
 }
 
 // Backward: the tile sums (sum d, sum d xhat) a data-gradient launch wrote (cms_conv_desc.bstats_*) -> sums[groups][2][c], what
-// cms_bn_reduce_ws(mode 1) leaves for cms_bn_bwd_apply_groups. Same kernel, same fixed order.
-extern "C" int cms_bn_bwd_sums_tiles(const float* tile_sums, int tile_rows, size_t n_pixels, int c, int groups, double* sums,
-                                     void* stream) {
+// bn_reduce_ws(mode 1) leaves for bn_bwd_apply. Same kernel, same fixed order.
+static int bn_bwd_sums_tiles(const float* tile_sums, int tile_rows, size_t n_pixels, int c, int groups, double* sums, void* stream) {
     CMS_REQUIRE(tile_sums && sums, "bn_bwd_sums_tiles: NULL pointer");
     CMS_REQUIRE(n_pixels > 0 && c > 0 && tile_rows > 0, "bn_bwd_sums_tiles: bad geometry");
     CMS_REQUIRE(n_pixels + (size_t)tile_rows < (1ull << 31), "bn_bwd_sums_tiles: more than 2^31 pixel rows");
@@ -781,30 +780,17 @@ extern "C" int cms_bn_bwd_sums_tiles(const float* tile_sums, int tile_rows, size
     return launch_status("cms_bn_bwd_sums_tiles");
 }
 
-extern "C" int cms_bn_finalize_ex(const double* sums, double count, const float* gamma, const float* beta, float eps,
-                                  float momentum, float* mean, float* rstd, float* scale, float* shift, float* running_mean,
-                                  float* running_var, int c, double* clear_a, double* clear_b, long long* counter,
-                                  void* stream) {
+static int bn_finalize(const double* sums, double count, const float* gamma, const float* beta, float eps, float momentum,
+                       float* mean, float* rstd, float* scale, float* shift, float* running_mean, float* running_var, int c,
+                       double* clear_a, double* clear_b, long long* counter, void* stream) {
     CMS_REQUIRE(sums && mean && rstd && scale && shift && c > 0 && count > 0, "bn_finalize: NULL pointer / bad geometry");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((c + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, count, gamma, beta,
                        eps, momentum, mean, rstd, scale, shift, running_mean, running_var, c, clear_a, clear_b, counter);
     return launch_status("cms_bn_finalize");
 }
 
-extern "C" int cms_bn_finalize(const double* sums, double count, const float* gamma, const float* beta, float eps,
-                               float momentum, float* mean, float* rstd, float* scale, float* shift, float* running_mean,
-                               float* running_var, int c, void* stream) {
-    return cms_bn_finalize_ex(sums, count, gamma, beta, eps, momentum, mean, rstd, scale, shift, running_mean, running_var, c,
-                              nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int cms_bn_apply_groups(const void* x, const void* res, void* y, int dtype, const float* scale, const float* shift,
-                                   int relu, size_t n_pixels, int c, int groups, void* stream) {
-    return cms_bn_apply_groups_bits(x, res, y, dtype, scale, shift, relu, n_pixels, c, groups, nullptr, stream);
-}
-
-extern "C" int cms_bn_apply_groups_bits(const void* x, const void* res, void* y, int dtype, const float* scale, const float* shift,
-                                        int relu, size_t n_pixels, int c, int groups, uint8_t* mask_bits_out, void* stream) {
+static int bn_apply(const void* x, const void* res, void* y, int dtype, const float* scale, const float* shift, int relu,
+                    size_t n_pixels, int c, int groups, uint8_t* mask_bits_out, void* stream) {
     CMS_REQUIRE(x && y && scale && shift, "bn_apply: NULL pointer");
     CMS_REQUIRE(dtype == CMS_F32 || dtype == CMS_BF16, "bn_apply: bad dtype");
     CMS_REQUIRE(bn_geo_ok(n_pixels, c), "bn_apply: bad geometry (channels %% 8 == 0)");
@@ -864,20 +850,9 @@ extern "C" int cms_frozen_bn_act_bwd(const void* dy, const void* y, void* dx, vo
     return launch_status("cms_frozen_bn_act_bwd");
 }
 
-extern "C" int cms_bn_apply(const void* x, const void* res, void* y, int dtype, const float* scale, const float* shift, int relu,
-                            size_t n_pixels, int c, void* stream) {
-    return cms_bn_apply_groups(x, res, y, dtype, scale, shift, relu, n_pixels, c, 1, stream);
-}
-
-extern "C" int cms_bn_bwd_apply_groups(const void* x, const void* dy, const void* y, void* dx, void* dres, int dtype,
-                                       const float* mean, const float* rstd, const float* gamma, const double* sums, double count,
-                                       size_t n_pixels, int c, int groups, void* stream) {
-    return cms_bn_bwd_apply_groups_bits(x, dy, y, nullptr, dx, dres, dtype, mean, rstd, gamma, sums, count, n_pixels, c, groups, stream);
-}
-
-extern "C" int cms_bn_bwd_apply_groups_bits(const void* x, const void* dy, const void* y, const uint8_t* mask_bits, void* dx, void* dres,
-                                            int dtype, const float* mean, const float* rstd, const float* gamma, const double* sums,
-                                            double count, size_t n_pixels, int c, int groups, void* stream) {
+static int bn_bwd_apply(const void* x, const void* dy, const void* y, const uint8_t* mask_bits, void* dx, void* dres, int dtype,
+                        const float* mean, const float* rstd, const float* gamma, const double* sums, double count, size_t n_pixels,
+                        int c, int groups, void* stream) {
     CMS_REQUIRE(x && dy && dx && mean && rstd && sums, "bn_bwd_apply: NULL pointer");
     CMS_REQUIRE(dtype == CMS_F32 || dtype == CMS_BF16, "bn_bwd_apply: bad dtype");
     CMS_REQUIRE(bn_geo_ok(n_pixels, c) && count > 0, "bn_bwd_apply: bad geometry (channels %% 8 == 0)");
@@ -907,8 +882,40 @@ extern "C" int cms_bn_bwd_apply_groups_bits(const void* x, const void* dy, const
     return launch_status("cms_bn_bwd_apply");
 }
 
-extern "C" int cms_bn_bwd_apply(const void* x, const void* dy, const void* y, void* dx, void* dres, int dtype, const float* mean,
-                                const float* rstd, const float* gamma, const double* sums, double count, size_t n_pixels, int c,
-                                void* stream) {
-    return cms_bn_bwd_apply_groups(x, dy, y, dx, dres, dtype, mean, rstd, gamma, sums, count, n_pixels, c, 1, stream);
+// The one launch entry point: which of the launches above a cms_bn_op runs on (include/cutmixseg.h describes the operands of
+// every kind). Recorded programs (csrc/program.hip) and the eager Python paths both come through here.
+extern "C" int cms_bn_run(const cms_bn_op* op, void* stream) {
+    CMS_REQUIRE(op, "bn_run: NULL op");
+    const cms_bn_op& b = *op;
+    const size_t n = (size_t)b.n_pixels;
+    const int g = b.groups > 1 ? b.groups : 1;
+    const uint8_t* bits = (const uint8_t*)b.mask_bits;
+    switch (b.what) {
+    case CMS_BN_REDUCE:
+        if (b.ws) return bn_reduce_ws(b.x, nullptr, nullptr, b.dtype, nullptr, nullptr, b.sums, n, b.c, g, 0, b.ws, stream);
+        return bn_reduce(b.x, nullptr, nullptr, b.dtype, nullptr, nullptr, b.sums, n, b.c, 0, stream);
+    case CMS_BN_FINALIZE:
+        return bn_finalize(b.sums, b.count, b.gamma, b.beta, b.eps, b.momentum, b.mean, b.rstd, b.scale, b.shift, b.running_mean,
+                           b.running_var, b.c, b.clear_a, b.clear_b, b.counter, stream);
+    case CMS_BN_APPLY:
+        return bn_apply(b.x, b.res, b.y, b.dtype, b.scale, b.shift, b.relu, n, b.c, g, (uint8_t*)b.mask_bits, stream);
+    case CMS_BN_REDUCE_BWD:
+        if (b.ws && bits) return bn_reduce_ws_bits(b.x, b.dy, bits, b.dtype, b.mean, b.rstd, b.sums, n, b.c, g, b.ws, stream);
+        if (b.ws) return bn_reduce_ws(b.x, b.dy, b.y, b.dtype, b.mean, b.rstd, b.sums, n, b.c, g, 1, b.ws, stream);
+        return bn_reduce(b.x, b.dy, b.y, b.dtype, b.mean, b.rstd, b.sums, n, b.c, 1, stream);
+    case CMS_BN_BWD_APPLY:
+        return bn_bwd_apply(b.x, b.dy, b.y, bits, b.dx, b.dres, b.dtype, b.mean, b.rstd, b.gamma, b.sums, b.count, n, b.c, g, stream);
+    case CMS_BN_COUNT:
+        return cms_increment_counter((int64_t*)b.counter, stream);
+    case CMS_BN_STATS:
+        return bn_stats(b.x, b.dtype, n, b.c, g, b.gamma, b.beta, b.eps, b.momentum, b.mean, b.rstd, b.scale, b.shift, b.running_mean,
+                        b.running_var, b.counter, b.sums, b.ws, stream);
+    case CMS_BN_FINALIZE_TILES:
+        return bn_finalize_tiles((const float*)b.ws, b.tile_rows, n, b.c, g, b.gamma, b.beta, b.eps, b.momentum, b.mean, b.rstd, b.scale,
+                                 b.shift, b.running_mean, b.running_var, b.counter, stream);
+    case CMS_BN_BWD_SUMS_TILES:
+        return bn_bwd_sums_tiles((const float*)b.ws, b.tile_rows, n, b.c, g, b.sums, stream);
+    }
+    set_error("bn_run: unknown BatchNorm op %d", b.what);
+    return CMS_EINVAL;
 }

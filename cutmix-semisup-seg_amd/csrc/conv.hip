@@ -1297,7 +1297,7 @@ extern "C" int cms_conv_igemm_route(const cms_conv_desc* d) {
 }
 
 // Pixel rows per tile of the per-tile statistics a launch of this descriptor would write to stats_out ([ceil(M / rows)][2][2][Cout]
-// floats), 0 when it cannot (then cms_bn_stats reads the output back instead), negative for an invalid descriptor.
+// floats), 0 when it cannot (then CMS_BN_STATS reads the output back instead), negative for an invalid descriptor.
 extern "C" int cms_conv_igemm_stats_tile_rows(const cms_conv_desc* d) {
     int rc = conv_check(d);
     if (rc) return rc;

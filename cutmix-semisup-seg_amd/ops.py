@@ -859,6 +859,38 @@ def _world(group):
     return 1
 
 
+_BN_WHAT = {'reduce': _lib.BN_REDUCE, 'finalize': _lib.BN_FINALIZE, 'apply': _lib.BN_APPLY, 'reduce_bwd': _lib.BN_REDUCE_BWD,
+            'bwd_apply': _lib.BN_BWD_APPLY, 'count': _lib.BN_COUNT, 'stats': _lib.BN_STATS, 'finalize_tiles': _lib.BN_FINALIZE_TILES,
+            'sums_tiles': _lib.BN_BWD_SUMS_TILES}
+_BN_DTYPE = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, None: _lib.BF16}      # (None: kinds that touch no activation)
+
+
+def _bn_desc(what, c=0, dtype=None, n_pixels=0, count=0.0, relu=False, eps=1e-5, momentum=0.1, groups=1, tile_rows=0, **t):
+    """The cms_bn_op of one launch (arguments: bn_op). It is host time of the eager U-Net / DeepLab v3+ head passes: the struct
+    starts zeroed and only what is not zero is set."""
+    d = _lib.BnOp()
+    d.what = _BN_WHAT[what]
+    if dtype not in _BN_DTYPE:
+        raise TypeError('unsupported dtype {}'.format(dtype))
+    d.dtype = _BN_DTYPE[dtype]
+    d.c, d.groups, d.n_pixels = int(c), int(groups), int(n_pixels)
+    d.eps, d.momentum = float(eps), float(momentum)
+    if relu:
+        d.relu = 1
+    if count:
+        d.count = float(count)
+    if tile_rows:
+        d.tile_rows = int(tile_rows)
+    for k, v in t.items():
+        if v is not None:
+            setattr(d, k, v.data_ptr())
+    return d
+
+
+def _bn_run(d):
+    check(fn['cms_bn_run'](C.byref(d), _stream()), 'cms_bn_run')
+
+
 class _BatchNormActFn(torch.autograd.Function):
     """relu(batch_norm(x) (+ res)) on NHWC tensors with batch statistics (csrc/bn.hip); under torch.distributed the
     statistics are all-reduced between the two passes of either direction (SyncBN). `groups`: the batch
@@ -877,23 +909,22 @@ class _BatchNormActFn(torch.autograd.Function):
             # [G][2][C] doubles, then finalised group by group, in order (the running statistics move once per group, as in the
             # reference's separate passes); count = the group's pixels on ALL ranks
             stats = torch.empty(groups * 2 * c, dtype=torch.float64, device=dev)
-            check(fn['cms_bn_reduce_ws'](_ptr(x), None, None, _dtype_code(x), None, None, _ptr(stats), n_pix, c, groups, 0, _ptr(ws),
-                                         _stream()), 'cms_bn_reduce_ws')
+            _bn_run(_bn_desc('reduce', c=c, dtype=x.dtype, n_pixels=n_pix, groups=groups, x=x, sums=stats, ws=ws))
             _allreduce_sum(stats, group)
             count = float(n_pix // groups) * world       # (equal shards: the per-GPU batch is fixed under weak scaling)
             for g in range(groups):
                 sl = slice(g * c, (g + 1) * c)
-                check(fn['cms_bn_finalize'](_ptr(stats[g * 2 * c:(g + 1) * 2 * c]), count, _ptr(gamma), _ptr(beta), float(eps),
-                                            float(momentum), _ptr(mean[sl]), _ptr(rstd[sl]), _ptr(scale[sl]), _ptr(shift[sl]),
-                                            _ptr(running_mean), _ptr(running_var), c, _stream()), 'cms_bn_finalize')
+                _bn_run(_bn_desc('finalize', c=c, count=count, eps=eps, momentum=momentum, sums=stats[g * 2 * c:(g + 1) * 2 * c],
+                                 gamma=gamma, beta=beta, mean=mean[sl], rstd=rstd[sl], scale=scale[sl], shift=shift[sl],
+                                 running_mean=running_mean, running_var=running_var))
         else:                                  # statistics and their finalisation in ONE launch
             count = float(n_pix // groups)
-            check(fn['cms_bn_stats'](_ptr(x), _dtype_code(x), n_pix, c, groups, _ptr(gamma), _ptr(beta), float(eps),
-                                     float(momentum), _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(shift), _ptr(running_mean),
-                                     _ptr(running_var), None, None, _ptr(ws), _stream()), 'cms_bn_stats')
+            _bn_run(_bn_desc('stats', c=c, dtype=x.dtype, n_pixels=n_pix, groups=groups, eps=eps, momentum=momentum, x=x, ws=ws,
+                             gamma=gamma, beta=beta, mean=mean, rstd=rstd, scale=scale, shift=shift, running_mean=running_mean,
+                             running_var=running_var))
         y = torch.empty_like(x)
-        check(fn['cms_bn_apply_groups'](_ptr(x), _ptr(res), _ptr(y), _dtype_code(x), _ptr(scale), _ptr(shift), int(bool(relu)),
-                                        n_pix, c, groups, _stream()), 'cms_bn_apply')
+        _bn_run(_bn_desc('apply', c=c, dtype=x.dtype, n_pixels=n_pix, groups=groups, relu=relu, x=x, res=res, y=y, scale=scale,
+                         shift=shift))
         ctx.save_for_backward(x, y if relu else None, mean, rstd, gamma, ws)
         ctx.meta = (n_pix, c, count, group, res is not None, gamma is not None and gamma.requires_grad,
                     beta is not None and beta.requires_grad, groups)
@@ -907,17 +938,16 @@ class _BatchNormActFn(torch.autograd.Function):
         if dy.dtype != x.dtype:
             dy = dy.to(x.dtype)
         sums = torch.empty(groups * 2 * c, dtype=torch.float64, device=x.device)
-        check(fn['cms_bn_reduce_ws'](_ptr(x), _ptr(dy), _ptr(y), _dtype_code(x), _ptr(mean), _ptr(rstd), _ptr(sums), n_pix, c,
-                                     groups, 1, _ptr(ws), _stream()), 'cms_bn_reduce_ws')
+        _bn_run(_bn_desc('reduce_bwd', c=c, dtype=x.dtype, n_pixels=n_pix, groups=groups, x=x, dy=dy, y=y, mean=mean, rstd=rstd,
+                         sums=sums, ws=ws))
         local = sums
         if _world(group) > 1:
             local = sums.clone()                 # parameter gradients stay local (the arena all-reduce sums them)
             _allreduce_sum(sums, group)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if has_res else None
-        check(fn['cms_bn_bwd_apply_groups'](_ptr(x), _ptr(dy), _ptr(y), _ptr(dx), _ptr(dres), _dtype_code(x), _ptr(mean),
-                                            _ptr(rstd), _ptr(gamma), _ptr(sums), count, n_pix, c, groups, _stream()),
-              'cms_bn_bwd_apply')
+        _bn_run(_bn_desc('bwd_apply', c=c, dtype=x.dtype, n_pixels=n_pix, groups=groups, count=count, x=x, dy=dy, y=y, dx=dx,
+                         dres=dres, mean=mean, rstd=rstd, gamma=gamma, sums=sums))
         local = local.view(groups, 2, c).sum(0)    # the groups' passes add into the same parameter gradients
         dgamma = local[1].float() if want_g else None
         dbeta = local[0].float() if want_b else None
@@ -926,15 +956,14 @@ class _BatchNormActFn(torch.autograd.Function):
 
 class _FrozenBnActFn(torch.autograd.Function):
     """relu(x * scale + shift (+ res)) on contiguous NHWC tensors, scale / shift fp32 [C] WITHOUT gradient (an eval-mode BatchNorm whose
-    affine does not train: the teacher of the VAT trainer): one launch forward (cms_bn_apply), one backward (cms_frozen_bn_act_bwd)."""
+    affine does not train: the teacher of the VAT trainer): one launch forward (the 'apply' kind), one backward (cms_frozen_bn_act_bwd)."""
 
     @staticmethod
     def forward(ctx, x, scale, shift, res, relu):
         n_pix = x.numel() // x.shape[-1]
         c = int(x.shape[-1])
         y = torch.empty_like(x)
-        check(fn['cms_bn_apply_groups_bits'](_ptr(x), _ptr(res) if res is not None else None, _ptr(y), _dtype_code(x), _ptr(scale), _ptr(shift),
-                                             int(bool(relu)), n_pix, c, 1, None, _stream()), 'cms_bn_apply')
+        _bn_run(_bn_desc('apply', c=c, dtype=x.dtype, n_pixels=n_pix, relu=relu, x=x, res=res, y=y, scale=scale, shift=shift))
         ctx.save_for_backward(scale, y if relu else None)
         ctx.geo = (n_pix, c, res is not None)
         return y
@@ -991,79 +1020,30 @@ def bn_workspace(n_pixels, c, device, groups=1):
     return ws
 
 
-_BN_WHAT = {'reduce': 0, 'finalize': 1, 'apply': 2, 'reduce_bwd': 3, 'bwd_apply': 4, 'count': 5, 'stats': 6, 'finalize_tiles': 7, 'sums_tiles': 8}
-
-
 def bn_op(what, c=0, dtype=None, n_pixels=0, count=0.0, relu=False, eps=1e-5, momentum=0.1, groups=1, tile_rows=0, **t):
-    """One launch of the batch-statistics BatchNorm protocol (csrc/bn.hip) on caller-owned buffers -- issued now, or appended
-    to the program being recorded (cms_program_add_bn): the executor's batch-statistics passes (backbone_hip.py) are made of
-    these. `what`: reduce | finalize | apply | reduce_bwd | bwd_apply | count | stats (= reduce + finalize in one launch) |
+    """One launch of the batch-statistics BatchNorm protocol (csrc/bn.hip: cms_bn_run) on caller-owned buffers -- issued now, or
+    appended to the program being recorded (cms_program_add_bn): the executor's batch-statistics passes (backbone_hip.py) are made
+    of these. `what`: reduce | finalize | apply | reduce_bwd | bwd_apply | count | stats (= reduce + finalize in one launch) |
     finalize_tiles (statistics from the tile sums the unit's convolution wrote: ws = conv_igemm's stats['tile_sums'], tile_rows) |
     sums_tiles (backward sums from the tile sums of the data-gradient launch that wrote dy: ws, tile_rows -> sums);
     tensors by keyword (x, res, y, dy, dx, dres, sums, gamma, beta, mean, rstd, scale, shift, running_mean, running_var,
     counter, clear_a, clear_b, ws, mask_bits). `mask_bits` (uint8 [pixel rows][c / 8]): 'apply' writes [y > 0] there as bits,
-    'reduce_bwd' (with ws) / 'bwd_apply' read them instead of y (1/16 of its bytes; bit-identical results). With `ws` (bn_workspace) the reductions take the atomics-free kernels; `groups` > 1
-    (sample groups normalised separately, include/cutmixseg.h) needs them. `count` = pixels of one group."""
+    'reduce_bwd' (with ws) / 'bwd_apply' read them instead of y (1/16 of its bytes; bit-identical results). With `ws` (bn_workspace)
+    the reductions take the atomics-free kernels; `groups` > 1 (sample groups normalised separately) needs them. `count` = pixels
+    of one group. include/cutmixseg.h (cms_bn_op) says which kind reads which field."""
     _need_cuda(*t.values())
-    d = _lib.BnOp()
-    d.what = _BN_WHAT[what]
-    d.dtype = _lib.F32 if dtype == torch.float32 else _lib.BF16
-    d.c, d.relu, d.groups = int(c), int(bool(relu)), int(groups)
-    for k, v in t.items():
-        setattr(d, k, None if v is None else v.data_ptr())
-    d.count, d.n_pixels = float(count), int(n_pixels)
-    d.eps, d.momentum = float(eps), float(momentum)
-    d.reserved = int(tile_rows)
-    has_ws = t.get('ws') is not None
-    if d.groups > 1 and what in ('reduce', 'reduce_bwd') and not has_ws:
+    if int(groups) > 1 and what in ('reduce', 'reduce_bwd') and t.get('ws') is None:
         raise ValueError('bn_op: grouped reductions need a workspace')
-    if _REC is not None:
-        prog = _REC[0]
-        idx = fn['cms_program_add_bn'](prog.h, C.byref(d), _rec_stream_index(), prog.group)
-        if idx < 0:
-            check(idx, 'cms_program_add_bn')
-        prog.keep += [v for v in t.values() if v is not None]
-        prog.bn_kinds[what] = prog.bn_kinds.get(what, 0) + 1
+    d = _bn_desc(what, c, dtype, n_pixels, count, relu, eps, momentum, groups, tile_rows, **t)
+    if _REC is None:
+        _bn_run(d)
         return
-    g = lambda k: _ptr(t.get(k))
-    G = max(1, d.groups)
-    if what == 'reduce' and has_ws:
-        check(fn['cms_bn_reduce_ws'](g('x'), None, None, d.dtype, None, None, g('sums'), d.n_pixels, d.c, G, 0, g('ws'),
-                                     _stream()), 'cms_bn_reduce_ws')
-    elif what == 'reduce':
-        check(fn['cms_bn_reduce'](g('x'), None, None, d.dtype, None, None, g('sums'), d.n_pixels, d.c, 0, _stream()), 'cms_bn_reduce')
-    elif what == 'stats':
-        check(fn['cms_bn_stats'](g('x'), d.dtype, d.n_pixels, d.c, G, g('gamma'), g('beta'), d.eps, d.momentum, g('mean'),
-                                 g('rstd'), g('scale'), g('shift'), g('running_mean'), g('running_var'), g('counter'), g('sums'),
-                                 g('ws'), _stream()), 'cms_bn_stats')
-    elif what == 'finalize_tiles':
-        check(fn['cms_bn_finalize_tiles'](g('ws'), int(tile_rows), d.n_pixels, d.c, G, g('gamma'), g('beta'), d.eps, d.momentum,
-                                          g('mean'), g('rstd'), g('scale'), g('shift'), g('running_mean'), g('running_var'),
-                                          g('counter'), _stream()), 'cms_bn_finalize_tiles')
-    elif what == 'sums_tiles':
-        check(fn['cms_bn_bwd_sums_tiles'](g('ws'), int(tile_rows), d.n_pixels, d.c, G, g('sums'), _stream()), 'cms_bn_bwd_sums_tiles')
-    elif what == 'finalize':
-        check(fn['cms_bn_finalize_ex'](g('sums'), d.count, g('gamma'), g('beta'), d.eps, d.momentum, g('mean'), g('rstd'),
-                                       g('scale'), g('shift'), g('running_mean'), g('running_var'), d.c, g('clear_a'),
-                                       g('clear_b'), g('counter'), _stream()), 'cms_bn_finalize_ex')
-    elif what == 'apply':
-        check(fn['cms_bn_apply_groups_bits'](g('x'), g('res'), g('y'), d.dtype, g('scale'), g('shift'), d.relu, d.n_pixels, d.c, G,
-                                             g('mask_bits'), _stream()), 'cms_bn_apply')
-    elif what == 'reduce_bwd' and has_ws and t.get('mask_bits') is not None:
-        check(fn['cms_bn_reduce_ws_bits'](g('x'), g('dy'), g('mask_bits'), d.dtype, g('mean'), g('rstd'), g('sums'), d.n_pixels, d.c,
-                                          G, g('ws'), _stream()), 'cms_bn_reduce_ws_bits')
-    elif what == 'reduce_bwd' and has_ws:
-        check(fn['cms_bn_reduce_ws'](g('x'), g('dy'), g('y'), d.dtype, g('mean'), g('rstd'), g('sums'), d.n_pixels, d.c, G, 1,
-                                     g('ws'), _stream()), 'cms_bn_reduce_ws')
-    elif what == 'reduce_bwd':
-        check(fn['cms_bn_reduce'](g('x'), g('dy'), g('y'), d.dtype, g('mean'), g('rstd'), g('sums'), d.n_pixels, d.c, 1, _stream()),
-              'cms_bn_reduce')
-    elif what == 'bwd_apply':
-        check(fn['cms_bn_bwd_apply_groups_bits'](g('x'), g('dy'), g('y'), g('mask_bits'), g('dx'), g('dres'), d.dtype, g('mean'),
-                                                 g('rstd'), g('gamma'), g('sums'), d.count, d.n_pixels, d.c, G, _stream()),
-              'cms_bn_bwd_apply')
-    else:
-        check(fn['cms_increment_counter'](g('counter'), _stream()), 'cms_increment_counter')
+    prog = _REC[0]
+    idx = fn['cms_program_add_bn'](prog.h, C.byref(d), _rec_stream_index(), prog.group)
+    if idx < 0:
+        check(idx, 'cms_program_add_bn')
+    prog.keep += [v for v in t.values() if v is not None]
+    prog.bn_kinds[what] = prog.bn_kinds.get(what, 0) + 1
 
 
 # ---------------------------------------------------------------------------------------------- stem

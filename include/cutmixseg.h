@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CMS_VERSION 100
+#define CMS_VERSION 101
 
 #define CMS_OK 0
 #define CMS_EINVAL (-1)     /* bad argument */
@@ -307,9 +307,9 @@ typedef struct cms_conv_desc {
      * stats_out != NULL (bf16 NHWC output, mode 0): every workgroup also writes the per-channel (sum, sum of squares) of the bf16
      * values it STORES, per pixel tile: float [tiles][2 slots][2][cout], tiles = ceil(n * ho * wo / T), T =
      * cms_conv_igemm_stats_tile_rows(desc) (128 or 256 rows: the kernel that runs the launch; 0 = this launch cannot, use
-     * cms_bn_stats). The pixel rows are `groups` equal runs of stats_rows_per_group rows (sample groups normalised separately);
+     * CMS_BN_STATS). The pixel rows are `groups` equal runs of stats_rows_per_group rows (sample groups normalised separately);
      * slot 0 = the tile's rows of the group its FIRST row belongs to, slot 1 = its rows of the next group (written only by a tile that
-     * straddles a boundary). cms_bn_finalize_tiles turns them into mean / rstd / scale / shift and moves the running statistics. */
+     * straddles a boundary). CMS_BN_FINALIZE_TILES turns them into mean / rstd / scale / shift and moves the running statistics. */
     float* stats_out;
     int stats_rows_per_group;
     /* Round 5, data gradients with BOTH res and mask_bits: != 0 -> the bits gate the residual only, y = acc + (bit ? res : 0)
@@ -319,8 +319,8 @@ typedef struct cms_conv_desc {
     /* Round 5, data gradients (mode 1) with stats_out: the launch writes the gradient dy of the OUTPUT of a batch-statistics unit
      * y = relu(bn(u) (+ res)); with that unit's u (bf16, indexed like this launch's output), ReLU mask bits (NULL: no ReLU) and
      * statistics mean / rstd [groups][cout] it also leaves per-tile (sum d, sum d * xhat), d = bit ? dy : 0, xhat = (u - mean) * rstd --
-     * cms_bn_bwd_sums_tiles adds them into the sums cms_bn_bwd_apply_groups takes: the unit's backward reduction over u, dy and the
-     * mask (cms_bn_reduce_ws mode 1) is not launched. The stored output is unchanged (unmasked dy).                              */
+     * CMS_BN_BWD_SUMS_TILES adds them into the sums CMS_BN_BWD_APPLY takes: the unit's backward reduction over u, dy and the
+     * mask (CMS_BN_REDUCE_BWD) is not launched. The stored output is unchanged (unmasked dy).                              */
     const void* bstats_u;
     const uint8_t* bstats_bits;
     const float* bstats_mean;
@@ -489,70 +489,78 @@ int cms_augment_luma(const cms_augment_desc* d, float* luma, void* stream);
 /* ------------------------------------------------------------------------------------------------------------
  * Batch-statistics BatchNorm (+ ReLU, + residual) on NHWC activations (csrc/bn.hip): nn.BatchNorm2d in training mode,
  * architectures/deeplab2.py:72-84 without --freeze_bn, architectures/deeplab3plus.py:40-64 (head, always).
- * Statistics are a two-pass protocol so that a data-parallel caller can all-reduce `sums` (and the pixel count) between
- * the passes: SyncBN, SURVEY.md 8(e). `sums` = double[2*C], zero-filled by the caller, accumulated with atomics.
- *   forward : cms_bn_reduce(mode 0) -> sums = (sum x, sum x^2);  cms_bn_finalize -> mean, rstd, scale, shift and the
- *             running statistics (momentum, unbiased variance);  cms_bn_apply: y = relu(x*scale + shift (+ res))
- *   backward: cms_bn_reduce(mode 1) -> sums = (sum dy', sum dy'*xhat), dy' = dy * [y > 0] (y NULL: no ReLU);
- *             cms_bn_bwd_apply: dx = gamma*rstd*(dy' - sums0/count - xhat*sums1/count), optional dres = dy'.
+ * ONE descriptor (cms_bn_op) and ONE launch entry point (cms_bn_run, or cms_program_add_bn inside a recorded program);
+ * `what` names the launch, the fields a kind does not list are ignored (leave them NULL / 0):
+ *   forward : REDUCE -> sums = (sum x, sum x^2);  FINALIZE -> mean, rstd, scale, shift and the running statistics (momentum,
+ *             unbiased variance);  APPLY: y = relu(x*scale + shift (+ res)).
+ *             STATS = REDUCE + FINALIZE in one launch (single-process callers); FINALIZE_TILES = the same from the tile sums
+ *             the unit's convolution wrote (cms_conv_desc.stats_out): no pass over x at all.
+ *   backward: REDUCE_BWD -> sums = (sum dy', sum dy'*xhat), dy' = dy * [y > 0] (no mask given: no ReLU); BWD_SUMS_TILES = the
+ *             same from the tile sums of the data-gradient launch that wrote dy (cms_conv_desc.bstats_*);
+ *             BWD_APPLY: dx = gamma*rstd*(dy' - sums0/count - xhat*sums1/count), optional dres = dy'.
  *             dgamma = sums1, dbeta = sums0 (of the LOCAL pass).
+ *   COUNT   : *counter += 1 (cms_increment_counter as a program op).
+ * Statistics are a two-pass protocol so that a data-parallel caller can all-reduce `sums` between the passes (SyncBN,
+ * SURVEY.md 8(e)): forward between REDUCE and FINALIZE, backward between REDUCE_BWD / BWD_SUMS_TILES and BWD_APPLY, with
+ * `count` = the pixels of one group on ALL ranks. STATS and FINALIZE_TILES take count = n_pixels / groups themselves.
+ * Sample groups (`groups` >= 1, dividing n_pixels): the pixel rows are `groups` equal runs of consecutive samples whose
+ * statistics are kept apart -- ONE launch over [supervised batch; mixed batch] normalises each exactly as the reference's
+ * separate forward passes do (train_seg_semisup_mask_mt.py:296-358); the running statistics move once per group, in group
+ * order, `counter` by `groups`. Layouts with groups: mean / rstd / scale / shift float[groups][c], sums double[groups][2][c].
+ * FINALIZE handles ONE group of c channels (a grouped caller issues it per group on slices of sums / mean / ... ).
  * ------------------------------------------------------------------------------------------------------------ */
-int cms_bn_reduce(const void* x, const void* dy, const void* y, int dtype, const float* mean, const float* rstd, double* sums,
-                  size_t n_pixels, int c, int mode, void* stream);
-int cms_bn_finalize(const double* sums, double count, const float* gamma, const float* beta, float eps, float momentum,
-                    float* mean, float* rstd, float* scale, float* shift, float* running_mean, float* running_var, int c,
-                    void* stream);
-/* The same, plus what a REPLAYED pass needs from this launch (cms_program_add_bn): `clear_a` / `clear_b` (double[2*c] each, or
- * NULL) are zeroed after the statistics were read -- normally the forward sums themselves and the sums of the unit's backward
- * pass -- and `counter` (nn.BatchNorm2d.num_batches_tracked, or NULL) is incremented: three tiny launches fewer per layer. */
-int cms_bn_finalize_ex(const double* sums, double count, const float* gamma, const float* beta, float eps, float momentum,
-                       float* mean, float* rstd, float* scale, float* shift, float* running_mean, float* running_var, int c,
-                       double* clear_a, double* clear_b, long long* counter, void* stream);
-/* Round 3: the reductions without data atomics (inside the step the fp64 adds of cms_bn_reduce queue behind the weight
- * gradients' fp32 atomics in the memory-side units: 52 us per launch in the step against 10-22 alone). Blocks own 64-channel
- * tiles, store partial sums into `ws` and the last block of a tile adds them in fixed order in fp64: bit-reproducible; `sums` is
- * OVERWRITTEN, not accumulated. `ws`: cms_bn_workspace_bytes(n_pixels, c, groups) bytes, zero-filled once by the caller, owned
- * by one call site (launches on different streams must not share it); it is left ready for the next launch.
- * `groups` (>= 1, dividing n_pixels): the pixel rows are `groups` equal runs of consecutive samples whose statistics are kept
- * apart -- ONE launch over [supervised batch; mixed batch] normalises each exactly as the reference's separate forward passes
- * do (train_seg_semisup_mask_mt.py:296-358); the running statistics move once per group, in group order, `counter` by `groups`.
- * Layouts with groups: mean / rstd / scale / shift float[groups][c], sums double[groups][2][c]; `count` = pixels of ONE group.
- *   cms_bn_reduce_ws : cms_bn_reduce's contract (mode 0 / 1) -- the data-parallel protocol all-reduces `sums` after it.
- *   cms_bn_stats     : forward statistics AND cms_bn_finalize_ex's work (count = n_pixels / groups) in the one launch, for
- *                      single-process callers; `sums` optional (NULL: not written).
- *   cms_bn_apply_groups / cms_bn_bwd_apply_groups : the element-wise passes with per-group coefficients. */
+enum cms_bn_what { CMS_BN_REDUCE = 0, CMS_BN_FINALIZE, CMS_BN_APPLY, CMS_BN_REDUCE_BWD, CMS_BN_BWD_APPLY, CMS_BN_COUNT,
+                   CMS_BN_STATS, CMS_BN_FINALIZE_TILES, CMS_BN_BWD_SUMS_TILES };
+
+typedef struct cms_bn_op {
+    int what;                  /* enum cms_bn_what                                                             */
+    int dtype, c, relu;        /* of x / y / dy / dx / dres; channels (c % 8 == 0); APPLY: ReLU                */
+    const void* x;             /* conv output u, NHWC                                                          */
+    const void* res;           /* APPLY: residual or NULL                                                      */
+    void* y;                   /* APPLY: output; REDUCE_BWD / BWD_APPLY: the stored output (ReLU mask) or NULL */
+    const void* dy;            /* backward: incoming gradient                                                  */
+    void* dx;                  /* BWD_APPLY: gradient wrt x                                                    */
+    void* dres;                /* BWD_APPLY: gradient wrt the residual (= masked dy) or NULL                   */
+    double* sums;              /* double[groups][2][c]. Without `ws`, REDUCE / REDUCE_BWD ACCUMULATE into it with atomics (the
+                                * caller zero-fills; layers wider than 2048 channels run as channel slices); with `ws` and from
+                                * BWD_SUMS_TILES it is OVERWRITTEN, bit-reproducibly. STATS: optional copy of the sums (NULL: not
+                                * written). Read by FINALIZE and BWD_APPLY                                                     */
+    const float* gamma;        /* FINALIZE / STATS / FINALIZE_TILES / BWD_APPLY; NULL = 1                      */
+    const float* beta;         /* NULL = 0                                                                     */
+    float* mean;               /* written by FINALIZE / STATS / FINALIZE_TILES, read by the backward kinds     */
+    float* rstd;
+    float* scale;              /* gamma * rstd: written like mean, read by APPLY                               */
+    float* shift;              /* beta - mean * scale                                                          */
+    float* running_mean;       /* FINALIZE / STATS / FINALIZE_TILES: moved like nn.BatchNorm2d's, or NULL      */
+    float* running_var;
+    long long* counter;        /* num_batches_tracked: COUNT; optional for FINALIZE (+ 1) and STATS / FINALIZE_TILES (+ groups) */
+    double* clear_a;           /* FINALIZE: double[2*c] each, zeroed after the statistics were read -- normally the forward sums   */
+    double* clear_b;           /* themselves and the sums of the unit's backward pass, for their next replay -- or NULL            */
+    void* ws;                  /* REDUCE / REDUCE_BWD (optional; needed for groups > 1 and for mask_bits) and STATS: the reductions
+                                * WITHOUT data atomics -- blocks own 64-channel tiles, store partial sums here and the last block of a
+                                * tile adds them in fixed order in fp64. cms_bn_workspace_bytes(n_pixels, c, groups) bytes, zero-filled
+                                * once by the caller, owned by one call site (launches on different streams must not share it), left
+                                * ready for the next launch. FINALIZE_TILES / BWD_SUMS_TILES: the tile sums instead, float
+                                * [tiles][2 slots][2][c] as cms_conv_desc.stats_out describes them                                 */
+    double count;              /* FINALIZE / BWD_APPLY: pixels the statistics of ONE group run over            */
+    unsigned long long n_pixels; /* pixel rows of x (all groups)                                               */
+    float eps, momentum;
+    int groups;                /* sample groups (0 / 1: one)                                                   */
+    int tile_rows;             /* FINALIZE_TILES / BWD_SUMS_TILES: pixel rows per statistics tile (cms_conv_igemm_stats_tile_rows of
+                                * the launch that wrote them); a group is at least one tile long, groups <= 64 */
+    void* mask_bits;           /* the ReLU mask as BITS beside y -- uint8 [pixel rows][c / 8], bit e of byte (row, v) = [stored
+                                * y[row][8 v + e] > 0], the layout of cms_conv_desc.mask_bits_out. APPLY writes them (or NULL);
+                                * REDUCE_BWD (with ws) and BWD_APPLY read them INSTEAD of y: 1/16 of the bytes of one of the three
+                                * tensors they stream, bit-identical results. NULL: y is the mask                                  */
+} cms_bn_op;
+
 size_t cms_bn_workspace_bytes(size_t n_pixels, int c, int groups);
-int cms_bn_reduce_ws(const void* x, const void* dy, const void* y, int dtype, const float* mean, const float* rstd, double* sums,
-                     size_t n_pixels, int c, int groups, int mode, void* ws, void* stream);
-int cms_bn_stats(const void* x, int dtype, size_t n_pixels, int c, int groups, const float* gamma, const float* beta, float eps,
-                 float momentum, float* mean, float* rstd, float* scale, float* shift, float* running_mean, float* running_var,
-                 long long* counter, double* sums, void* ws, void* stream);
-int cms_bn_apply_groups(const void* x, const void* res, void* y, int dtype, const float* scale, const float* shift, int relu,
-                        size_t n_pixels, int c, int groups, void* stream);
-int cms_bn_bwd_apply_groups(const void* x, const void* dy, const void* y, void* dx, void* dres, int dtype, const float* mean,
-                            const float* rstd, const float* gamma, const double* sums, double count, size_t n_pixels, int c,
-                            int groups, void* stream);
-/* Round 5: the ReLU mask of a unit as BITS beside its output -- uint8 [pixel rows][c / 8], bit e of byte (row, v) = [stored
- * y[row][8 v + e] > 0], the layout of cms_conv_desc.mask_bits_out. cms_bn_apply_groups_bits writes them (mask_bits_out may be NULL),
- * the backward passes read them INSTEAD of y: 1/16 of the bytes of one of the three tensors each of them streams.
- * (cms_bn_bwd_apply_groups_bits: mask_bits == NULL falls back to y.) Results are bit-identical to the y-masked calls. */
-int cms_bn_apply_groups_bits(const void* x, const void* res, void* y, int dtype, const float* scale, const float* shift, int relu,
-                             size_t n_pixels, int c, int groups, uint8_t* mask_bits_out, void* stream);
+int cms_bn_run(const cms_bn_op* op, void* stream);
 /* Backward of y = relu(x * scale + shift (+ res)) with FROZEN statistics (an eval-mode BatchNorm as an affine: the forward is
- * cms_bn_apply with scale = gamma * rstd, shift = beta - mean * scale; architectures/deeplab2.py LayerEngine.bn_act, the teacher of
+ * CMS_BN_APPLY with scale = gamma * rstd, shift = beta - mean * scale; architectures/deeplab2.py LayerEngine.bn_act, the teacher of
  * train_seg_semisup_vat_mt.py:237): dx = scale * dy', dres = dy' (or NULL), dy' = dy * [y > 0] (y = the forward's output; NULL: no ReLU). */
 int cms_frozen_bn_act_bwd(const void* dy, const void* y, void* dx, void* dres, int dtype, const float* scale, size_t n_pixels, int c,
                           void* stream);
-int cms_bn_reduce_ws_bits(const void* x, const void* dy, const uint8_t* mask_bits, int dtype, const float* mean, const float* rstd,
-                          double* sums, size_t n_pixels, int c, int groups, void* ws, void* stream);
-int cms_bn_bwd_apply_groups_bits(const void* x, const void* dy, const void* y, const uint8_t* mask_bits, void* dx, void* dres,
-                                 int dtype, const float* mean, const float* rstd, const float* gamma, const double* sums,
-                                 double count, size_t n_pixels, int c, int groups, void* stream);
-int cms_bn_apply(const void* x, const void* res, void* y, int dtype, const float* scale, const float* shift, int relu,
-                 size_t n_pixels, int c, void* stream);
-int cms_bn_bwd_apply(const void* x, const void* dy, const void* y, void* dx, void* dres, int dtype, const float* mean,
-                     const float* rstd, const float* gamma, const double* sums, double count, size_t n_pixels, int c,
-                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * NHWC data movement of the DeepLab v3+ head (csrc/nhwc.hip; reference: architectures/deeplab3plus.py:40-55 -- torch.cat of
@@ -650,22 +658,6 @@ int cms_program_add_sync(cms_program* p, int from_stream, int to_stream, int gro
  * (The reference has no counterpart: its step is one stream, train_seg_semisup_mask_mt.py:287-476.) */
 int cms_program_sync_count(const cms_program* p);
 int cms_program_set_sync_flags(cms_program* p, int* flags_dev, int n_flags);
-/* Batch-statistics BatchNorm launches inside a program (round 3: DeepLab v2 WITHOUT --freeze_bn on the executor,
- * architectures/deeplab2.py:72-84 / train_seg_semisup_mask_mt.py:587). `what`: 0 = cms_bn_reduce(mode 0), 1 = cms_bn_finalize,
- * 2 = cms_bn_apply, 3 = cms_bn_reduce(mode 1), 4 = cms_bn_bwd_apply, 5 = cms_increment_counter(counter), 6 = cms_bn_stats,
- * 7 = cms_bn_finalize_tiles (tile sums in `ws`, tile rows in `reserved`), 8 = cms_bn_bwd_sums_tiles (likewise; writes `sums`); unused pointers NULL. With `ws` set, what 0 / 3
- * run cms_bn_reduce_ws.
- * All buffers are the caller's and persistent (a program is replayed many times). */
-/* Statistics of a unit from the tile sums its convolution wrote (cms_conv_desc.stats_out): per group and channel the tiles' sums are
- * added in a fixed order in fp64, then finalised exactly like cms_bn_stats (mean / rstd / scale / shift [groups][c], running statistics
- * moved once per group in group order, *counter += groups). tile_rows = cms_conv_igemm_stats_tile_rows of that launch. */
-int cms_bn_finalize_tiles(const float* tile_sums, int tile_rows, size_t n_pixels, int c, int groups, const float* gamma,
-                          const float* beta, float eps, float momentum, float* mean, float* rstd, float* scale, float* shift,
-                          float* running_mean, float* running_var, long long* counter, void* stream);
-
-/* backward counterpart: tile sums of a data-gradient launch with bstats_* -> sums[groups][2][c] (double) for cms_bn_bwd_apply_groups */
-int cms_bn_bwd_sums_tiles(const float* tile_sums, int tile_rows, size_t n_pixels, int c, int groups, double* sums, void* stream);
-
 /* Trainable BatchNorm affine over frozen statistics on the eight-phase weight-gradient kernel (csrc/wfinish.hip; the torchvision
  * backbone of architectures/deeplab3plus.py:96-98 + autograd): the weight-gradient launch writes the UNSCALED gradient G into a
  * scratch tensor of the weight's shape, cms_channel_sum takes d(beta) = sum_p dU, and one finishing launch per backward pass does,
@@ -690,35 +682,8 @@ int cms_program_add_channel_sum(cms_program* p, const void* src, int dtype, size
                                 int group);
 int cms_program_add_wgrad_finish(cms_program* p, const void* items_dev, int n_items, int total_blocks, int stream_idx, int group);
 
-typedef struct cms_bn_op {
-    int what, dtype, c, relu;
-    const void* x;             /* conv output u, NHWC                                                          */
-    const void* res;           /* apply: residual or NULL                                                      */
-    void* y;                   /* apply: output; reduce(mode 1) / bwd_apply: the stored output (ReLU mask) or NULL */
-    const void* dy;            /* backward: incoming gradient                                                  */
-    void* dx;                  /* bwd_apply: gradient wrt x                                                    */
-    void* dres;                /* bwd_apply: gradient wrt the residual (= masked dy) or NULL                   */
-    double* sums;              /* double[2*c] (+1): forward / backward sums                                    */
-    const float* gamma;
-    const float* beta;
-    float* mean;
-    float* rstd;
-    float* scale;
-    float* shift;
-    float* running_mean;
-    float* running_var;
-    long long* counter;        /* what 1 (optional) / what 5: num_batches_tracked                              */
-    double* clear_a;           /* what 1: zeroed after the statistics were read (cms_bn_finalize_ex), or NULL  */
-    double* clear_b;
-    void* ws;                  /* what 0 / 3 (optional), 6: cms_bn_workspace_bytes(n_pixels, c, groups) bytes;
-                                * what 7: the tile sums (cms_conv_desc.stats_out of the unit's convolution)   */
-    double count;              /* pixels the statistics run over                                               */
-    unsigned long long n_pixels;
-    float eps, momentum;
-    int groups;                /* sample groups (0 / 1: one); needs `ws` for what 0 / 3                       */
-    int reserved;              /* what 7: pixel rows per statistics tile (cms_conv_igemm_stats_tile_rows)      */
-    void* mask_bits;           /* what 2: written ([y > 0] as bits, or NULL); what 3 (with ws) / 4: read instead of y */
-} cms_bn_op;
+/* A cms_bn_run launch inside a program (DeepLab v2 WITHOUT --freeze_bn on the executor, architectures/deeplab2.py:72-84 /
+ * train_seg_semisup_mask_mt.py:587). All buffers are the caller's and persistent (a program is replayed many times). */
 int cms_program_add_bn(cms_program* p, const cms_bn_op* op, int stream_idx, int group);
 int cms_program_size(const cms_program* p);
 /* enqueue ops [first, last) (last < 0: to the end); never synchronises the host */

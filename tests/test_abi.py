@@ -28,7 +28,7 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(_lib.lib, n), 'libcutmixseg_hip.so does not export {}'.format(n)
     assert sorted(_lib.PROTOTYPES.keys()) == names, 'ctypes prototype table and header disagree'
-    assert _lib.version() == 100
+    assert _lib.version() == 101
 
 
 def test_struct_layouts_match_the_c_compiler():
