@@ -152,6 +152,9 @@ PROTOTYPES = {
     'cms_argmax_confusion': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_void_p, c_void_p, c_void_p]),
     'cms_confusion': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    'cms_fill_holes_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'cms_fill_holes': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
+                               c_void_p]),
     'cms_conv_igemm': (c_int, [_P(ConvDesc), c_void_p]),
     'cms_conv_igemm_workspace_bytes': (C.c_longlong, []),
     'cms_conv_igemm_route': (c_int, [_P(ConvDesc)]),

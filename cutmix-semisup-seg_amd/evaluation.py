@@ -6,7 +6,8 @@ The reference loops over classes in numpy on the host (evaluation.py:24-33; 0.28
 Here truth / prediction maps are histogrammed on the GPU into one C x C int64 matrix; intersection and union follow
 from it exactly: I = diag(cm), U = rowsum + colsum - diag (integer identity).
 `EvaluatorIoU.sample_logits` is the fused path used by the trainer: bilinear upsample + argmax + histogram straight
-from the network's low-resolution logits, nothing full-resolution ever leaves the device.
+from the network's low-resolution logits, nothing full-resolution ever leaves the device. With `fill_holes` (binary
+configurations) the argmax map is hole-filled on the device as well (csrc/fillholes.hip), fused with the histogram.
 """
 import numpy as np
 import torch
@@ -63,24 +64,26 @@ class EvaluatorIoU(object):
         return self._cm_dev
 
     def sample(self, truth, prediction, ignore_value=None):
-        """Accumulate one (H,W) [or batched] pair of integer maps (numpy or torch)."""
-        if self.fill_holes:
-            # binary post-processing stays a host-side scipy call, as in the reference (evaluation.py:53-55)
-            from scipy.ndimage import binary_fill_holes
-            p = prediction.cpu().numpy() if torch.is_tensor(prediction) else np.asarray(prediction)
-            prediction = binary_fill_holes(p != 0).astype(np.uint8)
+        """Accumulate one (H,W) [or batched (N,H,W)] pair of integer maps (numpy or torch)."""
         dev = _device()
-        ops.confusion(_to_u8_cuda(truth, dev, 'truth'), _to_u8_cuda(prediction, dev, 'prediction'), self.num_classes,
-                      ignore_index=ignore_value, cm=self._cm())
+        truth = _to_u8_cuda(truth, dev, 'truth')
+        prediction = _to_u8_cuda(prediction, dev, 'prediction')
+        if self.fill_holes:
+            # binary post-processing (the reference's scipy binary_fill_holes, evaluation.py:53-55) runs on the device, fused with
+            # the histogram: csrc/fillholes.hip. A 2-D pair is one image, an (N,H,W) pair N images filled independently.
+            ops.fill_holes(prediction, truth=truth, ignore_index=ignore_value, cm=self._cm())
+            return
+        ops.confusion(truth, prediction, self.num_classes, ignore_index=ignore_value, cm=self._cm())
 
     def sample_logits(self, logits, truth, out_size=None, ignore_value=255, align_corners=True):
         """Fused: logits (N,C,h,w) CUDA [low-res or full-res], truth (N,H,W)/(N,1,H,W) uint8/int64 CUDA."""
         if self.fill_holes:
             _, pred = ops.argmax_confusion(logits, None, self.num_classes, out_size or truth.shape[-2:],
                                            align_corners=align_corners, want_pred=True)
-            for i in range(pred.shape[0]):
-                t = truth[i, 0] if truth.dim() == 4 else truth[i]
-                self.sample(t, pred[i], ignore_value=ignore_value)
+            t = truth[:, 0] if truth.dim() == 4 else truth
+            # the whole batch in one call, filled in place (the argmax map is this function's own), histogram fused
+            ops.fill_holes(pred, out=pred, truth=_to_u8_cuda(t, pred.device, 'truth'), ignore_index=ignore_value,
+                           cm=self._cm())
             return
         ops.argmax_confusion(logits, truth, self.num_classes, out_size, ignore_index=ignore_value,
                              align_corners=align_corners, cm=self._cm())

@@ -851,6 +851,41 @@ def confusion(truth, pred, num_classes, ignore_index=None, cm=None):
     return cm
 
 
+def fill_holes(pred, out=None, truth=None, ignore_index=None, cm=None):
+    """
+    scipy.ndimage.binary_fill_holes(pred != 0) on the device, bit-identical (evaluation.py:53-55). pred uint8 CUDA (H,W) or
+    (N,H,W), each image filled on its own; `out` (same shape, {0,1}) may be `pred` itself. With `truth` (uint8, same shape)
+    the 2 x 2 confusion matrix of (truth, filled) is accumulated into `cm` in the same launches. Returns (out, cm|None).
+    """
+    _need_cuda(pred, out, truth, cm)
+    if pred.dtype != torch.uint8 or (truth is not None and truth.dtype != torch.uint8):
+        raise TypeError('fill_holes: uint8 maps required')
+    if pred.dim() not in (2, 3):
+        raise ValueError('fill_holes: pred must be (H,W) or (N,H,W)')
+    if cm is not None and truth is None:
+        raise ValueError('fill_holes: cm given without truth')
+    pred = pred.contiguous()
+    if out is None:
+        out = torch.empty_like(pred)
+    elif out.dtype != torch.uint8 or not out.is_contiguous():
+        raise TypeError('fill_holes: out must be a contiguous uint8 map')
+    if out.shape != pred.shape or (truth is not None and truth.shape != pred.shape):
+        raise ValueError('fill_holes: size mismatch')
+    n = int(pred.shape[0]) if pred.dim() == 3 else 1
+    h, w = int(pred.shape[-2]), int(pred.shape[-1])
+    if truth is not None:
+        truth = truth.contiguous()
+        if cm is None:
+            cm = torch.zeros((2, 2), dtype=torch.int64, device=pred.device)
+        elif cm.dtype != torch.int64 or tuple(cm.shape) != (2, 2) or not cm.is_contiguous():
+            raise TypeError('fill_holes: cm must be a contiguous int64 (2,2) matrix')
+    nbytes = int(fn['cms_fill_holes_workspace_bytes'](n, h, w))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=pred.device)
+    check(fn['cms_fill_holes'](_ptr(pred), _ptr(out), _ptr(truth), -1 if ignore_index is None else int(ignore_index),
+                               _ptr(cm), n, h, w, _ptr(ws), nbytes, _stream()), 'cms_fill_holes')
+    return out, cm
+
+
 # ---------------------------------------------------------------------------------------------- BatchNorm (batch stats)
 def _world(group):
     import torch.distributed as dist

@@ -243,6 +243,19 @@ int cms_argmax_confusion(const float* logits, const void* labels, int label_dtyp
 /* fast_cm / per_class_i_and_u_cm on integer maps (evaluation.py:6-37): truth, pred uint8 (count) */
 int cms_confusion(const uint8_t* truth, const uint8_t* pred, size_t count, int ignore_index, int c, int64_t* cm,
                   void* stream);
+/* Hole filling of binary predictions on the device (evaluation.py:53-55: scipy.ndimage.binary_fill_holes(pred != 0), default
+ * structure, bit-identical): pred (n,h,w) uint8, 0 = background, anything else foreground. A background pixel is kept iff it is
+ * 4-connected through background pixels to the outside of its image (every background pixel on the first / last row or column
+ * touches the outside); every other pixel comes out as 1. Each of the n images is filled on its own. Three stream-ordered
+ * launches (tile-local union-find, seams, resolve), no host synchronisation.
+ *   out    (n,h,w) uint8 in {0,1}; may alias pred; may be NULL when only cm is wanted
+ *   truth  (n,h,w) uint8 and cm int64 (2,2): both NULL or both given; cm[truth][filled] += counts over pixels with
+ *          truth != ignore_index (ignore_index < 0: none) and truth < 2, as cms_confusion would on the filled map
+ *   workspace: cms_fill_holes_workspace_bytes(n, h, w) bytes of device memory (one int32 per pixel plus one per image);
+ *          that function returns 0 for non-positive geometry or n * (h * w + 1) >= 2^31, which cms_fill_holes refuses */
+size_t cms_fill_holes_workspace_bytes(int n, int h, int w);
+int cms_fill_holes(const uint8_t* pred, uint8_t* out, const uint8_t* truth, int ignore_index, int64_t* cm, int n, int h, int w,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * MFMA implicit-GEMM convolution for the backbone   (nn.Conv2d + frozen nn.BatchNorm2d + ReLU (+ residual) of
