@@ -40,6 +40,13 @@ class ConsistencyDesc(C.Structure):
                 ('loss_fn', c_int), ('conf_thresh', c_float), ('conf_per_pixel', c_int)]
 
 
+class IctDesc(C.Structure):
+    _fields_ = [('l_stu', c_void_p), ('l_tea0', c_void_p), ('l_tea1', c_void_p), ('lam', c_void_p),
+                ('um0', c_void_p), ('um1', c_void_p),
+                ('n', c_int), ('c', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int),
+                ('align_corners', c_int), ('loss_fn', c_int), ('conf_thresh', c_float), ('conf_per_pixel', c_int)]
+
+
 class CeDesc(C.Structure):
     _fields_ = [('logits', c_void_p), ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int),
                 ('n', c_int), ('c', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int),
@@ -134,6 +141,10 @@ PROTOTYPES = {
     'cms_consistency_fused_supported': (c_int, [_P(ConsistencyDesc)]),
     'cms_consistency_fwd_bwd': (c_int, [_P(ConsistencyDesc), c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'cms_scale_by_scalar': (c_int, [c_void_p, C.c_longlong, c_void_p, c_int, c_float, c_void_p]),
+    'cms_ict_blend': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, C.c_longlong, c_void_p]),
+    'cms_ict_workspace_bytes': (c_size_t, [_P(IctDesc)]),
+    'cms_ict_fwd': (c_int, [_P(IctDesc), c_void_p, c_void_p, c_void_p]),
+    'cms_ict_bwd': (c_int, [_P(IctDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
     'cms_ce_workspace_bytes': (c_size_t, [_P(CeDesc)]),
     'cms_ce_fwd': (c_int, [_P(CeDesc), c_void_p, c_void_p, c_void_p]),
     'cms_ce_finalize': (c_int, [c_void_p, c_float, c_void_p, c_void_p]),

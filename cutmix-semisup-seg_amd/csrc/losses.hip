@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "common.hpp"
+#include "ict_math.hpp"
 
 namespace cms {
 
@@ -1239,4 +1240,341 @@ extern "C" int cms_ce_bwd(const cms_ce_desc* d, const float* scalars, float* gra
         });
     }
     return launch_status("cms_ce_bwd");
+}
+
+// ================================================================================================ ICT
+// Interpolation consistency training (train_seg_semisup_ict.py:306-391): the student sees a per-sample blend of two images,
+// the target is the same blend of the teacher's two predictions. Same kernel shapes as the CutMix consistency above (one
+// thread per output pixel, the low-resolution rectangles of the THREE logit tensors staged to LDS per tile, class axis in
+// registers, the tiled adjoint of the upsample for the backward); the per-pixel arithmetic is csrc/ict_math.hpp. Compulsory
+// traffic per launch: the two validity masks (2 * P * 4 B) and the three low-resolution logit tensors; nothing of size C * P.
+namespace cms {
+
+struct IctArgs {
+    cms_ict_desc d;
+    Geo g;
+    float tau, inv_root_c;
+    float* cmap;        // (H,W) sum_i [conf(i,y,x) >= tau] -- --conf_per_pixel with a threshold only, else NULL
+    int count_pass;     // forward kernels: 1 = write `cmap` (teachers only), 0 = the loss sums
+};
+
+__device__ __forceinline__ float ict_um(const IctArgs& a, size_t pix, float lam) {
+    // um0 * (1 - lam) + um1 * lam (:311); a missing mask is the all-ones mask the reference's loader would deliver
+    const float u0 = a.d.um0 ? a.d.um0[pix] : 1.0f, u1 = a.d.um1 ? a.d.um1[pix] : 1.0f;
+    return ict_mix(u0, u1, 1.0f - lam, lam);
+}
+
+// one pixel of a forward kernel from its three gathers: a vote into the confidence map (count pass) or the three loss sums
+template <int CT, bool IDENT>
+__device__ __forceinline__ void ict_fwd_pixel(const IctArgs& a, const Gather<IDENT>& gs, const Gather<IDENT>& g0,
+                                              const Gather<IDENT>& g1, int n, int y, int x, float lam, float (&acc)[3]) {
+    const Geo& g = a.g;
+    const size_t yx = (size_t)y * g.W + x;
+    if (a.count_pass) {
+        float conf;
+        if (CT > 0) {
+            RegVec<CT> r0, r1;
+            fill<CT, IDENT>(r0, g0);
+            fill<CT, IDENT>(r1, g1);
+            conf = ict_conf<CT>(r0, r1, lam, g.c);
+        } else {
+            conf = ict_conf<0>(g0, g1, lam, g.c);
+        }
+        // whole numbers <= N: the float sum is exact whatever order the samples' workgroups arrive in
+        if (conf >= a.tau) atomicAdd(a.cmap + yx, 1.0f);
+        return;
+    }
+    PixelFwd r;
+    if (CT > 0) {
+        RegVec<CT> rs, r0, r1;
+        fill<CT, IDENT>(rs, gs);
+        fill<CT, IDENT>(r0, g0);
+        fill<CT, IDENT>(r1, g1);
+        r = ict_pixel_fwd<CT>(rs, r0, r1, lam, g.c, a.d.loss_fn, a.inv_root_c);
+    } else {
+        r = ict_pixel_fwd<0>(gs, g0, g1, lam, g.c, a.d.loss_fn, a.inv_root_c);
+    }
+    const float lm = r.loss * ict_um(a, (size_t)n * g.H * g.W + yx, lam);
+    const float cf = (a.tau > 0.0f && r.conf >= a.tau) ? 1.0f : 0.0f;
+    // --conf_per_pixel: the batch mean of the indicator at this pixel position (the reference's broadcast, cutmixseg.h)
+    const float wgt = a.cmap ? a.cmap[yx] / (float)g.n : cf;
+    acc[0] += lm;
+    acc[1] += lm * wgt;
+    acc[2] += cf;
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void ict_fwd_tiled_kernel(IctArgs a, float* __restrict__ partials, int patch_stride) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const Geo& g = a.g;
+    const int tiles_x = (g.W + TILE_W - 1) / TILE_W, tiles_y = (g.H + FWD_TILE_H - 1) / FWD_TILE_H;
+    int b = blockIdx.x;
+    const int tx_i = b % tiles_x;
+    b /= tiles_x;
+    const int ty_i = b % tiles_y;
+    const int n = b / tiles_y;
+    const int x0 = tx_i * TILE_W, y0 = ty_i * FWD_TILE_H;
+    const int tw = min(TILE_W, g.W - x0), th = min(FWD_TILE_H, g.H - y0);
+    const Patch p = tile_patch(g, x0, y0, tw, th);
+    const size_t plane = (size_t)g.h * g.w;
+    float* Ps = smem;
+    float* P0 = smem + patch_stride;
+    float* P1 = smem + 2 * patch_stride;
+    const size_t sample = (size_t)n * g.c * plane;
+    if (!a.count_pass) stage_patch(Ps, a.d.l_stu + sample, g.c, plane, g.w, p);
+    stage_patch(P0, a.d.l_tea0 + sample, g.c, plane, g.w, p);
+    stage_patch(P1, a.d.l_tea1 + sample, g.c, plane, g.w, p);
+    __syncthreads();
+    const float lam = a.d.lam[n];
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    const int col = threadIdx.x & (TILE_W - 1);
+#pragma unroll 1
+    for (int rr = 0; rr < FWD_TILE_H / 4; ++rr) {
+        const int row = (threadIdx.x >> 6) + rr * 4;
+        if (col < tw && row < th) {
+            const int y = y0 + row, x = x0 + col;
+            Gather<false> gs, g0, g1;
+            gs.base = Ps;
+            g0.base = P0;
+            g1.base = P1;
+            gs.plane = g0.plane = g1.plane = (size_t)p.n_rows * p.n_cols;
+            gs.w_in = g0.w_in = g1.w_in = p.n_cols;
+            Tap ty = bilin_tap(y, g.sy, g.h, g.align != 0), tx = bilin_tap(x, g.sx, g.w, g.align != 0);
+            rebase(ty, tx, p);
+            gs.ty = g0.ty = g1.ty = ty;
+            gs.tx = g0.tx = g1.tx = tx;
+            ict_fwd_pixel<CT, false>(a, gs, g0, g1, n, y, x, lam, acc);
+        }
+    }
+    if (a.count_pass) return;           // (uniform over the launch)
+    __shared__ float red[3 * 16];
+    block_sum<3>(acc, red);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x * 3 + 0] = acc[0];
+        partials[blockIdx.x * 3 + 1] = acc[1];
+        partials[blockIdx.x * 3 + 2] = acc[2];
+    }
+}
+
+// direct gathers from global memory: identity geometry (the U-Nets), or rectangles beyond FWD_PATCH_LDS_MAX
+template <int CT, bool IDENT>
+__global__ __launch_bounds__(256) void ict_fwd_kernel(IctArgs a, float* __restrict__ partials) {
+    const Geo& g = a.g;
+    const size_t P = (size_t)g.n * g.H * g.W;
+    const size_t plane = (size_t)g.h * g.w;
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < P; idx += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(idx % g.W);
+        const size_t t = idx / g.W;
+        const int y = (int)(t % g.H);
+        const int n = (int)(t / g.H);
+        const size_t sample = (size_t)n * g.c * plane;
+        Gather<IDENT> gs, g0, g1;
+        gs.base = a.d.l_stu + sample;
+        g0.base = a.d.l_tea0 + sample;
+        g1.base = a.d.l_tea1 + sample;
+        gs.plane = g0.plane = g1.plane = plane;
+        gs.w_in = g0.w_in = g1.w_in = g.w;
+        if (IDENT) {
+            gs.off = g0.off = g1.off = (size_t)y * g.w + x;
+        } else {
+            gs.ty = g0.ty = g1.ty = bilin_tap(y, g.sy, g.h, g.align != 0);
+            gs.tx = g0.tx = g1.tx = bilin_tap(x, g.sx, g.w, g.align != 0);
+        }
+        ict_fwd_pixel<CT, IDENT>(a, gs, g0, g1, n, y, x, a.d.lam[n], acc);
+    }
+    if (a.count_pass) return;           // (uniform over the launch)
+    __shared__ float red[3 * 16];
+    block_sum<3>(acc, red);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x * 3 + 0] = acc[0];
+        partials[blockIdx.x * 3 + 1] = acc[1];
+        partials[blockIdx.x * 3 + 2] = acc[2];
+    }
+}
+
+// factor of a pixel's gradient vector: the finalised scale x the blended validity mask [x the batch-mean indicator]. The
+// confidence enters through scalars[2] (default mode: the rate) or the map (--conf_per_pixel); neither depends on the student.
+__device__ __forceinline__ float ict_bwd_factor(const IctArgs& a, float gscale, int n, int y, int x, float lam) {
+    const Geo& g = a.g;
+    const size_t yx = (size_t)y * g.W + x;
+    float f = gscale * ict_um(a, (size_t)n * g.H * g.W + yx, lam);
+    if (a.cmap) f *= a.cmap[yx] / (float)g.n;
+    return f;
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void ict_bwd_ident_kernel(IctArgs a, const float* __restrict__ scalars, float* __restrict__ grad) {
+    const Geo& g = a.g;
+    const size_t P = (size_t)g.n * g.H * g.W;
+    const size_t plane = (size_t)g.h * g.w;
+    const float gscale = scalars[2];
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < P; idx += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(idx % g.W);
+        const size_t t = idx / g.W;
+        const int y = (int)(t % g.H);
+        const int n = (int)(t / g.H);
+        const size_t sample = (size_t)n * g.c * plane;
+        const float lam = a.d.lam[n];
+        Gather<true> gs, g0, g1;
+        gs.base = a.d.l_stu + sample;
+        g0.base = a.d.l_tea0 + sample;
+        g1.base = a.d.l_tea1 + sample;
+        gs.plane = g0.plane = g1.plane = plane;
+        gs.w_in = g0.w_in = g1.w_in = g.w;
+        gs.off = g0.off = g1.off = (size_t)y * g.w + x;
+        float* gp = grad + sample + gs.off;
+        const float f = ict_bwd_factor(a, gscale, n, y, x, lam);
+        // (no early-out on f == 0, see cons_bwd_ident_kernel)
+        if (CT > 0) {
+            RegVec<CT> rs, r0, r1;
+            fill<CT, true>(rs, gs);
+            fill<CT, true>(r0, g0);
+            fill<CT, true>(r1, g1);
+            ict_pixel_bwd<CT>(rs, r0, r1, lam, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { gp[k * plane] += f * v; });
+        } else {
+            ict_pixel_bwd<0>(gs, g0, g1, lam, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { gp[k * plane] += f * v; });
+        }
+    }
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void ict_bwd_tiled_kernel(IctArgs a, const float* __restrict__ scalars, float* __restrict__ grad,
+                                                            int patch_stride) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const Geo& g = a.g;
+    const float gscale = scalars[2];
+    const size_t plane = (size_t)g.h * g.w;
+    // LDS copies of the tile's logit rectangles: student | teacher 0 | teacher 1, `pstride` floats apart
+    const int pstride = patch_stride;
+    auto stage = [&](int n, const Patch& p, float* P) {
+        const size_t sample = (size_t)n * g.c * plane;
+        stage_patch(P, a.d.l_stu + sample, g.c, plane, g.w, p);
+        stage_patch(P + pstride, a.d.l_tea0 + sample, g.c, plane, g.w, p);
+        stage_patch(P + 2 * pstride, a.d.l_tea1 + sample, g.c, plane, g.w, p);
+    };
+    auto pixel_grad = [&](int n, int y, int x, const Tap& ty, const Tap& tx, const Patch& p, const float* P, auto emit) -> bool {
+        const float lam = a.d.lam[n];
+        const float f = ict_bwd_factor(a, gscale, n, y, x, lam);
+        Gather<false> gs, g0, g1;
+        gs.base = P;
+        g0.base = P + pstride;
+        g1.base = P + 2 * pstride;
+        gs.plane = g0.plane = g1.plane = (size_t)p.n_rows * p.n_cols;
+        gs.w_in = g0.w_in = g1.w_in = p.n_cols;
+        gs.ty = g0.ty = g1.ty = ty;              // (taps already rebased to the rectangle)
+        gs.tx = g0.tx = g1.tx = tx;
+        if (CT > 0) {
+            RegVec<CT> rs, r0, r1;
+            fill<CT, false>(rs, gs);
+            fill<CT, false>(r0, g0);
+            fill<CT, false>(r1, g1);
+            ict_pixel_bwd<CT>(rs, r0, r1, lam, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { emit(k, f * v); });
+        } else {
+            ict_pixel_bwd<0>(gs, g0, g1, lam, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { emit(k, f * v); });
+        }
+        return true;
+    };
+    tiled_scatter(g, stage, pixel_grad, grad, smem);
+}
+
+// ---- host side
+static int check_ict(const cms_ict_desc* d) {
+    CMS_REQUIRE(d != nullptr, "ict: null descriptor");
+    CMS_REQUIRE(d->l_stu && d->l_tea0 && d->l_tea1, "ict: l_stu / l_tea0 / l_tea1 must not be NULL");
+    CMS_REQUIRE(d->lam, "ict: lam must not be NULL");
+    CMS_REQUIRE(d->n > 0 && d->c > 0 && d->h > 0 && d->w > 0 && d->H > 0 && d->W > 0, "ict: bad geometry");
+    CMS_REQUIRE(d->h <= d->H && d->w <= d->W, "ict: logits larger than the loss geometry");
+    CMS_REQUIRE(d->loss_fn >= CMS_LOSS_VAR && d->loss_fn <= CMS_LOSS_KLD, "Unknown consistency loss function %d", d->loss_fn);
+    return CMS_OK;
+}
+
+static bool ict_has_map(const cms_ict_desc* d) { return d->conf_thresh > 0.0f && d->conf_per_pixel != 0; }
+
+// workspace = [per-workgroup partial sums, padded to 256 B][the (H,W) confidence map, --conf_per_pixel only]
+static size_t ict_partials_bytes(const Geo& g) {
+    return (((size_t)fwd_blocks(g, 3) * 3 * sizeof(float)) + 255) / 256 * 256;
+}
+
+static IctArgs make_ict_args(const cms_ict_desc* d, const void* workspace) {
+    IctArgs a;
+    a.d = *d;
+    a.g = make_geo(d->n, d->c, d->h, d->w, d->H, d->W, d->align_corners);
+    a.tau = d->conf_thresh;
+    a.inv_root_c = (float)(1.0 / sqrt((double)d->c));
+    a.cmap = ict_has_map(d) ? (float*)((char*)workspace + ict_partials_bytes(a.g)) : nullptr;
+    a.count_pass = 0;
+    return a;
+}
+
+}  // namespace cms
+
+extern "C" size_t cms_ict_workspace_bytes(const cms_ict_desc* d) {
+    if (!d || d->n <= 0 || d->c <= 0 || d->h <= 0 || d->w <= 0 || d->H <= 0 || d->W <= 0) return 0;
+    const Geo g = make_geo(d->n, d->c, d->h, d->w, d->H, d->W, d->align_corners);
+    return ict_partials_bytes(g) + (ict_has_map(d) ? (size_t)d->H * d->W * sizeof(float) : 0);
+}
+
+extern "C" int cms_ict_fwd(const cms_ict_desc* d, void* workspace, double* stats_out, void* stream) {
+    int rc = check_ict(d);
+    if (rc) return rc;
+    CMS_REQUIRE(workspace && stats_out, "ict_fwd: workspace / stats_out NULL");
+    IctArgs a = make_ict_args(d, workspace);
+    const size_t P = (size_t)d->n * d->H * d->W;
+    hipStream_t s = (hipStream_t)stream;
+    const bool ident = d->h == d->H && d->w == d->W;
+    float* partials = (float*)workspace;
+    size_t lds = 0;
+    int pstride = 0;
+    const int tiles = fwd_tiles(a.g, 3, &lds, &pstride);
+    const int grid = tiles > 0 ? tiles : fwd_grid(P);
+    if (a.cmap) {
+        hipError_t e = hipMemsetAsync(a.cmap, 0, (size_t)d->H * d->W * sizeof(float), s);
+        CMS_REQUIRE(e == hipSuccess, "ict_fwd: clearing the confidence map: %s", hipGetErrorString(e));
+    }
+    // --conf_per_pixel: every sample's vote into the map first, then the loss sums weighted with it
+    for (int pass = a.cmap ? 1 : 0; pass >= 0; --pass) {
+        a.count_pass = pass;
+        CMS_DISPATCH_C(d->c, {
+            if (tiles > 0) {
+                if (lds > 48 * 1024)
+                    (void)hipFuncSetAttribute((const void*)ict_fwd_tiled_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL((ict_fwd_tiled_kernel<CT>), dim3(grid), dim3(256), lds, s, a, partials, pstride);
+            }
+            else if (ident) hipLaunchKernelGGL((ict_fwd_kernel<CT, true>), dim3(grid), dim3(256), 0, s, a, partials);
+            else hipLaunchKernelGGL((ict_fwd_kernel<CT, false>), dim3(grid), dim3(256), 0, s, a, partials);
+        });
+    }
+    hipLaunchKernelGGL((reduce_partials_kernel<3>), dim3(1), dim3(256), 0, s, partials, grid, stats_out, (double)P, 3);
+    return launch_status("cms_ict_fwd");
+}
+
+extern "C" int cms_ict_bwd(const cms_ict_desc* d, const void* workspace, const float* scalars, float* grad_l_stu, void* stream) {
+    int rc = check_ict(d);
+    if (rc) return rc;
+    CMS_REQUIRE(scalars && grad_l_stu, "ict_bwd: scalars / grad NULL");
+    CMS_REQUIRE(workspace || !ict_has_map(d), "ict_bwd: conf_per_pixel needs the workspace cms_ict_fwd filled");
+    IctArgs a = make_ict_args(d, workspace);
+    hipStream_t s = (hipStream_t)stream;
+    const bool ident = d->h == d->H && d->w == d->W;
+    if (ident) {
+        const int grid = fwd_grid((size_t)d->n * d->H * d->W);
+        CMS_DISPATCH_C(d->c, {
+            hipLaunchKernelGGL((ict_bwd_ident_kernel<CT>), dim3(grid), dim3(256), 0, s, a, scalars, grad_l_stu);
+        });
+    } else {
+        const size_t lds = tile_lds_bytes(d->c, a.g.sy, a.g.sx, 3);
+        const int pstride = (int)patch_floats(d->c, a.g.sy, a.g.sx, TILE_H);
+        CMS_REQUIRE(lds <= 160 * 1024 - 4096, "ict_bwd: %d classes at this scale need %zu B of LDS", d->c, lds);
+        CMS_DISPATCH_C(d->c, {
+            if (lds > 48 * 1024)
+                (void)hipFuncSetAttribute((const void*)ict_bwd_tiled_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            tiled_launches(a.g, [&](const Geo& gc, int tiles) {
+                IctArgs ac = a;
+                ac.g = gc;
+                hipLaunchKernelGGL((ict_bwd_tiled_kernel<CT>), dim3(tiles), dim3(256), lds, s, ac, scalars, grad_l_stu, pstride);
+            });
+        });
+    }
+    return launch_status("cms_ict_bwd");
 }

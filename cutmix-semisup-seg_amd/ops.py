@@ -271,6 +271,96 @@ def consistency_loss(l_stu, l_tea0, l_tea1, out_size, cfg, ranges=None, mask=Non
                                 cons_weight, group)
 
 
+# ---------------------------------------------------------------------------------------------- ICT
+def _lam_vector(lam, n):
+    """mix factors as a contiguous f32 (N,) tensor: the reference keeps them as (N,1,1,1), train_seg_semisup_ict.py:306-307"""
+    lam = _f32c(lam).reshape(-1)
+    if int(lam.numel()) != int(n):
+        raise ValueError('ict: {} mix factors for {} samples'.format(int(lam.numel()), int(n)))
+    return lam
+
+
+def ict_blend(x0, x1, lam, out=None):
+    """out = x0*(1-lam) + x1*lam with one factor per sample (train_seg_semisup_ict.py:310-311): fp32 or bf16 (N, ...) tensors,
+    arithmetic in fp32 with the reference's roundings. Images and validity masks."""
+    _need_cuda(x0, x1, lam, out)
+    if x0.shape != x1.shape or x0.dtype != x1.dtype:
+        raise ValueError('ict_blend: x0/x1 shape or dtype mismatch')
+    x0, x1 = x0.contiguous(), x1.contiguous()
+    n = int(x0.shape[0])
+    lam = _lam_vector(lam, n)
+    if out is None:
+        out = torch.empty_like(x0)
+    elif out.shape != x0.shape or out.dtype != x0.dtype or not out.is_contiguous():
+        raise ValueError('ict_blend: out must be a contiguous tensor of the inputs\' shape and dtype')
+    if x0.numel() == 0:
+        return out
+    check(fn['cms_ict_blend'](_ptr(x0), _ptr(x1), _ptr(out), _dtype_code(x0), _ptr(lam), n, int(x0.numel()) // n, _stream()),
+          'cms_ict_blend')
+    return out
+
+
+class ICTConsistencyConfig(object):
+    """Static configuration of the ICT loss (train_seg_semisup_ict.py CLI flags)."""
+
+    def __init__(self, loss_fn='var', conf_thresh=0.97, conf_per_pixel=False, align_corners=True):
+        if loss_fn not in _lib.LOSS_IDS:
+            raise ValueError('Unknown consistency loss function {}'.format(loss_fn))
+        self.loss_fn = loss_fn
+        self.conf_thresh = float(conf_thresh)
+        self.conf_per_pixel = bool(conf_per_pixel)
+        self.align_corners = bool(align_corners)
+
+
+def ict_consistency_forward(cfg, l_stu, l_tea0, l_tea1, lam, out_size, um0=None, um1=None, ramp_val=1.0, cons_weight=1.0):
+    """
+    Fused ICT loss, forward (train_seg_semisup_ict.py:320-390). Returns (scalars, ctx) as consistency_forward does: scalars = f32[4]
+    device tensor [consistency_loss, conf_rate, grad_scale, unsup_loss]; ctx feeds ict_consistency_backward. No host sync.
+    """
+    _need_cuda(l_stu, l_tea0, l_tea1, lam, um0, um1)
+    l_stu, l_tea0, l_tea1 = _f32c(l_stu), _f32c(l_tea0), _f32c(l_tea1)
+    um0, um1 = _f32c(um0), _f32c(um1)
+    if l_tea0.shape != l_stu.shape or l_tea1.shape != l_stu.shape:
+        raise ValueError('ict: student / teacher logits shapes differ')
+    n, c, h, w = (int(s) for s in l_stu.shape)
+    H, W = int(out_size[0]), int(out_size[1])
+    for um in (um0, um1):
+        if um is not None and int(um.numel()) != n * H * W:
+            raise ValueError('ict: validity masks must be (N,1,H,W) of the loss geometry')
+    lam = _lam_vector(lam, n)
+    d = _lib.IctDesc()
+    d.l_stu, d.l_tea0, d.l_tea1, d.lam = l_stu.data_ptr(), l_tea0.data_ptr(), l_tea1.data_ptr(), lam.data_ptr()
+    d.um0 = um0.data_ptr() if um0 is not None else None
+    d.um1 = um1.data_ptr() if um1 is not None else None
+    d.n, d.c, d.h, d.w, d.H, d.W = n, c, h, w, H, W
+    d.align_corners = int(cfg.align_corners)
+    d.loss_fn = _lib.LOSS_IDS[cfg.loss_fn]
+    d.conf_thresh = cfg.conf_thresh
+    d.conf_per_pixel = int(cfg.conf_per_pixel)
+    dev = l_stu.device
+    # the workspace goes into the context: the backward reads the confidence map of --conf_per_pixel from it
+    ws = torch.empty(max(int(fn['cms_ict_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    check(fn['cms_ict_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_ict_fwd')
+    scalars = torch.empty(4, dtype=torch.float32, device=dev)
+    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats), cfg.conf_thresh, int(cfg.conf_per_pixel),
+                                         float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
+          'cms_consistency_finalize')
+    keep = (l_stu, l_tea0, l_tea1, lam, um0, um1)
+    return scalars, (d, keep, ws, stats)
+
+
+def ict_consistency_backward(ctx, scalars, grad_out=None):
+    """fp32 gradient wrt the (low-res) student logits; `grad_out` f32 (N,C,h,w) is accumulated into when given."""
+    d, keep, ws, _ = ctx
+    if grad_out is None:
+        grad_out = torch.zeros_like(keep[0])
+    elif grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(keep[0].shape) or not grad_out.is_contiguous():
+        raise ValueError('ict_consistency_backward: grad_out must be a contiguous f32 tensor of the logits\' shape')
+    check(fn['cms_ict_bwd'](C.byref(d), _ptr(ws), _ptr(scalars), _ptr(grad_out), _stream()), 'cms_ict_bwd')
+    return grad_out
+
+
 # ---------------------------------------------------------------------------------------------- supervised CE
 def _ce_desc(logits, labels, ignore_index, out_size, align_corners):
     n, c, h, w = (int(s) for s in logits.shape)

@@ -162,6 +162,52 @@ int cms_ce_fwd_bwd(const cms_ce_desc* d, void* workspace, double* stats_out, flo
 int cms_loss_set_deterministic(int on);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * ICT (interpolation consistency training): per-sample blends and the fused interpolation loss
+ *                               (train_seg_semisup_ict.py:306-391)
+ * ------------------------------------------------------------------------------------------------------------ */
+
+/* out[i, :] = x0[i, :] * (1 - lam[i]) + x1[i, :] * lam[i] for n samples of `chw` elements each (:310-311). fp32 arithmetic in
+ * the reference's order (1 - lam in fp32, two rounded products, their sum; no FMA), one rounding to bf16 for CMS_BF16. `lam`:
+ * n device floats. Images (chw = C*H*W) and, with CMS_F32 and chw = H*W, validity masks. 16-byte accesses when the three
+ * pointers are 16-byte aligned, element-wise otherwise. */
+int cms_ict_blend(const void* x0, const void* x1, void* out, int dtype, const float* lam, int n, long long chw, void* stream);
+
+/* The loss: the teacher's two predictions are BLENDED per sample, probabilities p_t = softmax(L0)(1-lam) + softmax(L1) lam for
+ * var / bce / kld, logits l_t = L0 (1-lam) + L1 lam for logits_var / logits_smoothl1 (:328-329, 360-380); the confidence is
+ * max softmax(L0) (1-lam) + max softmax(L1) lam (:338-341); the loss mask is um0 (1-lam) + um1 lam (:311), blended in-kernel. */
+typedef struct cms_ict_desc {
+    const float* l_stu;    /* (N,C,h,w) student logits of the blended image                                  */
+    const float* l_tea0;   /* (N,C,h,w) teacher logits of image 0                                            */
+    const float* l_tea1;   /* (N,C,h,w) teacher logits of image 1                                            */
+    const float* lam;      /* (N) mix factors                                                                */
+    const float* um0;      /* (N,1,H,W) validity mask of image 0, NULL = all ones                            */
+    const float* um1;      /* (N,1,H,W) validity mask of image 1, NULL = all ones                            */
+    int n, c, h, w;        /* logits geometry                                                                */
+    int H, W;              /* loss geometry (crop size); logits are upsampled h x w -> H x W in-kernel       */
+    int align_corners;
+    int loss_fn;           /* CMS_LOSS_*                                                                     */
+    float conf_thresh;     /* <= 0 disables confidence thresholding (:334)                                   */
+    int conf_per_pixel;    /* --conf_per_pixel (:347), with the reference's broadcast: see below             */
+} cms_ict_desc;
+
+/* bytes of scratch for cms_ict_fwd / cms_ict_bwd: per-workgroup partial sums and, with conf_per_pixel and a threshold, the
+ * (H,W) map of sum_i [conf(i,y,x) >= thresh] */
+size_t cms_ict_workspace_bytes(const cms_ict_desc* d);
+
+/* stats_out: double[4] = { sum(loss*um), sum(loss*um*cbar), count(conf >= thresh), P = N*H*W } (device), the contract of
+ * cms_consistency_fwd, so cms_consistency_finalize turns it into the loss, the rate and the gradient scale unchanged.
+ * --conf_per_pixel: the reference's mask comes out as (N,1,1,H,W) against a (N,1,H,W) loss (:343 indexes a keepdim tensor), and
+ * the mean over the (N,N,1,H,W) product weights pixel (y,x) of EVERY sample with cbar[y,x] = (1/N) sum_i [conf(i,y,x) >=
+ * thresh], the batch mean of the indicator: a first launch writes the map of that sum into `workspace`, the loss launch and
+ * cms_ict_bwd read it. The workspace is the caller's and must stay intact between cms_ict_fwd and cms_ict_bwd. Without
+ * conf_per_pixel no map is written and stats_out[1] holds sum(loss*um*[own conf >= thresh]), which nothing reads. */
+int cms_ict_fwd(const cms_ict_desc* d, void* workspace, double* stats_out, void* stream);
+
+/* grad_l_stu f32 (N,C,h,w) += d unsup_loss / d l_stu; reads scalars[2] (cms_consistency_finalize) and, with conf_per_pixel,
+ * the map cms_ict_fwd left in `workspace`. cms_loss_set_deterministic applies. */
+int cms_ict_bwd(const cms_ict_desc* d, const void* workspace, const float* scalars, float* grad_l_stu, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Bilinear upsample (F.interpolate(mode='bilinear'), architectures/deeplab2.py:204, deeplab3plus.py:54-55,77)
  * Stand-alone form for the `forward(x) -> (N,C,H,W)` contract of the reference models.
  * ------------------------------------------------------------------------------------------------------------ */
