@@ -47,6 +47,13 @@ class IctDesc(C.Structure):
                 ('align_corners', c_int), ('loss_fn', c_int), ('conf_thresh', c_float), ('conf_per_pixel', c_int)]
 
 
+class AugDesc(C.Structure):
+    _fields_ = [('l_stu', c_void_p), ('l_tea', c_void_p), ('xf', c_void_p), ('um0', c_void_p), ('um1', c_void_p),
+                ('n', c_int), ('c', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int),
+                ('align_corners', c_int), ('loss_fn', c_int), ('conf_thresh', c_float), ('conf_per_pixel', c_int),
+                ('force_global', c_int)]
+
+
 class CeDesc(C.Structure):
     _fields_ = [('logits', c_void_p), ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int),
                 ('n', c_int), ('c', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int),
@@ -145,6 +152,9 @@ PROTOTYPES = {
     'cms_ict_workspace_bytes': (c_size_t, [_P(IctDesc)]),
     'cms_ict_fwd': (c_int, [_P(IctDesc), c_void_p, c_void_p, c_void_p]),
     'cms_ict_bwd': (c_int, [_P(IctDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    'cms_aug_workspace_bytes': (c_size_t, [_P(AugDesc)]),
+    'cms_aug_fwd': (c_int, [_P(AugDesc), c_void_p, c_void_p, c_void_p]),
+    'cms_aug_bwd': (c_int, [_P(AugDesc), c_void_p, c_void_p, c_void_p]),
     'cms_ce_workspace_bytes': (c_size_t, [_P(CeDesc)]),
     'cms_ce_fwd': (c_int, [_P(CeDesc), c_void_p, c_void_p, c_void_p]),
     'cms_ce_finalize': (c_int, [c_void_p, c_float, c_void_p, c_void_p]),

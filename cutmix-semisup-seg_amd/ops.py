@@ -361,6 +361,102 @@ def ict_consistency_backward(ctx, scalars, grad_out=None):
     return grad_out
 
 
+# ---------------------------------------------------------------------------------------------- augmentation consistency
+def aug_pixel_matrices(xf0_to_1, out_size, device=None):
+    """
+    The reference's `xf0_to_1` (N,2,3) -- the theta of F.affine_grid(..., align_corners=True), train_seg_semisup_aug_mt.py:302 --
+    folded with the un-normalisation of F.grid_sample(align_corners=True) into pixel-space matrices: f32 (N,6) rows
+    [a00 a01 a02 a10 a11 a12], a student pixel (x, y) samples the teacher's map at (a00 x + a01 y + a02, a10 x + a11 y + a12).
+    The fold is done in float64 and rounded once. numpy / CPU tensors are folded on the host (and copied to `device` through
+    pinned memory when one is given), device tensors on the device; no host synchronisation either way.
+    """
+    H, W = int(out_size[0]), int(out_size[1])
+    if H < 2 or W < 2:
+        raise ValueError('aug: the align_corners=True grid needs H >= 2 and W >= 2 (got {} x {})'.format(H, W))
+    t = torch.as_tensor(xf0_to_1)
+    if t.dim() != 3 or tuple(t.shape[1:]) != (2, 3):
+        raise ValueError('aug: xf0_to_1 must be (N,2,3), got {}'.format(tuple(t.shape)))
+    t = t.to(torch.float64)
+    rx, ry = (W - 1) / 2.0, (H - 1) / 2.0
+    a = torch.stack([t[:, 0, 0], t[:, 0, 1] * (rx / ry), (t[:, 0, 2] - t[:, 0, 0] - t[:, 0, 1] + 1.0) * rx,
+                     t[:, 1, 0] * (ry / rx), t[:, 1, 1], (t[:, 1, 2] - t[:, 1, 0] - t[:, 1, 1] + 1.0) * ry], dim=1)
+    a = a.to(torch.float32).contiguous()
+    if device is not None and not a.is_cuda and torch.device(device).type == 'cuda':
+        a = a.pin_memory().to(device, non_blocking=True)          # (pinned: see ranges_to_device)
+    return a
+
+
+class AugConsistencyConfig(object):
+    """Static configuration of the augmentation-consistency loss (train_seg_semisup_aug_mt.py CLI flags). `force_global`: never
+    stage the teacher's rectangle in LDS (tests: both routes give the same bits)."""
+
+    def __init__(self, loss_fn='var', conf_thresh=0.97, conf_per_pixel=False, align_corners=True, force_global=False):
+        if loss_fn not in _lib.LOSS_IDS:
+            raise ValueError('Unknown consistency loss function {}'.format(loss_fn))
+        self.loss_fn = loss_fn
+        self.conf_thresh = float(conf_thresh)
+        self.conf_per_pixel = bool(conf_per_pixel)
+        self.align_corners = bool(align_corners)
+        self.force_global = bool(force_global)
+
+
+def aug_consistency_forward(cfg, l_stu, l_tea, xf0_to_1, out_size, um0=None, um1=None, ramp_val=1.0, cons_weight=1.0):
+    """
+    Fused affine-warp consistency loss, forward (train_seg_semisup_aug_mt.py:302-397): the teacher's prediction of view 0
+    (`l_tea`, low-resolution logits) warped into the student's view 1 (`l_stu`) by `xf0_to_1` (N,2,3; numpy, CPU or device
+    tensor). Returns (scalars, ctx) as consistency_forward does: scalars = f32[4] device tensor [consistency_loss, conf_rate,
+    grad_scale, unsup_loss]; ctx feeds aug_consistency_backward. No host sync.
+    """
+    if not (torch.is_tensor(l_stu) and torch.is_tensor(l_tea) and l_stu.is_cuda and l_tea.is_cuda):
+        raise ValueError('aug: the logits must be GPU tensors; there is no CPU fallback')
+    _need_cuda(um0, um1)
+    l_stu, l_tea = _f32c(l_stu), _f32c(l_tea)
+    um0, um1 = _f32c(um0), _f32c(um1)
+    if l_stu.dim() != 4 or l_tea.shape != l_stu.shape:
+        raise ValueError('aug: student / teacher logits must be (N,C,h,w) of the same shape')
+    n, c, h, w = (int(s) for s in l_stu.shape)
+    H, W = int(out_size[0]), int(out_size[1])
+    if h > H or w > W:
+        raise ValueError('aug: logits larger than the loss geometry')
+    for um in (um0, um1):
+        if um is not None and (int(um.numel()) != n * H * W or int(um.shape[0]) != n):
+            raise ValueError('aug: validity masks must be (N,1,H,W) of the loss geometry')
+    xf = aug_pixel_matrices(xf0_to_1, (H, W), l_stu.device)
+    if int(xf.shape[0]) != n:
+        raise ValueError('aug: {} warp matrices for {} samples'.format(int(xf.shape[0]), n))
+    d = _lib.AugDesc()
+    d.l_stu, d.l_tea, d.xf = l_stu.data_ptr(), l_tea.data_ptr(), xf.data_ptr()
+    d.um0 = um0.data_ptr() if um0 is not None else None
+    d.um1 = um1.data_ptr() if um1 is not None else None
+    d.n, d.c, d.h, d.w, d.H, d.W = n, c, h, w, H, W
+    d.align_corners = int(cfg.align_corners)
+    d.loss_fn = _lib.LOSS_IDS[cfg.loss_fn]
+    d.conf_thresh = cfg.conf_thresh
+    d.conf_per_pixel = int(cfg.conf_per_pixel)
+    d.force_global = int(cfg.force_global)
+    dev = l_stu.device
+    ws = torch.empty(max(int(fn['cms_aug_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    check(fn['cms_aug_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_aug_fwd')
+    scalars = torch.empty(4, dtype=torch.float32, device=dev)
+    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats), cfg.conf_thresh, int(cfg.conf_per_pixel),
+                                         float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
+          'cms_consistency_finalize')
+    keep = (l_stu, l_tea, xf, um0, um1)
+    return scalars, (d, keep, ws, stats)
+
+
+def aug_consistency_backward(ctx, scalars, grad_out=None):
+    """fp32 gradient wrt the (low-res) student logits; `grad_out` f32 (N,C,h,w) is accumulated into when given."""
+    d, keep, _, _ = ctx
+    if grad_out is None:
+        grad_out = torch.zeros_like(keep[0])
+    elif grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(keep[0].shape) or not grad_out.is_contiguous():
+        raise ValueError('aug_consistency_backward: grad_out must be a contiguous f32 tensor of the logits\' shape')
+    check(fn['cms_aug_bwd'](C.byref(d), _ptr(scalars), _ptr(grad_out), _stream()), 'cms_aug_bwd')
+    return grad_out
+
+
 # ---------------------------------------------------------------------------------------------- supervised CE
 def _ce_desc(logits, labels, ignore_index, out_size, align_corners):
     n, c, h, w = (int(s) for s in logits.shape)

@@ -208,6 +208,46 @@ int cms_ict_fwd(const cms_ict_desc* d, void* workspace, double* stats_out, void*
 int cms_ict_bwd(const cms_ict_desc* d, const void* workspace, const float* scalars, float* grad_l_stu, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Augmentation consistency (the classic mean teacher between two augmented views): the fused affine-warp loss
+ *                               (train_seg_semisup_aug_mt.py:302-390)
+ * ------------------------------------------------------------------------------------------------------------ */
+
+/* The teacher's prediction of view 0 is warped into the student's view 1 per pixel: a student pixel (x, y) samples the teacher's
+ * full-resolution map at ix = a00 x + a01 y + a02, iy = a10 x + a11 y + a12 with the four taps and the zero padding of
+ * F.grid_sample(bilinear). `xf` holds these PIXEL-space matrices, one per sample: F.affine_grid(theta, align_corners=True)
+ * followed by grid_sample's un-normalisation, folded:  a00 = t00, a01 = t01 (W-1)/(H-1), a02 = (t02 - t00 - t01 + 1)(W-1)/2,
+ * a10 = t10 (H-1)/(W-1), a11 = t11, a12 = (t12 - t10 - t11 + 1)(H-1)/2. Only that grid convention is supported (the reference
+ * passes no other). The target is sum_k w_k softmax(L_k) for var / bce / kld and sum_k w_k L_k for logits_var /
+ * logits_smoothl1, L_k = the teacher's logits at tap k (the bilinear upsample of l_tea, as the network's own); the confidence
+ * is the max of the warped probabilities (:347); the loss mask is grid_sample(um0) * um1 (:306). No full-resolution map is
+ * written. logits_var: sum_c (delta logits)^2 / sqrt(C) -- the reference's branch raises, this is its evident intent. */
+typedef struct cms_aug_desc {
+    const float* l_stu;    /* (N,C,h,w) student logits of view 1                                              */
+    const float* l_tea;    /* (N,C,h,w) teacher logits of view 0                                              */
+    const float* xf;       /* (N,6) pixel-space warp matrices, view-1 pixel -> view-0 position (device)       */
+    const float* um0;      /* (N,1,H,W) validity mask of view 0, NULL = all ones (still zero-padded)          */
+    const float* um1;      /* (N,1,H,W) validity mask of view 1, NULL = all ones                              */
+    int n, c, h, w;        /* logits geometry                                                                 */
+    int H, W;              /* loss geometry (crop size), H >= 2 and W >= 2                                    */
+    int align_corners;     /* of the networks' upsample h x w -> H x W                                        */
+    int loss_fn;           /* CMS_LOSS_*                                                                      */
+    float conf_thresh;     /* <= 0 disables confidence thresholding (:345)                                    */
+    int conf_per_pixel;    /* --conf_per_pixel (:353): (N,1,H,W) against (N,1,H,W), the pixel's own indicator */
+    int force_global;      /* != 0: never stage the teacher's rectangle in LDS (same results bit for bit)     */
+} cms_aug_desc;
+
+/* bytes of scratch for cms_aug_fwd: per-workgroup partial sums */
+size_t cms_aug_workspace_bytes(const cms_aug_desc* d);
+
+/* stats_out: double[4] = { sum(loss*mask), sum(loss*mask*[conf >= thresh]), count(conf >= thresh), P = N*H*W } (device), the
+ * contract of cms_consistency_fwd: cms_consistency_finalize turns it into the loss, the rate and the gradient scale unchanged. */
+int cms_aug_fwd(const cms_aug_desc* d, void* workspace, double* stats_out, void* stream);
+
+/* grad_l_stu f32 (N,C,h,w) += d unsup_loss / d l_stu; reads scalars[2] (cms_consistency_finalize). The teacher carries no
+ * gradient. cms_loss_set_deterministic applies. */
+int cms_aug_bwd(const cms_aug_desc* d, const float* scalars, float* grad_l_stu, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Bilinear upsample (F.interpolate(mode='bilinear'), architectures/deeplab2.py:204, deeplab3plus.py:54-55,77)
  * Stand-alone form for the `forward(x) -> (N,C,H,W)` contract of the reference models.
  * ------------------------------------------------------------------------------------------------------------ */

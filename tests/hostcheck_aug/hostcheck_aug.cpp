@@ -1,0 +1,188 @@
+// TEST INFRASTRUCTURE (never shipped, never imported by the product package).
+//
+// Drives the `__host__ __device__` per-pixel arithmetic of cutmix-semisup-seg_amd/csrc/aug_math.hpp -- the code the
+// augmentation-consistency kernels inline -- in plain host loops over every pixel, with the upsampling done by bilin_tap /
+// bilin_gather, so that the formulas (the warp, the four zero-padded taps, the warped targets, confidence and mask, the five
+// losses and their analytic gradients) can be checked against tests/_aug_refs.py on a CPU-only machine. The kernels' indexing,
+// reductions, LDS tiling and the staged / global routes are covered by the `-m gpu` tests.
+//
+// Build: see the Makefile (shared object for the test; `make asan` runs a stand-alone driver under ASan + UBSan).
+#include <stdint.h>
+#include <stddef.h>
+#include <vector>
+#include "../../cutmix-semisup-seg_amd/csrc/aug_math.hpp"
+
+using namespace cms;
+
+namespace {
+
+struct HostGather {
+    const float* base;
+    size_t plane;
+    int w_in;
+    Tap ty, tx;
+    float operator()(int c) const { return bilin_gather(base + c * plane, w_in, ty, tx); }
+};
+
+// the teacher's upsampled logits at tap k of a student pixel
+struct HostTea {
+    const float* base;
+    size_t plane;
+    int h, w;
+    float sy, sx;
+    bool align;
+    int X0, Y0;
+    HostGather operator()(int k) const {
+        HostGather g;
+        g.base = base;
+        g.plane = plane;
+        g.w_in = w;
+        g.ty = bilin_tap(Y0 + (k >> 1), sy, h, align);
+        g.tx = bilin_tap(X0 + (k & 1), sx, w, align);
+        return g;
+    }
+};
+
+struct Problem {
+    const float *l_stu, *l_tea, *xf, *um0, *um1;
+    int n, c, h, w, H, W, align, loss_fn;
+    float tau;
+    int per_pixel;
+};
+
+// CT > 0: the class axis in a register-like array, as the kernels' compile-time instantiations; CT == 0: re-gathering callables
+template <int CT>
+void run(const Problem& q, double* stats, float gscale, float* grad) {
+    const float sy = bilin_scale(q.h, q.H, q.align != 0), sx = bilin_scale(q.w, q.W, q.align != 0);
+    const size_t plane = (size_t)q.h * q.w;
+    const float inv_root_c = (float)(1.0 / sqrt((double)q.c));
+    const bool thresh = q.tau > 0.0f, pp = thresh && q.per_pixel;
+    stats[0] = stats[1] = stats[2] = 0.0;
+    std::vector<float> gv(q.c);
+    for (int i = 0; i < q.n; ++i) {
+        const float* xf = q.xf + (size_t)i * 6;
+        for (int y = 0; y < q.H; ++y)
+            for (int x = 0; x < q.W; ++x) {
+                const size_t img = (size_t)i * q.H * q.W, pix = img + (size_t)y * q.W + x;
+                HostGather gs;
+                gs.base = q.l_stu + (size_t)i * q.c * plane;
+                gs.plane = plane;
+                gs.w_in = q.w;
+                gs.ty = bilin_tap(y, sy, q.h, q.align != 0);
+                gs.tx = bilin_tap(x, sx, q.w, q.align != 0);
+                const AugTaps taps = aug_taps(xf, x, y, q.H, q.W);
+                HostTea tea = {q.l_tea + (size_t)i * q.c * plane, plane, q.h, q.w, sy, sx, q.align != 0, taps.X0, taps.Y0};
+                const PixelFwd r = aug_pixel_fwd<CT>(gs, taps, tea, q.c, q.loss_fn, inv_root_c, thresh);
+                const float m = aug_warp_mask(taps, q.um0 ? q.um0 + img : nullptr, q.W) * (q.um1 ? q.um1[pix] : 1.0f);
+                const float cf = (thresh && r.conf >= q.tau) ? 1.0f : 0.0f;
+                const float lm = r.loss * m;
+                stats[0] += (double)lm;
+                stats[1] += (double)(lm * cf);
+                stats[2] += cf;
+                if (grad) {
+                    const float base_f = gscale * m;
+                    aug_pixel_bwd<CT>(gs, taps, tea, q.c, q.loss_fn, inv_root_c, thresh,
+                                      [&](float conf) { return (pp && !(conf >= q.tau)) ? 0.0f : base_f; },
+                                      [&](int k, float v) { gv[k] = v; });
+                    float* gp = grad + (size_t)i * q.c * plane;
+                    for (int k = 0; k < q.c; ++k) {
+                        const float g = gv[k];
+                        gp[k * plane + (size_t)gs.ty.i0 * q.w + gs.tx.i0] += gs.ty.w0 * gs.tx.w0 * g;
+                        gp[k * plane + (size_t)gs.ty.i0 * q.w + gs.tx.i1] += gs.ty.w0 * gs.tx.w1 * g;
+                        gp[k * plane + (size_t)gs.ty.i1 * q.w + gs.tx.i0] += gs.ty.w1 * gs.tx.w0 * g;
+                        gp[k * plane + (size_t)gs.ty.i1 * q.w + gs.tx.i1] += gs.ty.w1 * gs.tx.w1 * g;
+                    }
+                }
+            }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// stats[3] = {sum loss*mask, sum loss*mask*[conf >= tau], count(conf >= tau)}; if grad != NULL also accumulates
+// gscale * mask [* the pixel's indicator, per_pixel] * d loss / d l_stu. xf: (n,6) pixel-space matrices.
+void hc_aug(const float* l_stu, const float* l_tea, const float* xf, const float* um0, const float* um1, int n, int c, int h, int w,
+            int H, int W, int align, int loss_fn, float tau, int per_pixel, double* stats, float gscale, float* grad) {
+    Problem q = {l_stu, l_tea, xf, um0, um1, n, c, h, w, H, W, align, loss_fn, tau, per_pixel};
+    switch (c) {
+        case 2: run<2>(q, stats, gscale, grad); break;
+        case 5: run<5>(q, stats, gscale, grad); break;
+        default: run<0>(q, stats, gscale, grad); break;
+    }
+}
+
+// sampling position and taps of every pixel of one sample: out[(y*W + x)*8 ..] = {X0, Y0, w0..w3, ix, iy} (ix, iy unclamped)
+void hc_aug_taps(const float* xf, int H, int W, float* out) {
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const AugTaps t = aug_taps(xf, x, y, H, W);
+            float* o = out + ((size_t)y * W + x) * 8;
+            o[0] = (float)t.X0; o[1] = (float)t.Y0;
+            for (int k = 0; k < 4; ++k) o[2 + k] = t.w[k];
+            aug_map(xf, x, y, o[6], o[7]);
+        }
+}
+
+// the rectangle of teacher pixels a tile samples (aug_tile_box): out = {x_lo, x_hi, y_lo, y_hi}
+void hc_aug_tile_box(const float* xf, int x0, int y0, int tw, int th, int H, int W, int* out) {
+    const AugBox b = aug_tile_box(xf, x0, y0, tw, th, H, W);
+    out[0] = b.x_lo; out[1] = b.x_hi; out[2] = b.y_lo; out[3] = b.y_hi;
+}
+
+}  // extern "C"
+
+#ifdef HC_AUG_MAIN
+// Stand-alone driver for the sanitizers: every loss x mode x class path on a small upsampling geometry with a mild warp, a
+// strong one, one wholly outside, and matrices of +-1e30 / NaN; fails on a non-finite sum or a contribution from outside.
+#include <stdio.h>
+int main() {
+    const int n = 6, h = 6, w = 7, H = 41, W = 50;
+    const float big = 1e30f, qnan = NAN;
+    const float xf[n * 6] = {0.97f, -0.12f, 3.5f,  0.12f, 0.97f, -2.25f,        // mild rotation + translation
+                             0.6f,  0.9f,   -8.0f, -0.9f, 0.6f,  30.0f,         // strong rotation + scale, partly outside
+                             1.0f,  0.0f,   500.0f, 0.0f, 1.0f,  -500.0f,       // wholly outside
+                             big,   big,    big,   -big,  -big,  -big,
+                             qnan,  qnan,   qnan,  qnan,  qnan,  qnan,
+                             1.0f,  0.0f,   0.0f,  0.0f,  1.0f,  0.0f};         // identity
+    uint32_t seed = 12345u;
+    auto rnd = [&]() {
+        seed = seed * 1664525u + 1013904223u;
+        return (float)(seed >> 8) / 16777216.0f * 2.0f - 1.0f;
+    };
+    int bad = 0;
+    for (int c : {2, 5, 7}) {
+        std::vector<float> ls((size_t)n * c * h * w), lt(ls.size()), um0((size_t)n * H * W), um1(um0.size());
+        for (auto& v : ls) v = 2.0f * rnd();
+        for (auto& v : lt) v = 3.0f * rnd();
+        for (auto& v : um0) v = rnd() > -0.4f ? 1.0f : 0.0f;
+        for (auto& v : um1) v = rnd() > -0.4f ? 1.0f : 0.0f;
+        for (int fn = 0; fn < 5; ++fn)
+            for (int mode = 0; mode < 3; ++mode)
+                for (int align = 0; align < 2; ++align) {
+                    std::vector<float> grad(ls.size(), 0.0f);
+                    double stats[3];
+                    hc_aug(ls.data(), lt.data(), xf, mode == 2 ? nullptr : um0.data(), mode == 2 ? nullptr : um1.data(), n, c, h, w, H,
+                           W, align, fn, mode == 2 ? 0.0f : 0.6f, mode == 1, stats, 1.0f / (n * H * W), grad.data());
+                    double gs = 0.0;
+                    for (float v : grad) gs += v;
+                    if (!(stats[0] == stats[0]) || !(gs == gs)) ++bad;
+                    // samples 2..4 see nothing of the teacher's view: no gradient may reach them
+                    for (size_t e = (size_t)2 * c * h * w; e < (size_t)5 * c * h * w; ++e)
+                        if (grad[e] != 0.0f) { ++bad; break; }
+                }
+    }
+    for (int i = 2; i < 5; ++i) {
+        std::vector<float> t((size_t)H * W * 8);
+        hc_aug_taps(xf + i * 6, H, W, t.data());
+        for (size_t p = 0; p < (size_t)H * W; ++p)
+            for (int k = 0; k < 4; ++k)
+                if (t[p * 8 + 2 + k] != 0.0f) ++bad;
+        int box[4];
+        hc_aug_tile_box(xf + i * 6, 0, 0, 50, 4, H, W, box);
+    }
+    printf("hostcheck_aug: %s\n", bad ? "BAD RESULT" : "ok");
+    return bad ? 1 : 0;
+}
+#endif
