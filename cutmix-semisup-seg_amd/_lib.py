@@ -111,6 +111,17 @@ class AugmentDesc(C.Structure):
                 ('n', c_int), ('hs', c_int), ('ws', c_int), ('h', c_int), ('w', c_int), ('out_dtype', c_int)]
 
 
+class StageEntry(C.Structure):
+    _fields_ = [('img_off', C.c_longlong), ('lab_off', C.c_longlong), ('hs', c_int), ('ws', c_int)]
+
+
+class StageDesc(C.Structure):
+    _fields_ = [('pool_img', c_void_p), ('pool_labels', c_void_p), ('entries', c_void_p), ('index', c_void_p),
+                ('out0', c_void_p), ('out1', c_void_p), ('out_labels', c_void_p), ('out_mask', c_void_p), ('params', c_void_p),
+                ('mean', c_float * 3), ('std_', c_float * 3),
+                ('n', c_int), ('n_entries', c_int), ('h', c_int), ('w', c_int), ('out_dtype', c_int)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('scale', c_void_p),
                 ('ntaps', c_int), ('cout', c_int), ('cin', c_int), ('first_block', c_int)]
@@ -196,6 +207,8 @@ PROTOTYPES = {
     'cms_conv_pack_transpose_batch64': (c_int, [c_void_p, c_int, c_int, c_void_p]),
     'cms_augment_batch': (c_int, [_P(AugmentDesc), c_void_p]),
     'cms_augment_luma': (c_int, [_P(AugmentDesc), c_void_p, c_void_p]),
+    'cms_stage_batch': (c_int, [_P(StageDesc), c_void_p]),
+    'cms_stage_luma': (c_int, [_P(StageDesc), c_void_p, c_void_p]),
     'cms_bn_workspace_bytes': (c_size_t, [c_size_t, c_int, c_int]),
     'cms_bn_run': (c_int, [_P(BnOp), c_void_p]),
     'cms_channel_copy': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_size_t, c_void_p]),

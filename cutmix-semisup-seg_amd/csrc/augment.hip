@@ -13,6 +13,7 @@
 // paired). Random parameters are drawn on the host in the reference's order (device_pipeline.py) and arrive as a small
 // table; nothing else crosses PCIe.
 #include "common.hpp"
+#include "stage_math.hpp"
 
 namespace cms {
 
@@ -28,126 +29,6 @@ struct AugArgs {
     int N, Hs, Ws, H, W;
 };
 
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
-
-__device__ __forceinline__ float gray_of(float r, float g, float b) { return 0.299f * r + 0.587f * g + 0.114f * b; }
-
-__device__ __forceinline__ void hue_shift(float& r, float& g, float& b, float dh) {
-    const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
-    const float d = mx - mn;
-    float h = 0.0f;
-    if (d > 0.0f) {
-        if (mx == r) h = (g - b) / d;
-        else if (mx == g) h = 2.0f + (b - r) / d;
-        else h = 4.0f + (r - g) / d;
-        h *= (1.0f / 6.0f);
-        if (h < 0.0f) h += 1.0f;
-    }
-    const float s = mx > 0.0f ? d / mx : 0.0f, v = mx;
-    h += dh;
-    h -= floorf(h);
-    const float hf = h * 6.0f;
-    const int i = (int)hf % 6;
-    const float f = hf - floorf(hf);
-    const float p = v * (1.0f - s), q = v * (1.0f - s * f), t = v * (1.0f - s * (1.0f - f));
-    switch (i) {
-    case 0: r = v; g = t; b = p; break;
-    case 1: r = q; g = v; b = p; break;
-    case 2: r = p; g = v; b = t; break;
-    case 3: r = p; g = q; b = v; break;
-    case 4: r = t; g = p; b = v; break;
-    default: r = v; g = p; b = q; break;
-    }
-}
-
-template <class T>
-__device__ __forceinline__ void put(void* base, size_t idx, float v) {
-    if constexpr (sizeof(T) == 4) reinterpret_cast<float*>(base)[idx] = v;
-    else reinterpret_cast<uint16_t*>(base)[idx] = f32_to_bf16(v);
-}
-
-// cv2.BORDER_REFLECT_101: ... 2 1 | 0 1 2 ... n-1 | n-2 n-3 ... (period 2n - 2), any distance outside
-__device__ __forceinline__ int reflect101(int i, int n) {
-    if (n == 1) return 0;
-    const int period = 2 * n - 2;
-    i %= period;
-    if (i < 0) i += period;
-    return i < n ? i : period - i;
-}
-
-// AFFINE WARP geometry (params slot 15 == 1): source position of (flip-undone) output pixel (cx, cy)
-__device__ __forceinline__ void warp_src(const float* p, int cx, int cy, float& sx, float& sy) {
-    sx = fmaf(p[16], (float)cx, fmaf(p[17], (float)cy, p[18]));
-    sy = fmaf(p[19], (float)cx, fmaf(p[20], (float)cy, p[21]));
-}
-
-// The geometric half of the transform for ONE (flip-undone) output pixel (cx, cy) of sample `img`: interpolated source colour
-// (0..255), validity weight `alpha`, `img_alpha` = factor of the mean in the standardisation (window mode: zero padding),
-// (ny, nx) = nearest source pixel for the labels. Shared by the image kernel and the luminance pre-pass, so that the contrast
-// pivot is the mean of exactly the pixels the image kernel produces (same taps, same weights).
-__device__ __forceinline__ void sample_source(const AugArgs& a, const float* p, const uint8_t* img, int cx, int cy, float (&rgb)[3],
-                                              float& alpha, float& img_alpha, int& ny, int& nx) {
-    const float y0 = p[0], x0 = p[1], sh = p[2], sw = p[3];
-    const bool warp = p[15] != 0.0f;
-    rgb[0] = rgb[1] = rgb[2] = 0.0f;
-    alpha = 0.0f;
-    img_alpha = 1.0f;
-    ny = nx = 0;
-    if (warp) {
-        // datapipe/seg_transforms_cv.py:344-362: cv2.warpAffine(image, local_xf, crop, flags=interp, BORDER_REFLECT_101),
-        // labels INTER_NEAREST / constant 255, mask constant 0
-        float sx, sy;
-        warp_src(p, cx, cy, sx, sy);
-        nx = (int)floorf(sx + 0.5f);
-        ny = (int)floorf(sy + 0.5f);
-        if (p[22] == 0.0f) {
-            const uint8_t* q = img + ((size_t)reflect101(ny, a.Hs) * a.Ws + reflect101(nx, a.Ws)) * 3;
-            rgb[0] = (float)q[0]; rgb[1] = (float)q[1]; rgb[2] = (float)q[2];
-            alpha = ((unsigned)ny < (unsigned)a.Hs && (unsigned)nx < (unsigned)a.Ws) ? 1.0f : 0.0f;
-        } else {
-            const int ix0 = (int)floorf(sx), iy0 = (int)floorf(sy);
-            const float wx = sx - (float)ix0, wy = sy - (float)iy0;
-            auto wtap = [&](int Y, int X, float w) {
-                const uint8_t* q = img + ((size_t)reflect101(Y, a.Hs) * a.Ws + reflect101(X, a.Ws)) * 3;
-                rgb[0] += w * (float)q[0];
-                rgb[1] += w * (float)q[1];
-                rgb[2] += w * (float)q[2];
-                if ((unsigned)Y < (unsigned)a.Hs && (unsigned)X < (unsigned)a.Ws) alpha += w;
-            };
-            wtap(iy0, ix0, (1.0f - wy) * (1.0f - wx));
-            wtap(iy0, ix0 + 1, (1.0f - wy) * wx);
-            wtap(iy0 + 1, ix0, wy * (1.0f - wx));
-            wtap(iy0 + 1, ix0 + 1, wy * wx);
-        }
-    } else {
-        // bilinear tap positions inside the source window (cv2.INTER_LINEAR: half-pixel centres, border replicated)
-        float fy = ((float)cy + 0.5f) * (sh / (float)a.H) - 0.5f, fx = ((float)cx + 0.5f) * (sw / (float)a.W) - 0.5f;
-        fy = fminf(fmaxf(fy, 0.0f), sh - 1.0f);
-        fx = fminf(fmaxf(fx, 0.0f), sw - 1.0f);
-        const int iy0 = (int)floorf(fy), ix0 = (int)floorf(fx);
-        const float wy = fy - (float)iy0, wx = fx - (float)ix0;
-        const int iy1 = min(iy0 + 1, (int)sh - 1), ix1 = min(ix0 + 1, (int)sw - 1);
-        const int Y0 = iy0 + (int)y0, Y1 = iy1 + (int)y0, X0 = ix0 + (int)x0, X1 = ix1 + (int)x0;
-        auto tap = [&](int Y, int X, float w) {
-            if (w != 0.0f && (unsigned)Y < (unsigned)a.Hs && (unsigned)X < (unsigned)a.Ws) {
-                const uint8_t* q = img + ((size_t)Y * a.Ws + X) * 3;
-                rgb[0] += w * (float)q[0];
-                rgb[1] += w * (float)q[1];
-                rgb[2] += w * (float)q[2];
-                alpha += w;
-            }
-        };
-        tap(Y0, X0, (1.0f - wy) * (1.0f - wx));
-        tap(Y0, X1, (1.0f - wy) * wx);
-        tap(Y1, X0, wy * (1.0f - wx));
-        tap(Y1, X1, wy * wx);
-        img_alpha = alpha;
-        // cv2.INTER_NEAREST: floor(dst * scale)
-        ny = min((int)((float)cy * (sh / (float)a.H)), (int)sh - 1) + (int)y0;
-        nx = min((int)((float)cx * (sw / (float)a.W)), (int)sw - 1) + (int)x0;
-    }
-}
-
 template <class T>
 __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) {
     const size_t total = (size_t)a.N * a.H * a.W;
@@ -158,60 +39,28 @@ __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) {
         const int oy = (int)(t0 % a.H);
         const int n = (int)(t0 / a.H);
         const float* p = a.params + (size_t)n * CMS_AUG_PARAMS;
-        // undo the flips (applied after the crop in the reference: x flip, y flip, transpose)
-        int cy = oy, cx = ox;
-        if (p[6] != 0.0f) { const int t = cy; cy = cx; cx = t; }
-        if (p[5] != 0.0f) cy = a.H - 1 - cy;
-        if (p[4] != 0.0f) cx = a.W - 1 - cx;
+        int cy, cx;
+        stage_unflip(p, a.H, a.W, ox, oy, cx, cy);
+        const StageSrc sv = {a.src + (size_t)n * a.Hs * a.Ws * 3, a.src_labels ? a.src_labels + (size_t)n * a.Hs * a.Ws : nullptr, a.Hs, a.Ws};
         float rgb[3];
         float alpha, img_alpha;
         int ny, nx;
-        sample_source(a, p, a.src + (size_t)n * a.Hs * a.Ws * 3, cx, cy, rgb, alpha, img_alpha, ny, nx);
+        sample_source(sv, a.H, a.W, p, cx, cy, rgb, alpha, img_alpha, ny, nx);
         float r = rgb[0] * (1.0f / 255.0f), g = rgb[1] * (1.0f / 255.0f), b = rgb[2] * (1.0f / 255.0f);
         const size_t o = (size_t)n * 3 * plane + (size_t)oy * a.W + ox;
         if (a.out0) {
-            put<T>(a.out0, o, (r - a.mean[0] * img_alpha) * a.inv_std[0]);
-            put<T>(a.out0, o + plane, (g - a.mean[1] * img_alpha) * a.inv_std[1]);
-            put<T>(a.out0, o + 2 * plane, (b - a.mean[2] * img_alpha) * a.inv_std[2]);
+            put_as<T>(a.out0, o, (r - a.mean[0] * img_alpha) * a.inv_std[0]);
+            put_as<T>(a.out0, o + plane, (g - a.mean[1] * img_alpha) * a.inv_std[1]);
+            put_as<T>(a.out0, o + 2 * plane, (b - a.mean[2] * img_alpha) * a.inv_std[2]);
         }
         if (a.out1) {
-            if (p[12] != 0.0f) {                       // ColorJitter applied (RandomApply, p = aug_colour_prob)
-                const int order = (int)p[13];          // permutation index of (brightness, contrast, saturation, hue)
-                // decode the permutation: order = ((i0 * 4 + i1) * 4 + i2) * 4 + i3
-                const int ops[4] = {(order >> 6) & 3, (order >> 4) & 3, (order >> 2) & 3, order & 3};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    switch (ops[k]) {
-                    case 0: r = clamp01(r * p[7]); g = clamp01(g * p[7]); b = clamp01(b * p[7]); break;
-                    case 1: {
-                        const float m = p[14];          // mean luminance at the time contrast is applied (pre-pass)
-                        r = clamp01((r - m) * p[8] + m); g = clamp01((g - m) * p[8] + m); b = clamp01((b - m) * p[8] + m);
-                        break;
-                    }
-                    case 2: {
-                        const float gr = gray_of(r, g, b);
-                        r = clamp01((r - gr) * p[9] + gr); g = clamp01((g - gr) * p[9] + gr); b = clamp01((b - gr) * p[9] + gr);
-                        break;
-                    }
-                    default: if (p[10] != 0.0f) hue_shift(r, g, b, p[10]); break;
-                    }
-                }
-            }
-            if (p[11] != 0.0f) {                       // RandomGrayscale
-                const float gr = gray_of(r, g, b);
-                r = g = b = gr;
-            }
-            put<T>(a.out1, o, (r - a.mean[0] * img_alpha) * a.inv_std[0]);
-            put<T>(a.out1, o + plane, (g - a.mean[1] * img_alpha) * a.inv_std[1]);
-            put<T>(a.out1, o + 2 * plane, (b - a.mean[2] * img_alpha) * a.inv_std[2]);
+            colour_chain(p, r, g, b);
+            put_as<T>(a.out1, o, (r - a.mean[0] * img_alpha) * a.inv_std[0]);
+            put_as<T>(a.out1, o + plane, (g - a.mean[1] * img_alpha) * a.inv_std[1]);
+            put_as<T>(a.out1, o + 2 * plane, (b - a.mean[2] * img_alpha) * a.inv_std[2]);
         }
         if (a.out_mask) a.out_mask[(size_t)n * plane + (size_t)oy * a.W + ox] = alpha;
-        if (a.out_labels) {
-            uint8_t lab = 255;
-            if (a.src_labels && (unsigned)ny < (unsigned)a.Hs && (unsigned)nx < (unsigned)a.Ws)
-                lab = a.src_labels[((size_t)n * a.Hs + ny) * a.Ws + nx];
-            a.out_labels[(size_t)n * plane + (size_t)oy * a.W + ox] = lab;
-        }
+        if (a.out_labels) a.out_labels[(size_t)n * plane + (size_t)oy * a.W + ox] = stage_label(sv, ny, nx);
     }
 }
 
@@ -220,13 +69,13 @@ __global__ __launch_bounds__(256) void augment_luma_kernel(AugArgs a, float* __r
     __shared__ float red[16];
     const int n = blockIdx.x;
     const float* p = a.params + (size_t)n * CMS_AUG_PARAMS;
-    const uint8_t* img = a.src + (size_t)n * a.Hs * a.Ws * 3;
+    const StageSrc sv = {a.src + (size_t)n * a.Hs * a.Ws * 3, nullptr, a.Hs, a.Ws};
     float acc = 0.0f;
     for (int i = threadIdx.x; i < a.H * a.W; i += blockDim.x) {
         const int cy = i / a.W, cx = i % a.W;           // (flips do not change the mean)
         float rgb[3], alpha, img_alpha;
         int ny, nx;
-        sample_source(a, p, img, cx, cy, rgb, alpha, img_alpha, ny, nx);      // the image kernel's own taps and weights
+        sample_source(sv, a.H, a.W, p, cx, cy, rgb, alpha, img_alpha, ny, nx);  // the image kernel's own taps and weights
         acc += gray_of(rgb[0], rgb[1], rgb[2]) * (1.0f / 255.0f);
     }
     float v[1] = {acc};

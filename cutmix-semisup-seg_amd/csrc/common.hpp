@@ -85,4 +85,11 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
     return (uint16_t)(u >> 16);
 }
 
+// element `idx` of a tensor of fp32 (sizeof(T) == 4) or bf16 (sizeof(T) == 2) elements = v
+template <class T>
+__device__ __forceinline__ void put_as(void* base, size_t idx, float v) {
+    if constexpr (sizeof(T) == 4) reinterpret_cast<float*>(base)[idx] = v;
+    else reinterpret_cast<uint16_t*>(base)[idx] = f32_to_bf16(v);
+}
+
 }  // namespace cms

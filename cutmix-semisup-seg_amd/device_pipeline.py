@@ -95,13 +95,21 @@ class DeviceAugmenter(object):
         return cat(cat(cat(T(crop[::-1] * 0.5), R), S), T(-centre[::-1]))
 
     def draw_params(self, n, src_hw, with_labels=False):
-        """-> float32 (n, CMS_AUG_PARAMS) parameter table of cms_augment_desc (slot 14, the contrast pivot, is filled on the
-        device). `with_labels`: the samples carry label maps (the supervised stream) -- decides the interpolation draw of the
-        rotate / scale crop exactly as the reference does (:353-356)."""
-        hs, ws = int(src_hw[0]), int(src_hw[1])
+        """-> float32 (n, CMS_AUG_PARAMS) parameter table of cms_augment_desc / cms_stage_desc (slot 14, the contrast pivot, is
+        filled on the device). `src_hw`: one (Hs, Ws) for the whole batch, or a list of n of them (a ragged batch): row i is then
+        what a single-sample draw with size i gives at that point of the same random stream -- the loader workers of the
+        reference transform sample after sample. `with_labels`: the samples carry label maps (the supervised stream) -- decides
+        the interpolation draw of the rotate / scale crop exactly as the reference does (:353-356)."""
+        if np.ndim(src_hw) == 1:
+            sizes = [(int(src_hw[0]), int(src_hw[1]))] * n
+        else:
+            sizes = [(int(v[0]), int(v[1])) for v in src_hw]
+            if len(sizes) != n:
+                raise ValueError('draw_params: {} sizes for {} samples'.format(len(sizes), n))
         crop = np.array(self.crop_size)
         out = np.zeros((n, _lib.AUG_PARAMS), dtype=np.float32)
         for i in range(n):
+            hs, ws = sizes[i]
             if self.warp:
                 if self.uniform_scale:
                     sf = np.exp(self.rng.uniform(-self.log_max_scale, self.log_max_scale, size=(1,)))
@@ -160,6 +168,83 @@ class DeviceAugmenter(object):
             out[i, 7:11] = (fb, fc, fs, fh)
             out[i, 11], out[i, 12] = grey, apply
             out[i, 13] = (int(order[0]) << 6) | (int(order[1]) << 4) | (int(order[2]) << 2) | int(order[3])
+
+    @staticmethod
+    def _pivot_scale(params):
+        """factor of the luminance pre-pass in the contrast pivot: the brightness factor where brightness comes before contrast"""
+        order = params[:, 13].astype(np.int64)
+        pos_b = np.array([[(o >> s) & 3 for s in (6, 4, 2, 0)].index(0) for o in order])
+        pos_c = np.array([[(o >> s) & 3 for s in (6, 4, 2, 0)].index(1) for o in order])
+        return np.where(pos_b < pos_c, params[:, 7], 1.0).astype(np.float32)
+
+    def _stage_desc(self, pool, indices, p_dev, h, w, out0, out1, labs, mask):
+        """cms_stage_desc over `pool` for the samples `indices` (+ the tensors it points to, to be kept alive by the caller)"""
+        if not pool.image_buffer.is_cuda:
+            raise RuntimeError('DeviceAugmenter: the pool must be resident on a GPU (no CPU path)')
+        dev = pool.image_buffer.device
+        idx = torch.from_numpy(pool.entries_of(indices)).to(dev, non_blocking=True)
+        d = _lib.StageDesc()
+        d.pool_img = pool.image_buffer.data_ptr()
+        d.pool_labels = pool.label_buffer.data_ptr() if (labs is not None and pool.label_buffer is not None) else None
+        d.entries, d.index = pool.table_dev.data_ptr(), idx.data_ptr()
+        d.out0, d.out1 = out0.data_ptr(), (out1.data_ptr() if out1 is not None else None)
+        d.out_labels = labs.data_ptr() if labs is not None else None
+        d.out_mask = mask.data_ptr() if mask is not None else None
+        d.params = p_dev.data_ptr()
+        for i in range(3):
+            d.mean[i], d.std_[i] = float(self.mean[i]), float(self.std[i])
+        d.n, d.n_entries, d.h, d.w = len(indices), len(pool), h, w
+        d.out_dtype = _lib.F32 if out0.dtype == torch.float32 else _lib.BF16
+        return d, idx
+
+    def stage(self, pool, indices, with_labels, params=None):
+        """The ragged form of __call__: batch sample i is sample `indices[i]` of a resident_pool.ResidentPool (each with its own
+        size), gathered on the device by csrc/stage.hip. -> the same dictionary as __call__."""
+        n = len(indices)
+        h, w = self.crop_size
+        if with_labels and pool.label_buffer is None:
+            raise ValueError('DeviceAugmenter.stage: the pool holds no labels')
+        if params is None:
+            params = self.draw_params(n, pool.sizes_of(indices), with_labels=with_labels)
+        dev = pool.image_buffer.device
+        p_dev = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev, non_blocking=True)
+        out0 = torch.empty((n, 3, h, w), dtype=self.out_dtype, device=dev)
+        out1 = torch.empty_like(out0) if self.strong_colour else None
+        mask = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
+        labs = torch.empty((n, 1, h, w), dtype=torch.uint8, device=dev) if with_labels else None
+        d, idx = self._stage_desc(pool, indices, p_dev, h, w, out0, out1, labs, mask)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.strong_colour:
+            luma = torch.empty(n, dtype=torch.float32, device=dev)
+            check(fn['cms_stage_luma'](C.byref(d), C.c_void_p(luma.data_ptr()), stream), 'cms_stage_luma')
+            p_dev[:, 14] = luma * torch.from_numpy(self._pivot_scale(params)).to(dev)
+        check(fn['cms_stage_batch'](C.byref(d), stream), 'cms_stage_batch')
+        res = dict(image=out0, mask=mask)
+        if out1 is not None:
+            res['image_stu'] = out1
+        if labs is not None:
+            res['labels'] = labs
+        return res
+
+    def stage_eval(self, pool, indices, block_size):
+        """Whole images for evaluation: the reference's SegCVTransformNormalizeToTensor + SegCollate (datapipe/seg_data.py:
+        181-216, 246-273) -- standardised, centred on a canvas of the batch maximum rounded up to `block_size`, padding exactly 0
+        in the image and 255 in the labels. One launch of the staging kernel in window mode (negative origin, scale 1).
+        -> dict(image (N,3,Hc,Wc), labels (N,1,Hc,Wc) uint8, canvas, offsets)"""
+        from .datapipe.seg_data import collate_geometry
+        n = len(indices)
+        (hc, wc), offsets = collate_geometry(pool.sizes_of(indices), block_size)
+        params = np.zeros((n, _lib.AUG_PARAMS), dtype=np.float32)
+        for i, (top, left) in enumerate(offsets):
+            params[i, 0:4] = (-top, -left, hc, wc)
+        params[:, 7:10] = 1.0
+        dev = pool.image_buffer.device
+        p_dev = torch.from_numpy(params).to(dev, non_blocking=True)
+        out0 = torch.empty((n, 3, hc, wc), dtype=self.out_dtype, device=dev)
+        labs = torch.empty((n, 1, hc, wc), dtype=torch.uint8, device=dev)
+        d, idx = self._stage_desc(pool, indices, p_dev, hc, wc, out0, None, labs, None)
+        check(fn['cms_stage_batch'](C.byref(d), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cms_stage_batch')
+        return dict(image=out0, labels=labs, canvas=(hc, wc), offsets=offsets)
 
     def __call__(self, src_u8, labels_u8=None, params=None):
         """src_u8: CUDA uint8 (N, Hs, Ws, 3); labels_u8: CUDA uint8 (N, Hs, Ws) or None.

@@ -5,9 +5,16 @@ same 56 command-line options (names and defaults, train_seg_semisup_mask_mt.py:5
 
 Differences, all additive:
   * `--synthetic` (plus `--synthetic_n_classes`, `--synthetic_val_batches`) trains on synthetic tensors of the crop
-    shape: there are no datasets, pretrained weights or network in this environment, and the
-    reference's CPU data pipeline (datapipe/, cv2 / skimage) is outside the hot path. Without `--synthetic` the
-    trainer stops with a clear message. Synthetic runs use `pretrained=False`.
+    shape. Synthetic runs use `pretrained=False`.
+  * without `--synthetic`, `--dataset pascal` / `pascal_aug` train on Pascal VOC from `./semantic_segmentation.cfg`
+    (settings.py, datapipe/): the reference's splits and index streams on the host, every image decoded once into an
+    HBM-resident pool (resident_pool.py), training crops and padded evaluation batches gathered on the device
+    (device_pipeline.DeviceAugmenter.stage / stage_eval, csrc/stage.hip); VAL mIoU every epoch, FINAL TEST with
+    `--n_val`. One GPU, a `--crop_size` is required, weights from the package's initialisation (no pretrained
+    files here). The other three data sets stop with a clear message. On this path `--synthetic_source_size`,
+    `--synthetic_n_classes` and `--synthetic_val_batches` have no effect (sizes, classes and the validation set are the
+    data set's), `--num_workers` is accepted and unused, and the crop / flip / colour / mask draws are unseeded numpy
+    streams as in the reference (the index streams follow `torch.manual_seed`).
   * `--compute_dtype {bf16,fp32}` and `--no_fuse_batches`.
   * one process per GPU under torchrun (RANK / LOCAL_RANK / WORLD_SIZE); the reference is single-GPU (`cuda:0`, :58).
   * losses are accumulated on the device and read back once per epoch instead of three host syncs per iteration;
@@ -60,9 +67,21 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
 
     crop = None if crop_size == '' else [int(x.strip()) for x in crop_size.split(',')]
 
+    # Without --synthetic: the reference's data set path (:64-72) for Pascal VOC. The splits are made on the host exactly as the
+    # reference makes them; the images are decoded ONCE into an HBM-resident pool (resident_pool.py) after the GPU is up.
+    ds_dict = None
     if not synthetic:
-        raise job_helper.JobNotRun('This build covers the training step, not the dataset pipeline (datapipe/, cv2, dataset ZIPs are out of '
-              'scope and absent); run with --synthetic.')
+        if crop is None:
+            raise job_helper.JobNotRun('The data set path stages fixed-size crops on the device: give a --crop_size '
+                                       '(whole-image training batches are not built).')
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise job_helper.JobNotRun('The data set path is single-GPU (WORLD_SIZE > 1 is served by --synthetic only).')
+        from .datapipe import datasets
+        from . import settings as settings_mod
+        try:
+            ds_dict = datasets.load_dataset(dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
+        except settings_mod.DataPathError as e:   # no configuration file / no `pascal_voc` path / directory missing
+            raise job_helper.JobNotRun('{} -- or run with --synthetic.'.format(e))
     if crop is None:
         raise ValueError('--synthetic needs a --crop_size')
 
@@ -86,6 +105,18 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         _ops.probe_streams(torch_device, again=True)
 
     n_classes = int(synthetic_n_classes)
+    pool = None
+    if ds_dict is not None:
+        from .resident_pool import ResidentPool
+        ds_src = ds_dict['ds_src']
+        tgt_val_ndx, test_ndx = ds_dict['val_ndx_tgt'], ds_dict['test_ndx_tgt']
+        sup_ndx, unsup_ndx = ds_dict['sup_ndx'], ds_dict['unsup_ndx']
+        n_classes = ds_src.num_classes
+        t0 = time.time()
+        pool = ResidentPool(ds_src, list(sup_ndx) + list(unsup_ndx) + list(tgt_val_ndx) +
+                            (list(test_ndx) if test_ndx is not None else []), torch_device)
+        print('Resident pool: {} samples, {:.1f} MB in HBM, decoded in {:.1f}s'.format(len(pool), pool.nbytes() / 1e6,
+                                                                                     time.time() - t0))
     if bin_fill_holes and n_classes != 2:
         print('Binary hole filling can only be used with binary (2-class) segmentation datasets')
         return
@@ -135,7 +166,10 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                                                within_bounds=not boxmask_outside_bounds, invert=not boxmask_no_invert)
 
     if iters_per_epoch == -1:
-        iters_per_epoch = 1000
+        iters_per_epoch = 1000 if pool is None else len(unsup_ndx) // batch_size
+        if iters_per_epoch == 0:
+            raise job_helper.JobNotRun('--iters_per_epoch -1 means len(unsup_ndx) // batch_size = {} // {} = 0 iterations per '
+                                       'epoch: give --iters_per_epoch or a smaller --batch_size.'.format(len(unsup_ndx), batch_size))
     total_iters = iters_per_epoch * num_epochs
     lr_epoch_scheduler, lr_iter_scheduler = lr_schedules.make_lr_schedulers(
         optimizer=student_optim, total_iters=total_iters, schedule_type=lr_sched, step_epochs=lr_step_epochs,
@@ -165,7 +199,29 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     # batch goes through the device-side input staging (device_pipeline.py: crop / Hung scale / flips / colour
     # augmentation / standardisation -- the reference's loader-worker transforms, :150-183, with the --aug_* options)
     augment = None
-    if synthetic_source_size:
+    if pool is not None:
+        # the data set path: the same staging, every sample gathered from its own (variable-sized) pool entry. The reference
+        # seeds none of its numpy draws; neither does this path.
+        from .device_pipeline import DeviceAugmenter
+        from .datapipe import seg_data
+        mean, std = ds_src.get_mean_std()
+        mean = student_net.MEAN if student_net.MEAN is not None else mean
+        std = student_net.STD if student_net.STD is not None else std
+        mask_rng = np.random.RandomState()
+        augment = DeviceAugmenter((H, W), mean, std, scale_hung=aug_scale_hung,
+                                  scale_non_uniform=aug_scale_non_uniform, hflip=aug_hflip, vflip=aug_vflip,
+                                  hvflip=aug_hvflip, strong_colour=aug_strong_colour, brightness=aug_colour_brightness,
+                                  contrast=aug_colour_contrast, saturation=aug_colour_saturation, hue=aug_colour_hue,
+                                  colour_prob=aug_colour_prob, greyscale_prob=aug_colour_greyscale_prob, out_dtype=dtype,
+                                  rot_mag=aug_rot_mag, max_scale=aug_max_scale)
+        # RepeatSampler(SubsetRandomSampler) index streams (:203-212); the two unsupervised streams share one sampler
+        sup_stream, _ = seg_data.repeat_stream(sup_ndx, batch_size)
+        unsup_stream_0 = unsup_stream_1 = None
+        if cons_weight > 0.0:
+            unsup_stream_0, unsup_sampler = seg_data.repeat_stream(unsup_ndx, batch_size)
+            if step_cfg.mix:
+                unsup_stream_1 = seg_data.IndexStream(unsup_sampler, batch_size)
+    elif synthetic_source_size:
         from .device_pipeline import DeviceAugmenter
         hs, ws = [int(v.strip()) for v in synthetic_source_size.split(',')]
         augment = DeviceAugmenter((H, W), student_net.MEAN, student_net.STD, scale_hung=aug_scale_hung,
@@ -188,7 +244,37 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     print('Settings:')
     print(', '.join(['{}={}'.format(key, settings[key]) for key in sorted(list(settings.keys()))]))
     print('Dataset:')
-    print('synthetic: crop={}x{}, classes={}, world_size={}'.format(H, W, n_classes, world))
+    if pool is None:
+        print('synthetic: crop={}x{}, classes={}, world_size={}'.format(H, W, n_classes, world))
+    else:
+        print('len(sup_ndx)={}'.format(len(sup_ndx)))
+        print('len(unsup_ndx)={}'.format(len(unsup_ndx)))
+        print('len(val_ndx)={}'.format(len(tgt_val_ndx)))
+        if test_ndx is not None:
+            print('len(test_ndx)={}'.format(len(test_ndx)))
+        if n_sup != -1:
+            print('sup_ndx={}'.format(sup_ndx.tolist()))
+        # iterators in the reference's order (:251-253): each draws its base seed from torch's global generator here
+        sup_iter = iter(sup_stream)
+        unsup_iter_0 = iter(unsup_stream_0) if unsup_stream_0 is not None else None
+        unsup_iter_1 = iter(unsup_stream_1) if unsup_stream_1 is not None else None
+
+        def staged_eval(ndx, evaluator=None, preds_dir=None):
+            """The reference's evaluation loop (:504-514, 541-571) over `ndx` in index order: whole images, centred on a padded
+            canvas per batch (stage_eval); padding carries label 255 and is ignored."""
+            with torch.no_grad():
+                for batch_ndx in seg_data.eval_batches(ndx, batch_size):
+                    ev = augment.stage_eval(pool, batch_ndx, student_net.BLOCK_SIZE)
+                    logits = eval_net.forward_lowres(ev['image'])
+                    if evaluator is not None:
+                        evaluator.sample_logits(logits, ev['labels'], ev['canvas'], ignore_value=255,
+                                                align_corners=step.align_corners)
+                    if preds_dir is not None:
+                        _, pred = ops.argmax_confusion(logits, None, n_classes, ev['canvas'],
+                                                       align_corners=step.align_corners, want_pred=True)
+                        pred = pred.cpu().numpy()
+                        for k, sample_ndx in enumerate(batch_ndx):
+                            ds_src.save_prediction_by_index(preds_dir, pred[k].astype(np.uint32), sample_ndx)
 
     iter_i = 0
     print('Training...')
@@ -215,7 +301,10 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
             if step.nan_detected():
                 print('NaN detected; network dead, bailing.')
                 return
-            if augment is not None:
+            if pool is not None:
+                sb = augment.stage(pool, next(sup_iter), True)
+                batch_x, batch_y = sb['image'], sb['labels']
+            elif augment is not None:
                 sb = staged(True)
                 batch_x, batch_y = sb['image'], sb['labels']
             else:
@@ -226,8 +315,12 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                     rng_np = mask_generator.generate_ranges(batch_size, (H, W), rng=mask_rng)
                     ranges = ops.ranges_to_device(rng_np, torch_device)
                     if augment is not None:
-                        u0 = staged(False)
-                        u1 = staged(False) if step_cfg.mix else None
+                        if pool is not None:
+                            u0 = augment.stage(pool, next(unsup_iter_0), False)
+                            u1 = augment.stage(pool, next(unsup_iter_1), False) if step_cfg.mix else None
+                        else:
+                            u0 = staged(False)
+                            u1 = staged(False) if step_cfg.mix else None
                         unsup.append(UnsupBatch(u0['image'], ranges, um0=u0['mask'],
                                                 x1_tea=None if u1 is None else u1['image'],
                                                 um1=None if u1 is None else u1['mask'], x0_stu=u0.get('image_stu'),
@@ -260,11 +353,14 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
 
         eval_net.eval()
         tgt_iou_eval = evaluation.EvaluatorIoU(n_classes, bin_fill_holes)
-        with torch.no_grad():
-            for _b in range(synthetic_val_batches):
-                vx, vy = synth_images(), synth_labels()
-                tgt_iou_eval.sample_logits(eval_net.forward_lowres(vx), vy, (H, W), ignore_value=255,
-                                           align_corners=step.align_corners)
+        if pool is not None:
+            staged_eval(tgt_val_ndx, tgt_iou_eval)
+        else:
+            with torch.no_grad():
+                for _b in range(synthetic_val_batches):
+                    vx, vy = synth_images(), synth_labels()
+                    tgt_iou_eval.sample_logits(eval_net.forward_lowres(vx), vy, (H, W), ignore_value=255,
+                                               align_corners=step.align_corners)
         tgt_iou_eval.all_reduce()
         tgt_iou = tgt_iou_eval.score()
         tgt_miou = tgt_iou.mean()
@@ -283,6 +379,21 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         from . import checkpoint
         model_path = os.path.join(submit_config.run_dir, 'model.pth')
         checkpoint.save_model(eval_net, model_path)
+
+    if pool is not None:
+        # :537-577 -- prediction files (the Pascal source inherits DataSource.save_prediction_by_index), then the held-out test set
+        out_dir = None
+        eval_net.eval()
+        if save_preds:
+            out_dir = os.path.join(submit_config.run_dir, 'preds')
+            os.makedirs(out_dir, exist_ok=True)
+            staged_eval(tgt_val_ndx, None, out_dir)
+        if test_ndx is not None:
+            test_iou_eval = evaluation.EvaluatorIoU(n_classes, bin_fill_holes)
+            staged_eval(test_ndx, test_iou_eval, out_dir)
+            test_iou = test_iou_eval.score()
+            print('FINAL TEST: mIoU={:.3%}'.format(test_iou.mean()))
+            print('-- TEST {}'.format(', '.join(['{:.3%}'.format(x) for x in test_iou])))
 
 
 _OPTIONS = [

@@ -586,6 +586,41 @@ int cms_augment_batch(const cms_augment_desc* d, void* stream);
 int cms_augment_luma(const cms_augment_desc* d, float* luma, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Ragged staging (csrc/stage.hip): the same transform, every batch sample gathered from its own entry of a pool of
+ * VARIABLE-SIZED uint8 images resident in HBM (data sets whose images differ in size: Pascal VOC). Entry e of the pool is
+ * [hs][ws][3] uint8 at pool_img + entries[e].img_off and, with labels, [hs][ws] uint8 at pool_labels + entries[e].lab_off
+ * (dense rows; 64-bit byte offsets: pools exceed 4 GB). index[n] names the entry of batch sample n (any order, repeats
+ * allowed). params / outputs / mean / std_ / out_dtype: exactly cms_augment_desc's, slot meanings unchanged; with entries of
+ * one size and index = 0..n-1 the outputs are cms_augment_batch's bit for bit. Nothing outside an entry's hs * ws pixels is
+ * read: window taps are bounds-tested, warp taps reflected; an index outside [0, n_entries) or an entry with a non-positive
+ * size stages as an empty source (image 0, labels 255, mask 0). Whole-image evaluation staging (datapipe/seg_data.py:181-216,
+ * 246-273: standardise, centre on a canvas padded with image 0 / label 255) is window mode with origin (-dh // 2, -dw // 2),
+ * window = canvas = (h, w).
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct cms_stage_entry {
+    long long img_off;          /* byte offset of the entry's pixels in pool_img (16-byte aligned)   */
+    long long lab_off;          /* byte offset of its label map in pool_labels, or -1                */
+    int hs, ws;                 /* its size                                                          */
+} cms_stage_entry;
+typedef struct cms_stage_desc {
+    const uint8_t* pool_img;    /* uint8 pool of images                                  */
+    const uint8_t* pool_labels; /* uint8 pool of label maps or NULL                      */
+    const cms_stage_entry* entries; /* DEVICE [n_entries]                                */
+    const int* index;           /* DEVICE int32 [n]: pool entry of each batch sample     */
+    void* out0;                 /* (N,3,h,w) NCHW, out_dtype, or NULL                    */
+    void* out1;                 /* (N,3,h,w) NCHW, out_dtype, or NULL                    */
+    uint8_t* out_labels;        /* (N,h,w) uint8 or NULL (255 outside the source image)  */
+    float* out_mask;            /* (N,1,h,w) fp32 validity mask or NULL                  */
+    const float* params;        /* DEVICE [N][CMS_AUG_PARAMS]                            */
+    float mean[3], std_[3];
+    int n, n_entries, h, w;
+    int out_dtype;
+} cms_stage_desc;
+int cms_stage_batch(const cms_stage_desc* d, void* stream);
+/* luma[n] as cms_augment_luma, for the ragged source */
+int cms_stage_luma(const cms_stage_desc* d, float* luma, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Batch-statistics BatchNorm (+ ReLU, + residual) on NHWC activations (csrc/bn.hip): nn.BatchNorm2d in training mode,
  * architectures/deeplab2.py:72-84 without --freeze_bn, architectures/deeplab3plus.py:40-64 (head, always).
  * ONE descriptor (cms_bn_op) and ONE launch entry point (cms_bn_run, or cms_program_add_bn inside a recorded program);
