@@ -11,6 +11,7 @@ Layout
                   host-side mirror of the reference modules of the same names (same classes, signatures,
                   error behaviour), routed to the kernels above
   step.py         the fused student+teacher training iteration used by the trainer and bench.py
+  trainer_common.py  what the four trainers share: option blocks, set-up, networks + optimisers, the epoch loop
 
 Import as `cutmix_semisup_seg_amd` (alias package next to this directory).
 """

@@ -22,7 +22,7 @@ Differences, all additive:
 """
 import click
 
-from . import job_helper
+from . import job_helper, trainer_common as tc
 
 
 @job_helper.job('train_seg_semisup_mask_mt', enumerate_job_names=False)
@@ -60,12 +60,10 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     import time
     import numpy as np
     import torch
-    import torch.distributed as dist
-    from .architectures import network_architectures
-    from . import evaluation, optim_weight_ema, mask_gen, lr_schedules, optim as fused_optim, ops
+    from . import evaluation, mask_gen, lr_schedules, ops
     from .step import CutMixMeanTeacherStep, StepConfig, UnsupBatch
 
-    crop = None if crop_size == '' else [int(x.strip()) for x in crop_size.split(',')]
+    crop = tc.parse_crop_size(crop_size)
 
     # Without --synthetic: the reference's data set path (:64-72) for Pascal VOC. The splits are made on the host exactly as the
     # reference makes them; the images are decoded ONCE into an HBM-resident pool (resident_pool.py) after the GPU is up.
@@ -85,24 +83,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     if crop is None:
         raise ValueError('--synthetic needs a --crop_size')
 
-    # one process per GPU
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    local_rank = int(os.environ.get('LOCAL_RANK', '0'))
-    if not torch.cuda.is_available():
-        raise RuntimeError('train_seg_semisup_mask_mt needs a GPU; there is no CPU fallback')
-    torch.cuda.set_device(local_rank)
-    torch_device = torch.device('cuda', local_rank)
-    if world > 1 and not dist.is_initialized():
-        dist.init_process_group('nccl')
-    if world > 1:
-        # RCCL creates its internal stream with the first collective; it occupies one of the four hardware queues. Probe the side
-        # streams AFTER that, so the step's roles avoid the queue RCCL sits on (ops.probe_streams)
-        from cutmix_semisup_seg_amd import ops as _ops
-        _t = torch.ones(1, device=torch_device)
-        dist.all_reduce(_t)
-        torch.cuda.synchronize(torch_device)
-        _ops.probe_streams(torch_device, again=True)
+    world, rank, torch_device = tc.setup_process('train_seg_semisup_mask_mt', data_parallel=True)
 
     n_classes = int(synthetic_n_classes)
     pool = None
@@ -117,48 +98,11 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                             (list(test_ndx) if test_ndx is not None else []), torch_device)
         print('Resident pool: {} samples, {:.1f} MB in HBM, decoded in {:.1f}s'.format(len(pool), pool.nbytes() / 1e6,
                                                                                      time.time() - t0))
-    if bin_fill_holes and n_classes != 2:
-        print('Binary hole filling can only be used with binary (2-class) segmentation datasets')
+    nets = tc.build_networks(arch, n_classes, model, compute_dtype, torch_device, world, opt_type, learning_rate, sgd_momentum,
+                             sgd_nesterov, sgd_weight_decay, teacher_alpha, freeze_bn, bin_fill_holes)
+    if nets is None:
         return
-    print('Loaded data')
-
-    NetClass = network_architectures.seg.get(arch)
-    student_net = NetClass(n_classes, pretrained=False).to(torch_device)
-    dtype = torch.bfloat16 if compute_dtype == 'bf16' else torch.float32
-    student_net.compute_dtype = dtype
-    if world > 1:
-        for t in student_net.state_dict().values():       # identical replicas
-            dist.broadcast(t, src=0)
-
-    groups = [dict(params=list(student_net.pretrained_parameters()), lr=learning_rate * 0.1),
-              dict(params=list(student_net.new_parameters()), lr=learning_rate)]
-    if opt_type == 'adam':
-        student_optim = fused_optim.FusedAdam(student_net, groups)
-    elif opt_type == 'sgd':
-        student_optim = fused_optim.FusedSGD(student_net, groups, momentum=sgd_momentum, nesterov=sgd_nesterov,
-                                             weight_decay=sgd_weight_decay)
-    else:
-        raise ValueError('Unknown opt_type {}'.format(opt_type))
-
-    if model == 'mean_teacher':
-        teacher_net = NetClass(n_classes, pretrained=False).to(torch_device)
-        teacher_net.compute_dtype = dtype
-        for p in teacher_net.parameters():
-            p.requires_grad = False
-        teacher_optim = optim_weight_ema.EMAWeightOptimizer(teacher_net, student_net, teacher_alpha)
-        teacher_optim.fuse_into(student_optim)
-        eval_net = teacher_net
-    elif model == 'pi':
-        teacher_net = student_net
-        teacher_optim = None
-        eval_net = student_net
-    else:
-        print('Unknown model type {}'.format(model))
-        return
-
-    if freeze_bn and not hasattr(student_net, 'freeze_batchnorm'):
-        raise ValueError('Network {} does not support batchnorm freezing'.format(arch))
-    print('Built network')
+    student_net, teacher_net, eval_net, student_optim, teacher_optim, dtype = nets
 
     mask_generator = mask_gen.BoxMaskGenerator(prop_range=mask_prop_range, n_boxes=boxmask_n_boxes,
                                                random_aspect_ratio=not boxmask_fixed_aspect_ratio,
@@ -170,9 +114,8 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         if iters_per_epoch == 0:
             raise job_helper.JobNotRun('--iters_per_epoch -1 means len(unsup_ndx) // batch_size = {} // {} = 0 iterations per '
                                        'epoch: give --iters_per_epoch or a smaller --batch_size.'.format(len(unsup_ndx), batch_size))
-    total_iters = iters_per_epoch * num_epochs
-    lr_epoch_scheduler, lr_iter_scheduler = lr_schedules.make_lr_schedulers(
-        optimizer=student_optim, total_iters=total_iters, schedule_type=lr_sched, step_epochs=lr_step_epochs,
+    schedulers = lr_schedules.make_lr_schedulers(
+        optimizer=student_optim, total_iters=iters_per_epoch * num_epochs, schedule_type=lr_sched, step_epochs=lr_step_epochs,
         step_gamma=lr_step_gamma, poly_power=lr_poly_power)
 
     step_cfg = StepConfig(mask_mode=mask_mode, cons_loss_fn=cons_loss_fn, cons_weight=cons_weight,
@@ -186,14 +129,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     H, W = crop
     gen = torch.Generator(device=torch_device).manual_seed(12345 + rank)
     mask_rng = np.random.RandomState(12345 + rank)
-
-    def synth_images():
-        return torch.randn(batch_size, 3, H, W, generator=gen, device=torch_device).to(dtype)
-
-    def synth_labels():
-        y = torch.randint(0, n_classes, (batch_size, 1, H, W), generator=gen, device=torch_device)
-        y[torch.rand(batch_size, 1, H, W, generator=gen, device=torch_device) < 0.05] = 255
-        return y.to(torch.uint8)
+    data = tc.SyntheticData(gen, batch_size, crop, n_classes, dtype)
 
     # `--synthetic_source_size h,w`: the synthetic samples are uint8 SOURCE images of that size resident in HBM and every
     # batch goes through the device-side input staging (device_pipeline.py: crop / Hung scale / flips / colour
@@ -241,11 +177,9 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
             sl = slice(i * batch_size, (i + 1) * batch_size)
             return augment(src_pool[sl], lab_pool[sl] if with_labels else None)
 
-    print('Settings:')
-    print(', '.join(['{}={}'.format(key, settings[key]) for key in sorted(list(settings.keys()))]))
-    print('Dataset:')
+    tc.print_settings(settings)
     if pool is None:
-        print('synthetic: crop={}x{}, classes={}, world_size={}'.format(H, W, n_classes, world))
+        tc.print_synthetic_dataset(crop, n_classes, world)
     else:
         print('len(sup_ndx)={}'.format(len(sup_ndx)))
         print('len(unsup_ndx)={}'.format(len(unsup_ndx)))
@@ -276,103 +210,53 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                         for k, sample_ndx in enumerate(batch_ndx):
                             ds_src.save_prediction_by_index(preds_dir, pred[k].astype(np.uint32), sample_ndx)
 
-    iter_i = 0
-    print('Training...')
-    for epoch_i in range(num_epochs):
-        if lr_epoch_scheduler is not None:
-            lr_epoch_scheduler.step(epoch_i)
-        t1 = time.time()
-        ramp_val = network_architectures.sigmoid_rampup(epoch_i, rampup) if rampup > 0 else 1.0
-
-        student_net.train()
-        if teacher_net is not student_net:
-            teacher_net.train()
-        if freeze_bn:
-            student_net.freeze_batchnorm()
-            if teacher_net is not student_net:
-                teacher_net.freeze_batchnorm()
-
-        acc = torch.zeros(3, dtype=torch.float64, device=torch_device)    # sup, consistency, conf-rate sums
-        n_sup_batches = 0
-        n_unsup_batches = 0
-        for _ in range(iters_per_epoch):
-            if lr_iter_scheduler is not None:
-                lr_iter_scheduler.step(iter_i)
-            if step.nan_detected():
-                print('NaN detected; network dead, bailing.')
-                return
-            if pool is not None:
-                sb = augment.stage(pool, next(sup_iter), True)
-                batch_x, batch_y = sb['image'], sb['labels']
-            elif augment is not None:
-                sb = staged(True)
-                batch_x, batch_y = sb['image'], sb['labels']
-            else:
-                batch_x, batch_y = synth_images(), synth_labels()
-            unsup = []
-            if cons_weight > 0.0:
-                for _r in range(unsup_batch_ratio):
-                    rng_np = mask_generator.generate_ranges(batch_size, (H, W), rng=mask_rng)
-                    ranges = ops.ranges_to_device(rng_np, torch_device)
-                    if augment is not None:
-                        if pool is not None:
-                            u0 = augment.stage(pool, next(unsup_iter_0), False)
-                            u1 = augment.stage(pool, next(unsup_iter_1), False) if step_cfg.mix else None
-                        else:
-                            u0 = staged(False)
-                            u1 = staged(False) if step_cfg.mix else None
-                        unsup.append(UnsupBatch(u0['image'], ranges, um0=u0['mask'],
-                                                x1_tea=None if u1 is None else u1['image'],
-                                                um1=None if u1 is None else u1['mask'], x0_stu=u0.get('image_stu'),
-                                                x1_stu=None if u1 is None else u1.get('image_stu')))
-                        continue
-                    x0 = synth_images()
-                    x1 = synth_images() if step_cfg.mix else None
-                    x0s = synth_images() if aug_strong_colour else None
-                    x1s = synth_images() if (aug_strong_colour and step_cfg.mix) else None
-                    unsup.append(UnsupBatch(x0, ranges, x1_tea=x1, x0_stu=x0s, x1_stu=x1s))
-            res = step(batch_x, batch_y, unsup, ramp_val=ramp_val)
-            acc[0] += res['sup_loss']
-            n_sup_batches += 1
-            if res['consistency_loss'] is not None:
-                acc[1] += res['consistency_loss']
-                if conf_thresh > 0.0:
-                    acc[2] += res['conf_rate']
-                elif rampup > 0:
-                    acc[2] += ramp_val          # reference quirk (:419-420)
-                n_unsup_batches += len(unsup)
-            iter_i += 1
-
-        sums = acc.cpu().numpy()                                           # the one host sync of the epoch
-        sup_loss_acc = sums[0] / max(n_sup_batches, 1)
-        consistency_loss_acc = sums[1] / max(n_sup_batches, 1) if n_unsup_batches > 0 else 0.0
-        conf_rate_acc = sums[2] / max(n_sup_batches, 1) if n_unsup_batches > 0 else 0.0
-        if np.isnan(sup_loss_acc):
-            print('NaN detected; network dead, bailing.')
-            return
-
-        eval_net.eval()
-        tgt_iou_eval = evaluation.EvaluatorIoU(n_classes, bin_fill_holes)
+    def make_batch():
         if pool is not None:
-            staged_eval(tgt_val_ndx, tgt_iou_eval)
+            sb = augment.stage(pool, next(sup_iter), True)
+            batch_x, batch_y = sb['image'], sb['labels']
+        elif augment is not None:
+            sb = staged(True)
+            batch_x, batch_y = sb['image'], sb['labels']
         else:
-            with torch.no_grad():
-                for _b in range(synthetic_val_batches):
-                    vx, vy = synth_images(), synth_labels()
-                    tgt_iou_eval.sample_logits(eval_net.forward_lowres(vx), vy, (H, W), ignore_value=255,
-                                               align_corners=step.align_corners)
-        tgt_iou_eval.all_reduce()
-        tgt_iou = tgt_iou_eval.score()
-        tgt_miou = tgt_iou.mean()
-        t2 = time.time()
-        if rank == 0:
-            print('Epoch {}: took {:.3f}s, TRAIN clf loss={:.6f}, consistency loss={:.6f}, conf rate={:.3%}, '
-                  'VAL mIoU={:.3%}'.format(epoch_i + 1, t2 - t1, sup_loss_acc, consistency_loss_acc, conf_rate_acc,
-                                           tgt_miou))
-            print('-- {}'.format(', '.join(['{:.3%}'.format(x) for x in tgt_iou])))
-            print('-- {:.2f} img/s ({} GPU{})'.format(iters_per_epoch * batch_size * world / max(t2 - t1, 1e-9), world,
-                                                      's' if world > 1 else ''))
+            batch_x, batch_y = data.images(), data.labels()
+        unsup = []
+        if cons_weight > 0.0:
+            for _r in range(unsup_batch_ratio):
+                rng_np = mask_generator.generate_ranges(batch_size, (H, W), rng=mask_rng)
+                ranges = ops.ranges_to_device(rng_np, torch_device)
+                if augment is not None:
+                    if pool is not None:
+                        u0 = augment.stage(pool, next(unsup_iter_0), False)
+                        u1 = augment.stage(pool, next(unsup_iter_1), False) if step_cfg.mix else None
+                    else:
+                        u0 = staged(False)
+                        u1 = staged(False) if step_cfg.mix else None
+                    unsup.append(UnsupBatch(u0['image'], ranges, um0=u0['mask'],
+                                            x1_tea=None if u1 is None else u1['image'],
+                                            um1=None if u1 is None else u1['mask'], x0_stu=u0.get('image_stu'),
+                                            x1_stu=None if u1 is None else u1.get('image_stu')))
+                    continue
+                x0 = data.images()
+                x1 = data.images() if step_cfg.mix else None
+                x0s = data.images() if aug_strong_colour else None
+                x1s = data.images() if (aug_strong_colour and step_cfg.mix) else None
+                unsup.append(UnsupBatch(x0, ranges, x1_tea=x1, x0_stu=x0s, x1_stu=x1s))
+        return batch_x, batch_y, unsup
 
+    if pool is not None:
+        evaluate = lambda evaluator: staged_eval(tgt_val_ndx, evaluator)
+    else:
+        evaluate = data.evaluate_with(eval_net, step, synthetic_val_batches)
+    # inherited, not chosen: only a NaN SUPERVISED loss ends the job, and the step's NaN flag is polled every iteration (the other
+    # three trainers check both losses and do not poll); the confusion matrix is all_reduced and only rank 0 prints; this is
+    # the one trainer with the img/s line
+    if not tc.run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, schedulers, num_epochs,
+                         iters_per_epoch, freeze_bn, rampup, conf_thresh, n_classes, bin_fill_holes, torch_device,
+                         data_parallel=True, rank=rank, nan_checks_consistency=False, polls_step_nan=True,
+                         img_per_s_of=(batch_size, world)):
+        return
+
+    # inherited, not chosen: the whole module through checkpoint.save_model (the VAT trainer writes a state_dict)
     if save_model and rank == 0 and submit_config.run_dir is not None:
         # the reference pickles the whole module (:533-535): a clean replica without this build's runtime state, under
         # the reference's class paths (checkpoint.py)
@@ -396,89 +280,23 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
             print('-- TEST {}'.format(', '.join(['{:.3%}'.format(x) for x in test_iou])))
 
 
-_OPTIONS = [
-    click.option('--job_desc', type=str, default=''),
-    click.option('--dataset', type=click.Choice(['camvid', 'cityscapes', 'pascal', 'pascal_aug', 'isic2017']),
-                 default='pascal_aug'),
-    click.option('--model', type=click.Choice(['mean_teacher', 'pi']), default='mean_teacher'),
-    click.option('--arch', type=str, default='resnet101_deeplab_imagenet'),
-    click.option('--freeze_bn', is_flag=True, default=False),
-    click.option('--opt_type', type=click.Choice(['adam', 'sgd']), default='adam'),
-    click.option('--sgd_momentum', type=float, default=0.9),
-    click.option('--sgd_nesterov', is_flag=True, default=False),
-    click.option('--sgd_weight_decay', type=float, default=5e-4),
-    click.option('--learning_rate', type=float, default=1e-4),
-    click.option('--lr_sched', type=click.Choice(['none', 'stepped', 'cosine', 'poly']), default='none'),
-    click.option('--lr_step_epochs', type=str, default=''),
-    click.option('--lr_step_gamma', type=float, default=0.1),
-    click.option('--lr_poly_power', type=float, default=0.9),
-    click.option('--teacher_alpha', type=float, default=0.99),
-    click.option('--bin_fill_holes', is_flag=True, default=False),
-    click.option('--crop_size', type=str, default='321,321'),
-    click.option('--aug_hflip', is_flag=True, default=False),
-    click.option('--aug_vflip', is_flag=True, default=False),
-    click.option('--aug_hvflip', is_flag=True, default=False),
-    click.option('--aug_scale_hung', is_flag=True, default=False),
-    click.option('--aug_max_scale', type=float, default=1.0),
-    click.option('--aug_scale_non_uniform', is_flag=True, default=False),
-    click.option('--aug_rot_mag', type=float, default=0.0),
-    click.option('--aug_strong_colour', is_flag=True, default=False),
-    click.option('--aug_colour_brightness', type=float, default=0.4),
-    click.option('--aug_colour_contrast', type=float, default=0.4),
-    click.option('--aug_colour_saturation', type=float, default=0.4),
-    click.option('--aug_colour_hue', type=float, default=0.1),
-    click.option('--aug_colour_prob', type=float, default=0.8),
-    click.option('--aug_colour_greyscale_prob', type=float, default=0.2),
-    click.option('--mask_mode', type=click.Choice(['zero', 'mix']), default='mix'),
-    click.option('--mask_prop_range', type=str, default='0.5'),
-    click.option('--boxmask_n_boxes', type=int, default=1),
-    click.option('--boxmask_fixed_aspect_ratio', is_flag=True, default=False),
-    click.option('--boxmask_by_size', is_flag=True, default=False),
-    click.option('--boxmask_outside_bounds', is_flag=True, default=False),
-    click.option('--boxmask_no_invert', is_flag=True, default=False),
-    click.option('--cons_loss_fn', type=click.Choice(['var', 'bce', 'kld', 'logits_var', 'logits_smoothl1']),
-                 default='var'),
-    click.option('--cons_weight', type=float, default=1.0),
-    click.option('--conf_thresh', type=float, default=0.97),
-    click.option('--conf_per_pixel', is_flag=True, default=False),
-    click.option('--rampup', type=int, default=-1),
-    click.option('--unsup_batch_ratio', type=int, default=1),
-    click.option('--num_epochs', type=int, default=300),
-    click.option('--iters_per_epoch', type=int, default=-1),
-    click.option('--batch_size', type=int, default=10),
-    click.option('--n_sup', type=int, default=100),
-    click.option('--n_unsup', type=int, default=-1),
-    click.option('--n_val', type=int, default=-1),
-    click.option('--split_seed', type=int, default=12345),
-    click.option('--split_path', type=click.Path(readable=True, exists=True)),
-    click.option('--val_seed', type=int, default=131),
-    click.option('--synthetic_source_size', type=str, default=''),
-    click.option('--save_preds', is_flag=True, default=False),
-    click.option('--save_model', is_flag=True, default=False),
-    click.option('--num_workers', type=int, default=4),
-    # additions of this build
-    click.option('--synthetic', is_flag=True, default=False),
-    click.option('--synthetic_n_classes', type=int, default=21),
-    click.option('--synthetic_val_batches', type=int, default=2),
-    click.option('--compute_dtype', type=click.Choice(['bf16', 'fp32']), default='bf16'),
-    click.option('--no_fuse_batches', is_flag=True, default=False),
-    # run-to-run deterministic weight gradients (slab + ordered reduce instead of fp32 atomics; 1.5-2 % slower)
-    click.option('--deterministic', is_flag=True, default=False),
-    # data-parallel gradient exchange: the fp32 arena (default) or a bf16 staging copy (half the bytes on xGMI)
-    click.option('--allreduce_dtype', type=click.Choice(['fp32', 'bf16']), default='fp32'),
-]
-
-
-def _with_options(f):
-    for opt in reversed(_OPTIONS):
-        f = opt(f)
-    return f
-
-
-@click.command()
-@_with_options
-def experiment(**params):
-    train_seg_semisup_mask_mt.submit(**params)
+experiment = tc.make_command(train_seg_semisup_mask_mt, (
+    tc.head_options(sgd_nesterov=False) + tc.geometry_options() + tc.colour_options() +
+    [click.option('--mask_mode', type=click.Choice(['zero', 'mix']), default='mix'),
+     click.option('--mask_prop_range', type=str, default='0.5'),
+     click.option('--boxmask_n_boxes', type=int, default=1),
+     click.option('--boxmask_fixed_aspect_ratio', is_flag=True, default=False),
+     click.option('--boxmask_by_size', is_flag=True, default=False),
+     click.option('--boxmask_outside_bounds', is_flag=True, default=False),
+     click.option('--boxmask_no_invert', is_flag=True, default=False)] +
+    tc.consistency_options() +
+    tc.run_options(after_val_seed=[click.option('--synthetic_source_size', type=str, default='')]) +
+    tc.build_options() +
+    [click.option('--no_fuse_batches', is_flag=True, default=False),
+     # run-to-run deterministic weight gradients (slab + ordered reduce instead of fp32 atomics; 1.5-2 % slower)
+     click.option('--deterministic', is_flag=True, default=False),
+     # data-parallel gradient exchange: the fp32 arena (default) or a bf16 staging copy (half the bytes on xGMI)
+     click.option('--allreduce_dtype', type=click.Choice(['fp32', 'bf16']), default='fp32')]))
 
 
 if __name__ == '__main__':
