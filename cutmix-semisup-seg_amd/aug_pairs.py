@@ -13,12 +13,22 @@ sample and in their order, and the matrices that go with them.
                                                                F.affine_grid(align_corners=True) that warps view 0 into view 1
 
 Matrices are `cv2.warpAffine`-style 2x3 float32 arrays composed in float32 with the conventions of datapipe/affine.py (x before
-y, rotation [[c, s], [-s, c]]), as DeviceAugmenter.local_xf already does for a single view. What this module does NOT do is
-cut the views: coupling real images to these matrices belongs to the dataset pipeline, which is out of scope.
+y, rotation [[c, s], [-s, c]]), as DeviceAugmenter.local_xf already does for a single view.
+
+The views themselves are cut on the device by the staging kernel (csrc/stage.hip) that cuts single views: `pair_rows` turns one
+drawn pair into two rows of its parameter table (include/cutmixseg.h, CMS_AUG_PARAMS), DeviceAugmenter.stage_pair adds the
+colour draw of view 1 and launches it over both views of a batch.
+
+    plain crop           two window rows: origin pos_v (relative to the unpadded source), size = crop
+    Hung scale crop      view 0: window pos0 / crop; view 1: window pos1 / sc_size1, resized by the kernel, its validity mask
+                         resized with INTER_NEAREST (:272; slot 23 = 1) where single views use INTER_LINEAR (:215)
+    rotate / scale crop  two warp rows: the float64 inverse of the pre-flip xf_cv[v], always INTER_LINEAR (:426)
+    flips                slots 4-6 of each row
 """
 import numpy as np
 
 F32 = np.float32
+N_PARAMS = 24               # == CMS_AUG_PARAMS
 
 
 def identity(n=1):
@@ -105,8 +115,42 @@ def xf0_to_1(xf0_cv, xf1_cv, size_hw):
     return cv_to_torch(cat(xf1_cv, inverse(xf0_cv)), size_hw).astype(F32)
 
 
+def inverse_slots(m):
+    """A 2x3 warpAffine matrix -> slots 16..21 of a warp row, (a00 a01 a02 a10 a11 a12) of its inverse in float64 (cv2 inverts
+    in double precision)"""
+    m = np.asarray(m).astype(np.float64)
+    det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    inv2 = np.array([[m[1, 1], -m[0, 1]], [-m[1, 0], m[0, 0]]]) / det
+    invt = -inv2 @ m[:, 2]
+    return (inv2[0, 0], inv2[0, 1], invt[0], inv2[1, 0], inv2[1, 1], invt[1])
+
+
+def pair_rows(info, crop_size):
+    """One drawn pair (the parameter dict of PairGeometry.draw) -> float32 (2, N_PARAMS): the rows of the staging kernel's
+    parameter table that cut view 0 and view 1. No colour change (slots 7-9 = 1, 11-13 = 0): DeviceAugmenter.stage_pair draws
+    view 1's."""
+    crop = (int(crop_size[0]), int(crop_size[1]))
+    rows = np.zeros((2, N_PARAMS), dtype=F32)
+    rows[:, 7:10] = 1.0
+    if info['kind'] == 'warp':
+        rows[:, 2:4] = crop
+        rows[:, 15] = 1.0
+        rows[:, 22] = 1.0                                  # an unlabelled pair is always INTER_LINEAR
+        for v in range(2):
+            rows[v, 16:22] = inverse_slots(info['xf_cv'][v])
+    else:
+        rows[0, 0:2], rows[1, 0:2] = info['pos0'], info['pos1']
+        rows[:, 2:4] = crop
+        if info['kind'] == 'hung':
+            rows[1, 2:4] = info['sc_size1']
+            rows[1, 23] = 1.0                              # view 1's mask is resized with INTER_NEAREST
+    if 'flips' in info:
+        rows[:, 4:7] = info['flips']
+    return rows
+
+
 class PairGeometry(object):
-    """Draws the geometry of pairs of views cut from source images of one size."""
+    """Draws the geometry of pairs of views cut from source images."""
 
     def __init__(self, crop_size, offset_range=16.0, scale_hung=False, max_scale=1.0, rot_mag=0.0, scale_non_uniform=False,
                  free_scale_rot=False, hflip=False, vflip=False, hvflip=False, rng=None):
@@ -179,7 +223,8 @@ class PairGeometry(object):
         return xf, dict(kind='warp', scales_yx=scales, thetas=thetas, centre0=centre0, offset1=offset1)
 
     def draw(self, src_hw):
-        """One pair. -> (xf_cv (2,2,3) float32: source image -> view 0 / view 1, xf0_to_1 (2,3) float32, the drawn parameters)"""
+        """One pair. -> (xf_cv (2,2,3) float32: source image -> view 0 / view 1, xf0_to_1 (2,3) float32, the drawn parameters;
+        their 'xf_cv' is the pair of matrices BEFORE the flips, which is what cuts the views: the flips come after the cut)"""
         img = np.array([int(src_hw[0]), int(src_hw[1])])
         if self.scale_hung:
             xf, info = self._hung_pair(img)
@@ -187,6 +232,7 @@ class PairGeometry(object):
             xf, info = self._warp_pair(img)
         else:
             xf, info = self._crop_pair(img)
+        info['xf_cv'] = xf
         if self.flip_flags.any():
             f = (self.rng.binomial(1, 0.5, size=(2, 3)) != 0) & self.flip_flags
             xf = cat(flips(f, tuple(self.crop)), xf)
@@ -194,6 +240,11 @@ class PairGeometry(object):
         return xf, xf0_to_1(xf[0:1], xf[1:2], tuple(self.crop))[0], info
 
     def draw_batch(self, n, src_hw):
-        """-> (xf0_to_1 (n,2,3) float32, xf_cv (n,2,2,3) float32, list of parameter dicts)"""
-        out = [self.draw(src_hw) for _ in range(n)]
+        """`src_hw`: one (Hs, Ws) for the whole batch, or a list of n of them (a ragged batch); the pairs are drawn one after the
+        other from the one generator, as the loader workers of the reference transform sample after sample.
+        -> (xf0_to_1 (n,2,3) float32, xf_cv (n,2,2,3) float32, list of parameter dicts)"""
+        sizes = [src_hw] * n if np.ndim(src_hw) == 1 else list(src_hw)
+        if len(sizes) != n:
+            raise ValueError('draw_batch: {} sizes for {} pairs'.format(len(sizes), n))
+        out = [self.draw(s) for s in sizes]
         return np.stack([o[1] for o in out]), np.stack([o[0] for o in out]), [o[2] for o in out]

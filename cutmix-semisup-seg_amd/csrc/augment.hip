@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) {
             put_as<T>(a.out1, o + plane, (g - a.mean[1] * img_alpha) * a.inv_std[1]);
             put_as<T>(a.out1, o + 2 * plane, (b - a.mean[2] * img_alpha) * a.inv_std[2]);
         }
-        if (a.out_mask) a.out_mask[(size_t)n * plane + (size_t)oy * a.W + ox] = alpha;
+        if (a.out_mask) a.out_mask[(size_t)n * plane + (size_t)oy * a.W + ox] = stage_mask(sv, p, alpha, ny, nx);
         if (a.out_labels) a.out_labels[(size_t)n * plane + (size_t)oy * a.W + ox] = stage_label(sv, ny, nx);
     }
 }

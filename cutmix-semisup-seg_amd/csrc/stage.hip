@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void stage_kernel(StageArgs a) {
             put_as<T>(a.out1, o + plane, (g - a.mean[1] * img_alpha) * a.inv_std[1]);
             put_as<T>(a.out1, o + 2 * plane, (b - a.mean[2] * img_alpha) * a.inv_std[2]);
         }
-        if (a.out_mask) a.out_mask[(size_t)n * plane + (size_t)i] = alpha;
+        if (a.out_mask) a.out_mask[(size_t)n * plane + (size_t)i] = ok ? stage_mask(sv, p, alpha, ny, nx) : 0.0f;
         if (a.out_labels) a.out_labels[(size_t)n * plane + (size_t)i] = ok ? stage_label(sv, ny, nx) : (uint8_t)255;
     }
 }

@@ -163,6 +163,15 @@ CMS_HD uint8_t stage_label(const StageSrc& s, int ny, int nx) {
     return 255;
 }
 
+// The validity mask of one output pixel from what sample_source returned (params slot 23, the mask mode): 0 = `alpha`, the
+// in-bounds weight of the image taps (cv2.INTER_LINEAR of the mask: single views, :215, and warps); 1 = whether the NEAREST source
+// pixel (ny, nx) lies inside the source (cv2.INTER_NEAREST of the mask: view 1 of a Hung pair, :272). The image's `img_alpha` is
+// the linear weight in both modes (the reference resizes the image's alpha channel linearly). No memory is read.
+CMS_HD float stage_mask(const StageSrc& s, const float* p, float alpha, int ny, int nx) {
+    if (p[23] == 0.0f) return alpha;
+    return ((unsigned)ny < (unsigned)s.Hs && (unsigned)nx < (unsigned)s.Ws) ? 1.0f : 0.0f;
+}
+
 // The colour half (student view): RandomApply(ColorJitter) in the drawn order, then RandomGrayscale; r, g, b in [0, 1]
 CMS_HD void colour_chain(const float* p, float& r, float& g, float& b) {
     if (p[12] != 0.0f) {                       // ColorJitter applied (RandomApply, p = aug_colour_prob)

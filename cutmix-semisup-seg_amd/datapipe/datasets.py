@@ -32,7 +32,7 @@ def load_dataset(dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_pat
     """-> dict(ds_src, ds_tgt, val_ndx_src, val_ndx_tgt, test_ndx_tgt, sup_ndx, unsup_ndx), the reference's keys"""
     if dataset in KNOWN and dataset not in BUILT:
         raise job_helper.JobNotRun('The data set path is built for {} only; `{}` is not (its ZIP readers and load-time resizing '
-                                   'are out of scope). Use one of those or --synthetic.'.format(' and '.join(BUILT), dataset))
+                                   'are out of scope). Use one of those, or run with --synthetic.'.format(' and '.join(BUILT), dataset))
     if dataset not in BUILT:
         raise ValueError('Unknown dataset {}'.format(dataset))
 

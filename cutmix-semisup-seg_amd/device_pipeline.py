@@ -20,6 +20,9 @@ are drawn on the host, per sample and in the reference's order:
     flips   rng.binomial(1, 0.5, size=(3,)) & [hflip, vflip, hvflip]        (:479-480)
     colour  (student view of a pair only, :575-583) RandomApply(ColorJitter, p), RandomGrayscale(p)   [torchvision]
 
+A PAIR of views of one sample (the augmentation trainer's unsupervised stream) is two rows of the same table, drawn by
+aug_pairs.PairGeometry and converted by aug_pairs.pair_rows; stage_pair stages both views of a batch in one launch.
+
 What is NOT reproduced bit for bit, and cannot be pinned here (cv2 / PIL / torchvision are absent): cv2.resize's 11-bit
 fixed-point interpolation and its rounding to uint8 before the colour operations, PIL's rounding after every jitter
 operation, and torchvision's use of Python's global `random` for the colour draws (a numpy RandomState here). The
@@ -31,7 +34,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, aug_pairs
 from ._lib import fn, check
 
 
@@ -123,14 +126,9 @@ class DeviceAugmenter(object):
                 centre = extra * self.rng.uniform(0.0, 1.0, size=(2,)) + np.minimum(sc_size, img) * 0.5
                 xf = self.local_xf(crop, theta[0], sf, centre)
                 interp = 0 if with_labels else int(self.rng.choice([0, 1]))        # cv2.INTER_NEAREST = 0, INTER_LINEAR = 1
-                m = xf.astype(np.float64)                                           # (cv2 inverts in double precision)
-                det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
-                inv2 = np.array([[m[1, 1], -m[0, 1]], [-m[1, 0], m[0, 0]]]) / det
-                invt = -inv2 @ m[:, 2]
                 out[i, 2:4] = crop
                 out[i, 15] = 1.0
-                out[i, 16:19] = (inv2[0, 0], inv2[0, 1], invt[0])
-                out[i, 19:22] = (inv2[1, 0], inv2[1, 1], invt[1])
+                out[i, 16:22] = aug_pairs.inverse_slots(xf)                         # (cv2 inverts in double precision)
                 out[i, 22] = interp
                 self._finish_row(out, i)
                 continue
@@ -154,6 +152,10 @@ class DeviceAugmenter(object):
         if self.flips.any():
             f = (self.rng.binomial(1, 0.5, size=(3,)) != 0) & self.flips
             out[i, 4:7] = f
+        self._colour_row(out, i)
+
+    def _colour_row(self, out, i):
+        """The colour draw of row i (torchvision's RandomApply(ColorJitter), RandomGrayscale); without it the factors are 1."""
         out[i, 7:10] = 1.0
         if self.strong_colour:
             cr = self.colour_rng
@@ -187,14 +189,15 @@ class DeviceAugmenter(object):
         d.pool_img = pool.image_buffer.data_ptr()
         d.pool_labels = pool.label_buffer.data_ptr() if (labs is not None and pool.label_buffer is not None) else None
         d.entries, d.index = pool.table_dev.data_ptr(), idx.data_ptr()
-        d.out0, d.out1 = out0.data_ptr(), (out1.data_ptr() if out1 is not None else None)
+        d.out0 = out0.data_ptr() if out0 is not None else None
+        d.out1 = out1.data_ptr() if out1 is not None else None
         d.out_labels = labs.data_ptr() if labs is not None else None
         d.out_mask = mask.data_ptr() if mask is not None else None
         d.params = p_dev.data_ptr()
         for i in range(3):
             d.mean[i], d.std_[i] = float(self.mean[i]), float(self.std[i])
         d.n, d.n_entries, d.h, d.w = len(indices), len(pool), h, w
-        d.out_dtype = _lib.F32 if out0.dtype == torch.float32 else _lib.BF16
+        d.out_dtype = _lib.F32 if (out0 if out0 is not None else out1).dtype == torch.float32 else _lib.BF16
         return d, idx
 
     def stage(self, pool, indices, with_labels, params=None):
@@ -225,6 +228,51 @@ class DeviceAugmenter(object):
         if labs is not None:
             res['labels'] = labs
         return res
+
+    def draw_pair_params(self, geometry, src_hw):
+        """The draws of a batch of PAIRS of views (aug_pairs.PairGeometry `geometry`, one (Hs, Ws) per sample in `src_hw`): the
+        geometry of every pair first, sample after sample, then the rows that cut them -- view-major float32
+        (2, n, CMS_AUG_PARAMS) -- with the colour draw on view 1 only (SegCVTransformTVT(apply_pair1=True), :575-583).
+        -> (params, xf0_to_1 (n,2,3) float32)"""
+        if tuple(int(v) for v in geometry.crop) != self.crop_size:
+            raise ValueError('draw_pair_params: the pair geometry cuts {} crops, the augmenter {}'.format(
+                tuple(geometry.crop), self.crop_size))
+        n = len(src_hw)
+        xf0_to_1, _, infos = geometry.draw_batch(n, src_hw)
+        params = np.zeros((2, n, _lib.AUG_PARAMS), dtype=np.float32)
+        for i, info in enumerate(infos):
+            params[:, i] = aug_pairs.pair_rows(info, self.crop_size)
+            self._colour_row(params[1], i)
+        return params, xf0_to_1
+
+    def stage_pair(self, pool, indices, geometry, drawn=None):
+        """Two views of every sample `indices[i]` of the pool, cut as the reference's `transform_pair` methods cut them
+        (aug_pairs.py) -- ONE launch of the staging kernel over 2n rows (view-major: the n entries twice), the luminance
+        pre-pass over the view-1 half only. View 0 carries no colour change, so the colour output serves both views.
+        `drawn`: the (params, xf0_to_1) of draw_pair_params instead of a fresh draw.
+        -> image0, image1 (n,3,h,w), mask0, mask1 (n,1,h,w) fp32 -- views into the halves of one buffer each -- and xf0_to_1
+        (n,2,3) float32 numpy, the theta of F.affine_grid(align_corners=True) that warps view 0 into view 1."""
+        n = len(indices)
+        h, w = self.crop_size
+        params, xf0_to_1 = drawn if drawn is not None else self.draw_pair_params(geometry, pool.sizes_of(indices))
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        if params.shape != (2, n, _lib.AUG_PARAMS):
+            raise ValueError('stage_pair: params {} for {} pairs'.format(params.shape, n))
+        dev = pool.image_buffer.device
+        p_dev = torch.from_numpy(params).to(dev, non_blocking=True)
+        image = torch.empty((2 * n, 3, h, w), dtype=self.out_dtype, device=dev)
+        mask = torch.empty((2 * n, 1, h, w), dtype=torch.float32, device=dev)
+        d, idx = self._stage_desc(pool, list(indices) * 2, p_dev, h, w, None, image, None, mask)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.strong_colour:
+            # the contrast pivot of the view-1 rows: the same descriptor, its index and params advanced by n rows
+            d1 = _lib.StageDesc.from_buffer_copy(d)
+            d1.index, d1.params, d1.n = idx.data_ptr() + n * idx.element_size(), p_dev[1].data_ptr(), n
+            luma = torch.empty(n, dtype=torch.float32, device=dev)
+            check(fn['cms_stage_luma'](C.byref(d1), C.c_void_p(luma.data_ptr()), stream), 'cms_stage_luma')
+            p_dev[1, :, 14] = luma * torch.from_numpy(self._pivot_scale(params[1])).to(dev)
+        check(fn['cms_stage_batch'](C.byref(d), stream), 'cms_stage_batch')
+        return image[:n], image[n:], mask[:n], mask[n:], xf0_to_1
 
     def stage_eval(self, pool, indices, block_size):
         """Whole images for evaluation: the reference's SegCVTransformNormalizeToTensor + SegCollate (datapipe/seg_data.py:

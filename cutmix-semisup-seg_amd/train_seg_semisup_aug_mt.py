@@ -3,13 +3,19 @@ Mirror of the reference's train_seg_semisup_aug_mt.py: the augmentation-consiste
 the same 51 command-line options (names and defaults, train_seg_semisup_aug_mt.py:515-567), job/log layout and per-epoch log
 lines, driving the MI355X iteration of aug.py.
 
-This trainer has no data set path: `--synthetic` data only (plus `--synthetic_n_classes`, `--synthetic_val_batches`,
-`--compute_dtype`). The option blocks, set-up, networks and epoch loop it shares with the other three trainers are in
-trainer_common.py; losses are accumulated on the device. The two views of an unsupervised batch are
-synthetic images as in the ICT trainer; the PAIR GEOMETRY (xf0_to_1) is drawn by aug_pairs.py with the reference's draws for
-the given --aug_* options, and the validity masks are all-valid. Cutting real views that go with these matrices (cv2 crops,
-resizes and warps of dataset images) belongs to the dataset pipeline, which stays out of scope. One GPU: the step has no
-data-parallel form yet and refuses WORLD_SIZE > 1.
+`--synthetic` (plus `--synthetic_n_classes`, `--synthetic_val_batches`) trains on synthetic tensors of the crop shape: the two
+views of an unsupervised batch are independent synthetic images, the PAIR GEOMETRY (xf0_to_1) is drawn by aug_pairs.py with the
+reference's draws for the given --aug_* options, and the validity masks are all-valid. `--compute_dtype` as in the other trainers.
+Without `--synthetic`, `--dataset pascal` / `pascal_aug` train on Pascal VOC from `./semantic_segmentation.cfg` through the
+data set path the four trainers share (trainer_common.open_dataset / DatasetRun, as in train_seg_semisup_mask_mt.py): the
+reference's splits and index streams on the host, every image decoded once into an HBM-resident pool, training crops and padded
+evaluation batches gathered on the device; VAL mIoU every epoch, `--save_preds`, FINAL TEST with `--n_val`. One GPU, a
+`--crop_size` is required; the other data sets, `--crop_size ''` and WORLD_SIZE > 1 stop with a message before the GPU is touched.
+There the two views of every unsupervised sample are cut on the device from its one pool entry as the drawn geometry says
+(aug_pairs.pair_rows -> DeviceAugmenter.stage_pair: one launch of the staging kernel for both views, their validity masks with
+them, the colour change on view 1 only); supervised batches are single views with the same --aug_* choice. The option blocks,
+set-up, networks, data set path and epoch loop it shares with the other three trainers are in trainer_common.py; losses are
+accumulated on the device. One GPU: the step has no data-parallel form yet and refuses WORLD_SIZE > 1.
 """
 import click
 
@@ -40,12 +46,18 @@ def train_seg_semisup_aug_mt(submit_config, dataset, model, arch, freeze_bn,
     from .aug import AugMeanTeacherStep, AugConfig, AugUnsupBatch
     from .aug_pairs import PairGeometry
 
-    crop = tc.synthetic_crop(crop_size, synthetic)
+    crop = tc.parse_crop_size(crop_size)
+    # Without --synthetic: the Pascal VOC data set path the four trainers share (trainer_common.py); refusals come first
+    ds_dict = tc.open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
     # inherited, not chosen: the step has no data-parallel form, so more than one process is refused
     world, _, torch_device = tc.setup_process('train_seg_semisup_aug_mt', data_parallel=False,
                                               one_gpu_what='augmentation consistency')
 
     n_classes = int(synthetic_n_classes)
+    run = None
+    if ds_dict is not None:
+        run = tc.DatasetRun(ds_dict, torch_device, batch_size)
+        n_classes = run.n_classes
     nets = tc.build_networks(arch, n_classes, model, compute_dtype, torch_device, world, opt_type, learning_rate, sgd_momentum,
                              sgd_nesterov, sgd_weight_decay, teacher_alpha, freeze_bn, bin_fill_holes)
     if nets is None:
@@ -53,7 +65,7 @@ def train_seg_semisup_aug_mt(submit_config, dataset, model, arch, freeze_bn,
     student_net, teacher_net, eval_net, student_optim, teacher_optim, dtype = nets
 
     if iters_per_epoch == -1:
-        iters_per_epoch = 1000
+        iters_per_epoch = 1000 if run is None else run.iters_per_epoch(iters_per_epoch)
     schedulers = lr_schedules.make_lr_schedulers(
         optimizer=student_optim, total_iters=iters_per_epoch * num_epochs, schedule_type=lr_sched, step_epochs=lr_step_epochs,
         step_gamma=lr_step_gamma, poly_power=lr_poly_power)
@@ -67,10 +79,24 @@ def train_seg_semisup_aug_mt(submit_config, dataset, model, arch, freeze_bn,
     # the transform choice of :129-144; the synthetic "source images" are 1.5 x the crop, so every transform has room to move
     pairs = PairGeometry(crop, offset_range=aug_offset_range, scale_hung=aug_scale_hung, max_scale=aug_max_scale,
                          rot_mag=aug_rot_mag, scale_non_uniform=aug_scale_non_uniform, free_scale_rot=aug_free_scale_rot,
-                         hflip=aug_hflip, vflip=aug_vflip, hvflip=aug_hvflip, rng=np.random.RandomState(12345))
+                         hflip=aug_hflip, vflip=aug_vflip, hvflip=aug_hvflip,
+                         rng=np.random.RandomState(12345) if run is None else None)
     src_hw = (H + H // 2, W + W // 2)
+    augment = None
+    if run is not None:
+        # supervised batches: the single-view transforms with the same --aug_* choice (:129-144)
+        augment = run.make_streams(student_net, crop, dtype, settings, 1 if cons_weight > 0.0 else 0)
 
     def make_batch():
+        if run is not None:
+            sb = augment.stage(run.pool, next(sup_iter), True)
+            unsup = []
+            if cons_weight > 0.0:
+                for _r in range(unsup_batch_ratio):
+                    # both views of every sample, cut on the device as the drawn pair geometry says (:274-281)
+                    x0, x1, um0, um1, xf0_to_1 = augment.stage_pair(run.pool, next(unsup_iter), pairs)
+                    unsup.append(AugUnsupBatch(x0, x1, xf0_to_1, um0=um0, um1=um1))
+            return sb['image'], sb['labels'], unsup
         batch_x, batch_y = data.images(), data.labels()
         unsup = []
         if cons_weight > 0.0:
@@ -81,14 +107,17 @@ def train_seg_semisup_aug_mt(submit_config, dataset, model, arch, freeze_bn,
         return batch_x, batch_y, unsup
 
     tc.print_settings(settings)
-    tc.print_synthetic_dataset(crop, n_classes, world)
+    if run is None:
+        tc.print_synthetic_dataset(crop, n_classes, world)
+    else:
+        sup_iter, unsup_iter = (run.print_sizes_and_start(n_sup) + [None])[:2]
 
     # inherited, not chosen: a NaN supervised OR consistency loss ends the job, the step's NaN flag is not polled; no all_reduce
     # of the confusion matrix and no rank gate on the prints (one process); no img/s line
-    if not tc.run_epochs(step, make_batch, data.evaluate_with(eval_net, step, synthetic_val_batches), student_net, teacher_net,
-                         eval_net, schedulers, num_epochs, iters_per_epoch, freeze_bn, rampup, conf_thresh, n_classes,
-                         bin_fill_holes, torch_device, data_parallel=False, nan_checks_consistency=True,
-                         polls_step_nan=False):
+    evaluate = run.evaluate_with(eval_net, step) if run is not None else data.evaluate_with(eval_net, step, synthetic_val_batches)
+    if not tc.run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, schedulers, num_epochs,
+                         iters_per_epoch, freeze_bn, rampup, conf_thresh, n_classes, bin_fill_holes, torch_device,
+                         data_parallel=False, nan_checks_consistency=True, polls_step_nan=False):
         return
 
     # inherited, not chosen: the whole module through checkpoint.save_model (the VAT trainer writes a state_dict)
@@ -96,6 +125,9 @@ def train_seg_semisup_aug_mt(submit_config, dataset, model, arch, freeze_bn,
         # the reference pickles the whole module (:467-469): a clean replica under the reference's class paths (checkpoint.py)
         from . import checkpoint
         checkpoint.save_model(eval_net, os.path.join(submit_config.run_dir, 'model.pth'))
+
+    if run is not None:
+        run.finish(eval_net, step, save_preds, submit_config, bin_fill_holes)       # :471-511
 
 
 experiment = tc.make_command(train_seg_semisup_aug_mt, (

@@ -7,8 +7,8 @@ Differences, all additive:
   * `--synthetic` (plus `--synthetic_n_classes`, `--synthetic_val_batches`) trains on synthetic tensors of the crop
     shape. Synthetic runs use `pretrained=False`.
   * without `--synthetic`, `--dataset pascal` / `pascal_aug` train on Pascal VOC from `./semantic_segmentation.cfg`
-    (settings.py, datapipe/): the reference's splits and index streams on the host, every image decoded once into an
-    HBM-resident pool (resident_pool.py), training crops and padded evaluation batches gathered on the device
+    (settings.py, datapipe/; trainer_common.open_dataset / DatasetRun, shared by the four trainers): the reference's splits and
+    index streams on the host, every image decoded once into an HBM-resident pool (resident_pool.py), training crops and padded evaluation batches gathered on the device
     (device_pipeline.DeviceAugmenter.stage / stage_eval, csrc/stage.hip); VAL mIoU every epoch, FINAL TEST with
     `--n_val`. One GPU, a `--crop_size` is required, weights from the package's initialisation (no pretrained
     files here). The other three data sets stop with a clear message. On this path `--synthetic_source_size`,
@@ -57,47 +57,23 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         raise ValueError('Unknown mask_mode {}'.format(mask_mode))
 
     import os
-    import time
     import numpy as np
     import torch
-    from . import evaluation, mask_gen, lr_schedules, ops
+    from . import mask_gen, lr_schedules, ops
     from .step import CutMixMeanTeacherStep, StepConfig, UnsupBatch
 
     crop = tc.parse_crop_size(crop_size)
 
-    # Without --synthetic: the reference's data set path (:64-72) for Pascal VOC. The splits are made on the host exactly as the
-    # reference makes them; the images are decoded ONCE into an HBM-resident pool (resident_pool.py) after the GPU is up.
-    ds_dict = None
-    if not synthetic:
-        if crop is None:
-            raise job_helper.JobNotRun('The data set path stages fixed-size crops on the device: give a --crop_size '
-                                       '(whole-image training batches are not built).')
-        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-            raise job_helper.JobNotRun('The data set path is single-GPU (WORLD_SIZE > 1 is served by --synthetic only).')
-        from .datapipe import datasets
-        from . import settings as settings_mod
-        try:
-            ds_dict = datasets.load_dataset(dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
-        except settings_mod.DataPathError as e:   # no configuration file / no `pascal_voc` path / directory missing
-            raise job_helper.JobNotRun('{} -- or run with --synthetic.'.format(e))
-    if crop is None:
-        raise ValueError('--synthetic needs a --crop_size')
+    # Without --synthetic: the reference's data set path (:64-72) for Pascal VOC, shared by the four trainers (trainer_common.py)
+    ds_dict = tc.open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
 
     world, rank, torch_device = tc.setup_process('train_seg_semisup_mask_mt', data_parallel=True)
 
     n_classes = int(synthetic_n_classes)
-    pool = None
+    run = None
     if ds_dict is not None:
-        from .resident_pool import ResidentPool
-        ds_src = ds_dict['ds_src']
-        tgt_val_ndx, test_ndx = ds_dict['val_ndx_tgt'], ds_dict['test_ndx_tgt']
-        sup_ndx, unsup_ndx = ds_dict['sup_ndx'], ds_dict['unsup_ndx']
-        n_classes = ds_src.num_classes
-        t0 = time.time()
-        pool = ResidentPool(ds_src, list(sup_ndx) + list(unsup_ndx) + list(tgt_val_ndx) +
-                            (list(test_ndx) if test_ndx is not None else []), torch_device)
-        print('Resident pool: {} samples, {:.1f} MB in HBM, decoded in {:.1f}s'.format(len(pool), pool.nbytes() / 1e6,
-                                                                                     time.time() - t0))
+        run = tc.DatasetRun(ds_dict, torch_device, batch_size)
+        n_classes = run.n_classes
     nets = tc.build_networks(arch, n_classes, model, compute_dtype, torch_device, world, opt_type, learning_rate, sgd_momentum,
                              sgd_nesterov, sgd_weight_decay, teacher_alpha, freeze_bn, bin_fill_holes)
     if nets is None:
@@ -110,10 +86,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                                                within_bounds=not boxmask_outside_bounds, invert=not boxmask_no_invert)
 
     if iters_per_epoch == -1:
-        iters_per_epoch = 1000 if pool is None else len(unsup_ndx) // batch_size
-        if iters_per_epoch == 0:
-            raise job_helper.JobNotRun('--iters_per_epoch -1 means len(unsup_ndx) // batch_size = {} // {} = 0 iterations per '
-                                       'epoch: give --iters_per_epoch or a smaller --batch_size.'.format(len(unsup_ndx), batch_size))
+        iters_per_epoch = 1000 if run is None else run.iters_per_epoch(iters_per_epoch)
     schedulers = lr_schedules.make_lr_schedulers(
         optimizer=student_optim, total_iters=iters_per_epoch * num_epochs, schedule_type=lr_sched, step_epochs=lr_step_epochs,
         step_gamma=lr_step_gamma, poly_power=lr_poly_power)
@@ -135,38 +108,18 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     # batch goes through the device-side input staging (device_pipeline.py: crop / Hung scale / flips / colour
     # augmentation / standardisation -- the reference's loader-worker transforms, :150-183, with the --aug_* options)
     augment = None
-    if pool is not None:
+    if run is not None:
         # the data set path: the same staging, every sample gathered from its own (variable-sized) pool entry. The reference
-        # seeds none of its numpy draws; neither does this path.
-        from .device_pipeline import DeviceAugmenter
-        from .datapipe import seg_data
-        mean, std = ds_src.get_mean_std()
-        mean = student_net.MEAN if student_net.MEAN is not None else mean
-        std = student_net.STD if student_net.STD is not None else std
+        # seeds none of its numpy draws; neither does this path. The two unsupervised streams share one sampler (:203-212)
         mask_rng = np.random.RandomState()
-        augment = DeviceAugmenter((H, W), mean, std, scale_hung=aug_scale_hung,
-                                  scale_non_uniform=aug_scale_non_uniform, hflip=aug_hflip, vflip=aug_vflip,
-                                  hvflip=aug_hvflip, strong_colour=aug_strong_colour, brightness=aug_colour_brightness,
-                                  contrast=aug_colour_contrast, saturation=aug_colour_saturation, hue=aug_colour_hue,
-                                  colour_prob=aug_colour_prob, greyscale_prob=aug_colour_greyscale_prob, out_dtype=dtype,
-                                  rot_mag=aug_rot_mag, max_scale=aug_max_scale)
-        # RepeatSampler(SubsetRandomSampler) index streams (:203-212); the two unsupervised streams share one sampler
-        sup_stream, _ = seg_data.repeat_stream(sup_ndx, batch_size)
-        unsup_stream_0 = unsup_stream_1 = None
-        if cons_weight > 0.0:
-            unsup_stream_0, unsup_sampler = seg_data.repeat_stream(unsup_ndx, batch_size)
-            if step_cfg.mix:
-                unsup_stream_1 = seg_data.IndexStream(unsup_sampler, batch_size)
+        augment = run.make_streams(student_net, (H, W), dtype, settings,
+                                   0 if cons_weight <= 0.0 else (2 if step_cfg.mix else 1))
     elif synthetic_source_size:
         from .device_pipeline import DeviceAugmenter
         hs, ws = [int(v.strip()) for v in synthetic_source_size.split(',')]
-        augment = DeviceAugmenter((H, W), student_net.MEAN, student_net.STD, scale_hung=aug_scale_hung,
-                                  scale_non_uniform=aug_scale_non_uniform, hflip=aug_hflip, vflip=aug_vflip,
-                                  hvflip=aug_hvflip, strong_colour=aug_strong_colour, brightness=aug_colour_brightness,
-                                  contrast=aug_colour_contrast, saturation=aug_colour_saturation, hue=aug_colour_hue,
-                                  colour_prob=aug_colour_prob, greyscale_prob=aug_colour_greyscale_prob, out_dtype=dtype,
+        augment = DeviceAugmenter((H, W), student_net.MEAN, student_net.STD, out_dtype=dtype,
                                   rng=np.random.RandomState(54321 + rank), colour_rng=np.random.RandomState(99 + rank),
-                                  rot_mag=aug_rot_mag, max_scale=aug_max_scale)
+                                  **tc.augmenter_options(settings))
         src_pool = torch.randint(0, 256, (4 * batch_size, hs, ws, 3), generator=gen, device=torch_device, dtype=torch.uint8)
         lab_pool = torch.randint(0, n_classes, (4 * batch_size, hs, ws), generator=gen, device=torch_device).to(torch.uint8)
         pool_pos = [0]
@@ -178,41 +131,14 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
             return augment(src_pool[sl], lab_pool[sl] if with_labels else None)
 
     tc.print_settings(settings)
-    if pool is None:
+    if run is None:
         tc.print_synthetic_dataset(crop, n_classes, world)
     else:
-        print('len(sup_ndx)={}'.format(len(sup_ndx)))
-        print('len(unsup_ndx)={}'.format(len(unsup_ndx)))
-        print('len(val_ndx)={}'.format(len(tgt_val_ndx)))
-        if test_ndx is not None:
-            print('len(test_ndx)={}'.format(len(test_ndx)))
-        if n_sup != -1:
-            print('sup_ndx={}'.format(sup_ndx.tolist()))
-        # iterators in the reference's order (:251-253): each draws its base seed from torch's global generator here
-        sup_iter = iter(sup_stream)
-        unsup_iter_0 = iter(unsup_stream_0) if unsup_stream_0 is not None else None
-        unsup_iter_1 = iter(unsup_stream_1) if unsup_stream_1 is not None else None
-
-        def staged_eval(ndx, evaluator=None, preds_dir=None):
-            """The reference's evaluation loop (:504-514, 541-571) over `ndx` in index order: whole images, centred on a padded
-            canvas per batch (stage_eval); padding carries label 255 and is ignored."""
-            with torch.no_grad():
-                for batch_ndx in seg_data.eval_batches(ndx, batch_size):
-                    ev = augment.stage_eval(pool, batch_ndx, student_net.BLOCK_SIZE)
-                    logits = eval_net.forward_lowres(ev['image'])
-                    if evaluator is not None:
-                        evaluator.sample_logits(logits, ev['labels'], ev['canvas'], ignore_value=255,
-                                                align_corners=step.align_corners)
-                    if preds_dir is not None:
-                        _, pred = ops.argmax_confusion(logits, None, n_classes, ev['canvas'],
-                                                       align_corners=step.align_corners, want_pred=True)
-                        pred = pred.cpu().numpy()
-                        for k, sample_ndx in enumerate(batch_ndx):
-                            ds_src.save_prediction_by_index(preds_dir, pred[k].astype(np.uint32), sample_ndx)
+        sup_iter, unsup_iter_0, unsup_iter_1 = (run.print_sizes_and_start(n_sup) + [None, None])[:3]
 
     def make_batch():
-        if pool is not None:
-            sb = augment.stage(pool, next(sup_iter), True)
+        if run is not None:
+            sb = augment.stage(run.pool, next(sup_iter), True)
             batch_x, batch_y = sb['image'], sb['labels']
         elif augment is not None:
             sb = staged(True)
@@ -225,9 +151,9 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                 rng_np = mask_generator.generate_ranges(batch_size, (H, W), rng=mask_rng)
                 ranges = ops.ranges_to_device(rng_np, torch_device)
                 if augment is not None:
-                    if pool is not None:
-                        u0 = augment.stage(pool, next(unsup_iter_0), False)
-                        u1 = augment.stage(pool, next(unsup_iter_1), False) if step_cfg.mix else None
+                    if run is not None:
+                        u0 = augment.stage(run.pool, next(unsup_iter_0), False)
+                        u1 = augment.stage(run.pool, next(unsup_iter_1), False) if step_cfg.mix else None
                     else:
                         u0 = staged(False)
                         u1 = staged(False) if step_cfg.mix else None
@@ -243,10 +169,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                 unsup.append(UnsupBatch(x0, ranges, x1_tea=x1, x0_stu=x0s, x1_stu=x1s))
         return batch_x, batch_y, unsup
 
-    if pool is not None:
-        evaluate = lambda evaluator: staged_eval(tgt_val_ndx, evaluator)
-    else:
-        evaluate = data.evaluate_with(eval_net, step, synthetic_val_batches)
+    evaluate = run.evaluate_with(eval_net, step) if run is not None else data.evaluate_with(eval_net, step, synthetic_val_batches)
     # inherited, not chosen: only a NaN SUPERVISED loss ends the job, and the step's NaN flag is polled every iteration (the other
     # three trainers check both losses and do not poll); the confusion matrix is all_reduced and only rank 0 prints; this is
     # the one trainer with the img/s line
@@ -264,20 +187,8 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         model_path = os.path.join(submit_config.run_dir, 'model.pth')
         checkpoint.save_model(eval_net, model_path)
 
-    if pool is not None:
-        # :537-577 -- prediction files (the Pascal source inherits DataSource.save_prediction_by_index), then the held-out test set
-        out_dir = None
-        eval_net.eval()
-        if save_preds:
-            out_dir = os.path.join(submit_config.run_dir, 'preds')
-            os.makedirs(out_dir, exist_ok=True)
-            staged_eval(tgt_val_ndx, None, out_dir)
-        if test_ndx is not None:
-            test_iou_eval = evaluation.EvaluatorIoU(n_classes, bin_fill_holes)
-            staged_eval(test_ndx, test_iou_eval, out_dir)
-            test_iou = test_iou_eval.score()
-            print('FINAL TEST: mIoU={:.3%}'.format(test_iou.mean()))
-            print('-- TEST {}'.format(', '.join(['{:.3%}'.format(x) for x in test_iou])))
+    if run is not None:
+        run.finish(eval_net, step, save_preds, submit_config, bin_fill_holes)       # :537-577
 
 
 experiment = tc.make_command(train_seg_semisup_mask_mt, (

@@ -3,9 +3,14 @@ Mirror of the reference's train_seg_semisup_vat_mt.py: the VAT mean-teacher (or 
 command-line options (names and defaults, train_seg_semisup_vat_mt.py:592-644), job/log layout and per-epoch log
 lines, driving the MI355X VAT iteration (vat.py). SURVEY.md 8(f) rank 2.
 
-This trainer has no data set path: `--synthetic` data only (plus `--synthetic_n_classes`, `--synthetic_val_batches`,
-`--compute_dtype`). One process per GPU under torchrun; the option blocks, set-up, networks and epoch loop it shares with the
-other three trainers are in trainer_common.py, losses are accumulated on the device.
+`--synthetic` (plus `--synthetic_n_classes`, `--synthetic_val_batches`) trains on synthetic tensors of the crop shape, one
+process per GPU under torchrun; `--compute_dtype` as in the other trainers. Without `--synthetic`, `--dataset pascal` / `pascal_aug` train on Pascal VOC from `./semantic_segmentation.cfg` through the
+data set path the four trainers share (trainer_common.open_dataset / DatasetRun, as in train_seg_semisup_mask_mt.py): the
+reference's splits and index streams on the host, every image decoded once into an HBM-resident pool, training crops and padded
+evaluation batches gathered on the device; VAL mIoU every epoch, `--save_preds`, FINAL TEST with `--n_val`. One GPU, a
+`--crop_size` is required; the other data sets, `--crop_size ''` and WORLD_SIZE > 1 stop with a message before the GPU is touched.
+The option blocks, set-up, networks, data set path and epoch loop it shares with the other three trainers are in trainer_common.py,
+losses are accumulated on the device.
 The reference runs this trainer with its DenseNet-161 U-Net (BASELINE configs[4]); that backbone's arithmetic lives in
 torchvision and is not part of this build -- the trainer takes any registered architecture, as the reference's does.
 """
@@ -37,10 +42,16 @@ def train_seg_semisup_vat_mt(submit_config, dataset, model, arch, freeze_bn,
     from . import lr_schedules
     from .vat import VATMeanTeacherStep, VATConfig, VATUnsupBatch
 
-    crop = tc.synthetic_crop(crop_size, synthetic)
+    crop = tc.parse_crop_size(crop_size)
+    # Without --synthetic: the Pascal VOC data set path the four trainers share (trainer_common.py); refusals come first
+    ds_dict = tc.open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
     world, rank, torch_device = tc.setup_process('train_seg_semisup_vat_mt', data_parallel=True)
 
     n_classes = int(synthetic_n_classes)
+    run = None
+    if ds_dict is not None:
+        run = tc.DatasetRun(ds_dict, torch_device, batch_size)
+        n_classes = run.n_classes
     nets = tc.build_networks(arch, n_classes, model, compute_dtype, torch_device, world, opt_type, learning_rate, sgd_momentum,
                              sgd_nesterov, sgd_weight_decay, teacher_alpha, freeze_bn, bin_fill_holes)
     if nets is None:
@@ -48,7 +59,7 @@ def train_seg_semisup_vat_mt(submit_config, dataset, model, arch, freeze_bn,
     student_net, teacher_net, eval_net, student_optim, teacher_optim, dtype = nets
 
     if iters_per_epoch == -1:
-        iters_per_epoch = 1000
+        iters_per_epoch = 1000 if run is None else run.iters_per_epoch(iters_per_epoch)
     schedulers = lr_schedules.make_lr_schedulers(
         optimizer=student_optim, total_iters=iters_per_epoch * num_epochs, schedule_type=lr_sched, step_epochs=lr_step_epochs,
         step_gamma=lr_step_gamma, poly_power=lr_poly_power)
@@ -61,7 +72,19 @@ def train_seg_semisup_vat_mt(submit_config, dataset, model, arch, freeze_bn,
     step = VATMeanTeacherStep(student_net, teacher_net, student_optim, teacher_optim, cfg,
                               vat_dir_from_student=vat_dir_from_student, generator=gen)
 
+    augment = None
+    if run is not None:
+        augment = run.make_streams(student_net, crop, dtype, settings, 1 if cons_weight > 0.0 else 0)
+
     def make_batch():
+        if run is not None:
+            sb = augment.stage(run.pool, next(sup_iter), True)
+            unsup = []
+            if cons_weight > 0.0:
+                for _r in range(unsup_batch_ratio):
+                    u = augment.stage(run.pool, next(unsup_iter), False)                  # :369
+                    unsup.append(VATUnsupBatch(u['image'], u.get('image_stu'), um=u['mask']))
+            return sb['image'], sb['labels'], unsup
         batch_x, batch_y = data.images(), data.labels()
         unsup = []
         if cons_weight > 0.0:
@@ -71,19 +94,25 @@ def train_seg_semisup_vat_mt(submit_config, dataset, model, arch, freeze_bn,
         return batch_x, batch_y, unsup
 
     tc.print_settings(settings)
-    tc.print_synthetic_dataset(crop, n_classes, world)
+    if run is None:
+        tc.print_synthetic_dataset(crop, n_classes, world)
+    else:
+        sup_iter, unsup_iter = (run.print_sizes_and_start(n_sup) + [None])[:2]
 
     # inherited, not chosen: a NaN supervised OR consistency loss ends the job, the step's NaN flag is not polled; the confusion
     # matrix is all_reduced and only rank 0 prints (the ICT and augmentation trainers do neither); no img/s line
-    if not tc.run_epochs(step, make_batch, data.evaluate_with(eval_net, step, synthetic_val_batches), student_net, teacher_net,
-                         eval_net, schedulers, num_epochs, iters_per_epoch, freeze_bn, rampup, conf_thresh, n_classes,
-                         bin_fill_holes, torch_device, data_parallel=True, rank=rank, nan_checks_consistency=True,
-                         polls_step_nan=False):
+    evaluate = run.evaluate_with(eval_net, step) if run is not None else data.evaluate_with(eval_net, step, synthetic_val_batches)
+    if not tc.run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, schedulers, num_epochs,
+                         iters_per_epoch, freeze_bn, rampup, conf_thresh, n_classes, bin_fill_holes, torch_device,
+                         data_parallel=True, rank=rank, nan_checks_consistency=True, polls_step_nan=False):
         return
 
     # inherited, not chosen: this trainer writes a state_dict, the other three go through checkpoint.save_model
     if save_model and rank == 0 and submit_config.run_dir is not None:
         torch.save(eval_net.state_dict(), os.path.join(submit_config.run_dir, 'model.pth'))
+
+    if run is not None:
+        run.finish(eval_net, step, save_preds, submit_config, bin_fill_holes)       # :547-587
 
 
 experiment = tc.make_command(train_seg_semisup_vat_mt, (

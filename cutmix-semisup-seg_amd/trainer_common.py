@@ -1,7 +1,8 @@
 """
 What the four semi-supervised trainers (train_seg_semisup_mask_mt / _vat_mt / _ict / _aug_mt) have in common: the shared blocks
-of the reference's option tables, process and device set-up, networks and optimisers, synthetic data, and the epoch loop with
-its bookkeeping and log lines. A trainer file keeps what is its own: its options, its config / step / batch construction and how
+of the reference's option tables, process and device set-up, networks and optimisers, synthetic data, the Pascal VOC data set
+path (pool, index streams, staged evaluation, prediction files, FINAL TEST), and the epoch loop with its bookkeeping and log
+lines. A trainer file keeps what is its own: its options, its config / step / batch construction and how
 it saves.
 
 Plain functions and one small class; what differs between trainers is a keyword argument or a callable passed in. torch is
@@ -125,15 +126,27 @@ def parse_crop_size(crop_size):
     return None if crop_size == '' else [int(x.strip()) for x in crop_size.split(',')]
 
 
-def synthetic_crop(crop_size, synthetic):
-    """`--crop_size` of a trainer that has no data set path: refuses to start without `--synthetic`."""
-    crop = parse_crop_size(crop_size)
+def open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path):
+    """The checks of a trainer's data before anything touches the GPU -> None with `--synthetic`, else the reference's data set
+    dictionary (datapipe.datasets.load_dataset: Pascal VOC, the splits made on the host exactly as the reference makes them).
+    Whatever keeps the data set path from starting is a JobNotRun that says so and names `--synthetic`: no log is left behind."""
+    import os
     if not synthetic:
-        raise job_helper.JobNotRun('This build covers the training step, not the dataset pipeline (datapipe/, cv2, dataset ZIPs are out of '
-              'scope and absent); run with --synthetic.')
+        if crop is None:
+            raise job_helper.JobNotRun('The data set path stages fixed-size crops on the device: give a --crop_size (whole-image '
+                                       'training batches are not built), or run with --synthetic.')
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise job_helper.JobNotRun('The data set path is single-GPU: start one process, or run with --synthetic '
+                                       '(which is what serves WORLD_SIZE > 1).')
+        from .datapipe import datasets
+        from . import settings as settings_mod
+        try:
+            return datasets.load_dataset(dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
+        except settings_mod.DataPathError as e:   # no configuration file / no `pascal_voc` path / directory missing
+            raise job_helper.JobNotRun('{} -- or run with --synthetic.'.format(e))
     if crop is None:
         raise ValueError('--synthetic needs a --crop_size')
-    return crop
+    return None
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -257,6 +270,124 @@ class SyntheticData(object):
                     evaluator.sample_logits(eval_net.forward_lowres(vx), vy, (self.H, self.W), ignore_value=255,
                                             align_corners=step.align_corners)
         return evaluate
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the data set path (Pascal VOC): what the reference's trainers do between `load_dataset` and `FINAL TEST`
+def augmenter_options(settings):
+    """The `--aug_*` options of a trainer (its `settings`) as the keyword arguments of device_pipeline.DeviceAugmenter."""
+    s = settings
+    return dict(scale_hung=s['aug_scale_hung'], scale_non_uniform=s['aug_scale_non_uniform'], hflip=s['aug_hflip'],
+                vflip=s['aug_vflip'], hvflip=s['aug_hvflip'], strong_colour=s['aug_strong_colour'],
+                brightness=s['aug_colour_brightness'], contrast=s['aug_colour_contrast'],
+                saturation=s['aug_colour_saturation'], hue=s['aug_colour_hue'], colour_prob=s['aug_colour_prob'],
+                greyscale_prob=s['aug_colour_greyscale_prob'], rot_mag=s['aug_rot_mag'], max_scale=s['aug_max_scale'])
+
+
+class DatasetRun(object):
+    """One trainer's run on the data set of `open_dataset`: every image decoded ONCE into an HBM-resident pool
+    (resident_pool.py), training crops and padded evaluation batches gathered on the device (device_pipeline.DeviceAugmenter),
+    batches drawn from the reference's index streams. The methods are called in the order a reference trainer does these things,
+    which is the order of its prints and of its draws from torch's global generator:
+
+        DatasetRun(...)  ->  iters_per_epoch  ->  make_streams  ->  print_sizes_and_start  ->  evaluate / finish
+    """
+
+    def __init__(self, ds_dict, torch_device, batch_size):
+        import time
+        from .resident_pool import ResidentPool
+        self.ds_src = ds_dict['ds_src']
+        self.val_ndx, self.test_ndx = ds_dict['val_ndx_tgt'], ds_dict['test_ndx_tgt']
+        self.sup_ndx, self.unsup_ndx = ds_dict['sup_ndx'], ds_dict['unsup_ndx']
+        self.n_classes = self.ds_src.num_classes
+        self.batch_size = batch_size
+        t0 = time.time()
+        self.pool = ResidentPool(self.ds_src, list(self.sup_ndx) + list(self.unsup_ndx) + list(self.val_ndx) +
+                                 (list(self.test_ndx) if self.test_ndx is not None else []), torch_device)
+        print('Resident pool: {} samples, {:.1f} MB in HBM, decoded in {:.1f}s'.format(
+            len(self.pool), self.pool.nbytes() / 1e6, time.time() - t0))
+
+    def iters_per_epoch(self, iters_per_epoch):
+        """`--iters_per_epoch -1` is len(unsup_ndx) // batch_size in all four reference trainers."""
+        if iters_per_epoch != -1:
+            return iters_per_epoch
+        if len(self.unsup_ndx) // self.batch_size == 0:
+            raise job_helper.JobNotRun('--iters_per_epoch -1 means len(unsup_ndx) // batch_size = {} // {} = 0 iterations per '
+                                       'epoch: give --iters_per_epoch or a smaller --batch_size.'.format(
+                                           len(self.unsup_ndx), self.batch_size))
+        return len(self.unsup_ndx) // self.batch_size
+
+    def make_streams(self, student_net, crop, dtype, settings, n_unsup_streams):
+        """The augmenter (statistics from the network, else the source; the reference seeds none of its numpy draws, neither does
+        this path) and the RepeatSampler(SubsetRandomSampler) index streams: the supervised one and `n_unsup_streams` (0, 1, or
+        the CutMix trainer's 2 that share one sampler) unsupervised ones. -> the augmenter"""
+        from .device_pipeline import DeviceAugmenter
+        from .datapipe import seg_data
+        mean, std = self.ds_src.get_mean_std()
+        mean = student_net.MEAN if student_net.MEAN is not None else mean
+        std = student_net.STD if student_net.STD is not None else std
+        self.student_net = student_net
+        self.augment = DeviceAugmenter(crop, mean, std, out_dtype=dtype, **augmenter_options(settings))
+        self._streams = [seg_data.repeat_stream(self.sup_ndx, self.batch_size)[0]]
+        if n_unsup_streams > 0:
+            stream_0, sampler = seg_data.repeat_stream(self.unsup_ndx, self.batch_size)
+            self._streams += [stream_0] + [seg_data.IndexStream(sampler, self.batch_size) for _ in range(n_unsup_streams - 1)]
+        return self.augment
+
+    def print_sizes_and_start(self, n_sup):
+        """The data set size prints, then the iterators in the reference's order: each draws its base seed from torch's global
+        generator here. -> [supervised iterator, unsupervised iterators...]"""
+        print('len(sup_ndx)={}'.format(len(self.sup_ndx)))
+        print('len(unsup_ndx)={}'.format(len(self.unsup_ndx)))
+        print('len(val_ndx)={}'.format(len(self.val_ndx)))
+        if self.test_ndx is not None:
+            print('len(test_ndx)={}'.format(len(self.test_ndx)))
+        if n_sup != -1:
+            print('sup_ndx={}'.format(self.sup_ndx.tolist()))
+        return [iter(st) for st in self._streams]
+
+    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None):
+        """The reference's evaluation loop over `ndx` in index order: whole images, centred on a padded canvas per batch
+        (stage_eval); padding carries label 255 and is ignored."""
+        import numpy as np
+        import torch
+        from . import ops
+        from .datapipe import seg_data
+        with torch.no_grad():
+            for batch_ndx in seg_data.eval_batches(ndx, self.batch_size):
+                ev = self.augment.stage_eval(self.pool, batch_ndx, self.student_net.BLOCK_SIZE)
+                logits = eval_net.forward_lowres(ev['image'])
+                if evaluator is not None:
+                    evaluator.sample_logits(logits, ev['labels'], ev['canvas'], ignore_value=255,
+                                            align_corners=step.align_corners)
+                if preds_dir is not None:
+                    _, pred = ops.argmax_confusion(logits, None, self.n_classes, ev['canvas'],
+                                                   align_corners=step.align_corners, want_pred=True)
+                    pred = pred.cpu().numpy()
+                    for k, sample_ndx in enumerate(batch_ndx):
+                        self.ds_src.save_prediction_by_index(preds_dir, pred[k].astype(np.uint32), sample_ndx)
+
+    def evaluate_with(self, eval_net, step):
+        """-> the `evaluate(evaluator)` of run_epochs over the validation set."""
+        return lambda evaluator: self.staged_eval(eval_net, step, self.val_ndx, evaluator)
+
+    def finish(self, eval_net, step, save_preds, submit_config, bin_fill_holes):
+        """After the last epoch: prediction files with `--save_preds` (the Pascal source inherits
+        DataSource.save_prediction_by_index), then the held-out test set and `FINAL TEST` when `--n_val` left one."""
+        import os
+        from . import evaluation
+        out_dir = None
+        eval_net.eval()
+        if save_preds:
+            out_dir = os.path.join(submit_config.run_dir, 'preds')
+            os.makedirs(out_dir, exist_ok=True)
+            self.staged_eval(eval_net, step, self.val_ndx, None, out_dir)
+        if self.test_ndx is not None:
+            test_iou_eval = evaluation.EvaluatorIoU(self.n_classes, bin_fill_holes)
+            self.staged_eval(eval_net, step, self.test_ndx, test_iou_eval, out_dir)
+            test_iou = test_iou_eval.score()
+            print('FINAL TEST: mIoU={:.3%}'.format(test_iou.mean()))
+            print('-- TEST {}'.format(', '.join(['{:.3%}'.format(x) for x in test_iou])))
 
 
 def print_settings(settings):

@@ -565,7 +565,11 @@ int cms_conv_pack_transpose_batch_f32(const cms_pack_item* items_dev, int n_item
  *      rotate + scale crop of datapipe/seg_transforms_cv.py:306-372 (cv2.warpAffine): output pixel (x, y) samples the
  *      source at (a00 x + a01 y + a02, a10 x + a11 y + a12) with slots 16..21 = a00 a01 a02 a10 a11 a12 (the INVERSE of
  *      the reference's local_xf), slot 22 = interpolation of the image (0 nearest: floor(s + 0.5); 1 bilinear), image
- *      border REFLECT_101, labels nearest with 255 outside, mask = in-bounds weight (constant border 0); 23 reserved
+ *      border REFLECT_101, labels nearest with 255 outside, mask = in-bounds weight (constant border 0)
+ *   23 mask mode (either geometry): 0 = the mask is the in-bounds weight of the image taps (cv2.INTER_LINEAR of the mask, what a
+ *      single view gets); 1 = the mask is 1 exactly when the NEAREST source pixel -- the one the labels are read from -- lies
+ *      inside the source, else 0 (cv2.INTER_NEAREST of the mask: view 1 of a Hung scale-crop PAIR, seg_transforms_cv.py:272).
+ *      The image and its zero padding do not depend on it.
  * out0 = geometric transform only (teacher view), out1 = + colour augmentation (student view); either may be NULL.
  * ------------------------------------------------------------------------------------------------------------ */
 #define CMS_AUG_PARAMS 24
