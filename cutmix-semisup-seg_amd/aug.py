@@ -9,7 +9,7 @@ train_seg_semisup_aug_mt.py:250-410, the classic mean teacher between two differ
     optimizer + EMA                                                                     :404-406
 
 What runs where: the network passes, the cross entropy and Adam/SGD + EMA are the MI355X kernels of the CutMix step (step.py);
-the warp and the loss are ONE pair of launches, the augmentation section of csrc/losses.hip (arithmetic in csrc/aug_math.hpp):
+the warp and the loss are ONE pair of launches, csrc/aug_loss.hip (arithmetic in csrc/aug_math.hpp):
 no F.affine_grid / F.grid_sample, no warped (N,C,H,W) tensor. The pair geometry (xf0_to_1) comes with the batch, as in the
 reference's loader; aug_pairs.py draws it for synthetic data.
 

@@ -1,5 +1,5 @@
 // Per-pixel arithmetic of the augmentation-consistency loss (the classic mean teacher between two differently augmented
-// views), shared by the kernels at the end of losses.hip and driven on the host by tests/hostcheck_aug. Same conventions as
+// views), shared by the kernels of aug_loss.hip and driven on the host by tests/hostcheck_aug. Same conventions as
 // pixel_math.hpp / ict_math.hpp: `__host__ __device__`, compile-time class count with the class axis in registers,
 // contraction off and explicit fmaf where two evaluations of the same expression must agree bit for bit (a pixel's target is
 // computed by the forward and the backward launch, from LDS or from global memory).

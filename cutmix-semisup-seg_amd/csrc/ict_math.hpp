@@ -1,5 +1,5 @@
-// Per-pixel arithmetic of the ICT (interpolation consistency training) loss, shared by the kernels at the end of
-// losses.hip and driven on the host by tests/hostcheck_ict. Same conventions as pixel_math.hpp: `__host__ __device__`,
+// Per-pixel arithmetic of the ICT (interpolation consistency training) loss, shared by the loss kernels of
+// ict.hip and driven on the host by tests/hostcheck_ict. Same conventions as pixel_math.hpp: `__host__ __device__`,
 // compile-time class count with the exponentials in registers, contraction off where two evaluations of the same
 // expression must agree bit for bit (the confidence of a pixel is computed by up to three launches).
 //

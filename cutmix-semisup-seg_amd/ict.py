@@ -10,7 +10,7 @@ train_seg_semisup_ict.py:249-403.
     optimizer + EMA                                                                     :397-399
 
 What runs where: the network passes, the cross entropy and Adam/SGD + EMA are the MI355X kernels of the CutMix step
-(step.py); the image blend and the interpolation loss are csrc/ict.hip and the ICT section of csrc/losses.hip. The validity
+(step.py); the image blend and the interpolation loss are both csrc/ict.hip (arithmetic in csrc/ict_math.hpp). The validity
 masks are blended inside the loss kernels (:311 never becomes a tensor). The mix factors are drawn on the host with the
 reference's own call (numpy's Beta sampler) and travel to the device as N floats.
 

@@ -97,20 +97,34 @@ def cutmix_paste(x0, x1, ranges=None, invert=True, mask=None, out=None):
 
 
 # ---------------------------------------------------------------------------------------------- consistency loss
-class ConsistencyConfig(object):
+class _LossConfig(object):
+    """What the three consistency losses share: the per-pixel loss function, the confidence threshold and its mode, the upsample."""
+
+    def __init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners):
+        if loss_fn not in _lib.LOSS_IDS:
+            raise ValueError('Unknown consistency loss function {}'.format(loss_fn))
+        self.loss_fn = loss_fn
+        self.conf_thresh = float(conf_thresh)
+        self.conf_per_pixel = bool(conf_per_pixel)
+        self.align_corners = bool(align_corners)
+
+    def fill(self, d):
+        """the shared fields of a loss descriptor"""
+        d.align_corners = int(self.align_corners)
+        d.loss_fn = _lib.LOSS_IDS[self.loss_fn]
+        d.conf_thresh = self.conf_thresh
+        d.conf_per_pixel = int(self.conf_per_pixel)
+
+
+class ConsistencyConfig(_LossConfig):
     """Static configuration of the unsupervised loss (train_seg_semisup_mask_mt.py CLI flags)."""
 
     def __init__(self, mode='mix', loss_fn='var', conf_thresh=0.97, conf_per_pixel=False, align_corners=True,
                  invert=True):
         if mode not in ('mix', 'cut'):
             raise ValueError('Unknown mask_mode {}'.format(mode))
-        if loss_fn not in _lib.LOSS_IDS:
-            raise ValueError('Unknown consistency loss function {}'.format(loss_fn))
+        _LossConfig.__init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners)
         self.mode = mode
-        self.loss_fn = loss_fn
-        self.conf_thresh = float(conf_thresh)
-        self.conf_per_pixel = bool(conf_per_pixel)
-        self.align_corners = bool(align_corners)
         self.invert = bool(invert)
 
 
@@ -132,14 +146,30 @@ def _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size):
     d.um1 = um1.data_ptr() if um1 is not None else None
     d.n, d.c, d.h, d.w = n, c, h, w
     d.H, d.W = int(out_size[0]), int(out_size[1])
-    d.align_corners = int(cfg.align_corners)
+    cfg.fill(d)
     d.n_boxes = int(ranges.shape[1]) if ranges is not None else 0
     d.invert = int(cfg.invert)
     d.mode = _lib.MODE_MIX if cfg.mode == 'mix' else _lib.MODE_CUT
-    d.loss_fn = _lib.LOSS_IDS[cfg.loss_fn]
-    d.conf_thresh = cfg.conf_thresh
-    d.conf_per_pixel = int(cfg.conf_per_pixel)
     return d
+
+
+def _workspace(name, d, device):
+    """uninitialised scratch of the size cms_<name>_workspace_bytes asks for"""
+    return torch.empty(max(int(fn['cms_{}_workspace_bytes'.format(name)](C.byref(d))), 16), dtype=torch.uint8, device=device)
+
+
+def _check_grad_out(who, grad_out, like):
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(like.shape) or not grad_out.is_contiguous():
+        raise ValueError('{}: grad_out must be a contiguous f32 tensor of the logits\' shape'.format(who))
+
+
+def _finalized_scalars(stats, stats_g, cfg, ramp_val, cons_weight):
+    """f32[4] [consistency_loss, conf_rate, grad_scale, unsup_loss] from the loss sums (`stats_g`: those of the global batch)"""
+    scalars = torch.empty(4, dtype=torch.float32, device=stats.device)
+    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats_g), cfg.conf_thresh, int(cfg.conf_per_pixel),
+                                         float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
+          'cms_consistency_finalize')
+    return scalars
 
 
 def _allreduce_sum(t, group):
@@ -150,6 +180,30 @@ def _allreduce_sum(t, group):
     return False
 
 
+def _cons_prepare(who, cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1, grad_out=None):
+    """The checks and conversions in front of a consistency launch: (descriptor, what the context keeps alive)."""
+    _need_cuda(l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, grad_out)
+    l_stu, l_tea0, l_tea1 = _f32c(l_stu), _f32c(l_tea0), _f32c(l_tea1)
+    mask, um0, um1 = _f32c(mask), _f32c(um0), _f32c(um1)
+    ranges = _nonempty_ranges(ranges)
+    if l_tea0.shape != l_stu.shape or (l_tea1 is not None and l_tea1.shape != l_stu.shape):
+        raise ValueError('consistency: student / teacher logits shapes differ')
+    if grad_out is not None:
+        _check_grad_out(who, grad_out, l_stu)
+    d = _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size)
+    return d, (l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, cfg, tuple(int(v) for v in out_size))
+
+
+def _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate):
+    """the finalised scalars, with the confidence count of the global batch under torch.distributed"""
+    stats_g = stats
+    if sync_conf_rate and cfg.conf_thresh > 0.0:
+        g = stats.clone()
+        if _allreduce_sum(g, group):
+            stats_g = g
+    return _finalized_scalars(stats, stats_g, cfg, ramp_val, cons_weight)
+
+
 def consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges=None, mask=None, um0=None, um1=None,
                         ramp_val=1.0, cons_weight=1.0, group=None, sync_conf_rate=True):
     """
@@ -157,28 +211,12 @@ def consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges=None, mask=
     [consistency_loss, conf_rate, grad_scale, unsup_loss]; ctx feeds consistency_backward. No host sync.
     Under torch.distributed the confidence count is all-reduced so that the rate is the global one.
     """
-    _need_cuda(l_stu, l_tea0, l_tea1, ranges, mask, um0, um1)
-    l_stu, l_tea0, l_tea1 = _f32c(l_stu), _f32c(l_tea0), _f32c(l_tea1)
-    mask, um0, um1 = _f32c(mask), _f32c(um0), _f32c(um1)
-    ranges = _nonempty_ranges(ranges)
-    if l_tea0.shape != l_stu.shape or (l_tea1 is not None and l_tea1.shape != l_stu.shape):
-        raise ValueError('consistency: student / teacher logits shapes differ')
-    d = _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size)
-    dev = l_stu.device
-    ws = torch.empty(max(int(fn['cms_consistency_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
+    d, keep = _cons_prepare('consistency_forward', cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1)
+    dev = keep[0].device
+    ws = _workspace('consistency', d, dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     check(fn['cms_consistency_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_consistency_fwd')
-    stats_g = stats
-    if sync_conf_rate and cfg.conf_thresh > 0.0:
-        g = stats.clone()
-        if _allreduce_sum(g, group):
-            stats_g = g
-    scalars = torch.empty(4, dtype=torch.float32, device=dev)
-    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats_g), cfg.conf_thresh, int(cfg.conf_per_pixel),
-                                         float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
-          'cms_consistency_finalize')
-    keep = (l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, cfg, tuple(int(v) for v in out_size))
-    return scalars, (d, keep, stats)
+    return _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate), (d, keep, stats)
 
 
 def consistency_backward(ctx, scalars, grad_out=None, samples=None):
@@ -208,36 +246,21 @@ def consistency_fused(cfg, l_stu, l_tea0, l_tea1, out_size, grad_out, ranges=Non
     scalars and ADDS d unsup_loss / d l_stu to `grad_out` (f32 (N,C,h,w), its rows must be ZERO on entry: the deferred scalar factor
     -- the confidence rate of the default mode, in which the gradient is linear -- is applied to the rows afterwards). Falls back to
     the two launches where the fused one does not exist (identity geometry, deterministic mode, CMS_LOSS_FUSED=0)."""
-    _need_cuda(l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, grad_out)
-    l_stu, l_tea0, l_tea1 = _f32c(l_stu), _f32c(l_tea0), _f32c(l_tea1)
-    mask, um0, um1 = _f32c(mask), _f32c(um0), _f32c(um1)
-    ranges = _nonempty_ranges(ranges)
-    if l_tea0.shape != l_stu.shape or (l_tea1 is not None and l_tea1.shape != l_stu.shape):
-        raise ValueError('consistency: student / teacher logits shapes differ')
-    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(l_stu.shape) or not grad_out.is_contiguous():
-        raise ValueError('consistency_fused: grad_out must be a contiguous f32 tensor of the logits\' shape')
-    d = _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size)
+    d, keep = _cons_prepare('consistency_fused', cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1, grad_out)
+    l_stu, l_tea0, l_tea1, ranges, mask, um0, um1 = keep[:7]
     if not fn['cms_consistency_fused_supported'](C.byref(d)):
         sc, cctx = consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1, ramp_val, cons_weight, group,
                                        sync_conf_rate)
         consistency_backward(cctx, sc, grad_out)
         return sc
     dev = l_stu.device
-    ws = torch.empty(max(int(fn['cms_consistency_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
+    ws = _workspace('consistency', d, dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     P = float(d.n) * float(d.H) * float(d.W)
     grad_unit = float(ramp_val) * float(cons_weight) / P
     check(fn['cms_consistency_fwd_bwd'](C.byref(d), grad_unit, _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()),
           'cms_consistency_fwd_bwd')
-    stats_g = stats
-    if sync_conf_rate and cfg.conf_thresh > 0.0:
-        g = stats.clone()
-        if _allreduce_sum(g, group):
-            stats_g = g
-    scalars = torch.empty(4, dtype=torch.float32, device=dev)
-    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats_g), cfg.conf_thresh, int(cfg.conf_per_pixel),
-                                         float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
-          'cms_consistency_finalize')
+    scalars = _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate)
     if cfg.conf_thresh > 0.0 and not cfg.conf_per_pixel:
         # default confidence mode (:415-418): the loss mask is the scalar RATE -- the factor the launch above left out
         check(fn['cms_scale_by_scalar'](_ptr(grad_out), grad_out.numel(), _ptr(scalars), 1, 1.0, _stream()), 'cms_scale_by_scalar')
@@ -300,16 +323,11 @@ def ict_blend(x0, x1, lam, out=None):
     return out
 
 
-class ICTConsistencyConfig(object):
+class ICTConsistencyConfig(_LossConfig):
     """Static configuration of the ICT loss (train_seg_semisup_ict.py CLI flags)."""
 
     def __init__(self, loss_fn='var', conf_thresh=0.97, conf_per_pixel=False, align_corners=True):
-        if loss_fn not in _lib.LOSS_IDS:
-            raise ValueError('Unknown consistency loss function {}'.format(loss_fn))
-        self.loss_fn = loss_fn
-        self.conf_thresh = float(conf_thresh)
-        self.conf_per_pixel = bool(conf_per_pixel)
-        self.align_corners = bool(align_corners)
+        _LossConfig.__init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners)
 
 
 def ict_consistency_forward(cfg, l_stu, l_tea0, l_tea1, lam, out_size, um0=None, um1=None, ramp_val=1.0, cons_weight=1.0):
@@ -333,21 +351,14 @@ def ict_consistency_forward(cfg, l_stu, l_tea0, l_tea1, lam, out_size, um0=None,
     d.um0 = um0.data_ptr() if um0 is not None else None
     d.um1 = um1.data_ptr() if um1 is not None else None
     d.n, d.c, d.h, d.w, d.H, d.W = n, c, h, w, H, W
-    d.align_corners = int(cfg.align_corners)
-    d.loss_fn = _lib.LOSS_IDS[cfg.loss_fn]
-    d.conf_thresh = cfg.conf_thresh
-    d.conf_per_pixel = int(cfg.conf_per_pixel)
+    cfg.fill(d)
     dev = l_stu.device
     # the workspace goes into the context: the backward reads the confidence map of --conf_per_pixel from it
-    ws = torch.empty(max(int(fn['cms_ict_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
+    ws = _workspace('ict', d, dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     check(fn['cms_ict_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_ict_fwd')
-    scalars = torch.empty(4, dtype=torch.float32, device=dev)
-    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats), cfg.conf_thresh, int(cfg.conf_per_pixel),
-                                         float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
-          'cms_consistency_finalize')
     keep = (l_stu, l_tea0, l_tea1, lam, um0, um1)
-    return scalars, (d, keep, ws, stats)
+    return _finalized_scalars(stats, stats, cfg, ramp_val, cons_weight), (d, keep, ws, stats)
 
 
 def ict_consistency_backward(ctx, scalars, grad_out=None):
@@ -355,8 +366,8 @@ def ict_consistency_backward(ctx, scalars, grad_out=None):
     d, keep, ws, _ = ctx
     if grad_out is None:
         grad_out = torch.zeros_like(keep[0])
-    elif grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(keep[0].shape) or not grad_out.is_contiguous():
-        raise ValueError('ict_consistency_backward: grad_out must be a contiguous f32 tensor of the logits\' shape')
+    else:
+        _check_grad_out('ict_consistency_backward', grad_out, keep[0])
     check(fn['cms_ict_bwd'](C.byref(d), _ptr(ws), _ptr(scalars), _ptr(grad_out), _stream()), 'cms_ict_bwd')
     return grad_out
 
@@ -386,17 +397,12 @@ def aug_pixel_matrices(xf0_to_1, out_size, device=None):
     return a
 
 
-class AugConsistencyConfig(object):
+class AugConsistencyConfig(_LossConfig):
     """Static configuration of the augmentation-consistency loss (train_seg_semisup_aug_mt.py CLI flags). `force_global`: never
     stage the teacher's rectangle in LDS (tests: both routes give the same bits)."""
 
     def __init__(self, loss_fn='var', conf_thresh=0.97, conf_per_pixel=False, align_corners=True, force_global=False):
-        if loss_fn not in _lib.LOSS_IDS:
-            raise ValueError('Unknown consistency loss function {}'.format(loss_fn))
-        self.loss_fn = loss_fn
-        self.conf_thresh = float(conf_thresh)
-        self.conf_per_pixel = bool(conf_per_pixel)
-        self.align_corners = bool(align_corners)
+        _LossConfig.__init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners)
         self.force_global = bool(force_global)
 
 
@@ -429,21 +435,14 @@ def aug_consistency_forward(cfg, l_stu, l_tea, xf0_to_1, out_size, um0=None, um1
     d.um0 = um0.data_ptr() if um0 is not None else None
     d.um1 = um1.data_ptr() if um1 is not None else None
     d.n, d.c, d.h, d.w, d.H, d.W = n, c, h, w, H, W
-    d.align_corners = int(cfg.align_corners)
-    d.loss_fn = _lib.LOSS_IDS[cfg.loss_fn]
-    d.conf_thresh = cfg.conf_thresh
-    d.conf_per_pixel = int(cfg.conf_per_pixel)
+    cfg.fill(d)
     d.force_global = int(cfg.force_global)
     dev = l_stu.device
-    ws = torch.empty(max(int(fn['cms_aug_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
+    ws = _workspace('aug', d, dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     check(fn['cms_aug_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_aug_fwd')
-    scalars = torch.empty(4, dtype=torch.float32, device=dev)
-    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats), cfg.conf_thresh, int(cfg.conf_per_pixel),
-                                         float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
-          'cms_consistency_finalize')
     keep = (l_stu, l_tea, xf, um0, um1)
-    return scalars, (d, keep, ws, stats)
+    return _finalized_scalars(stats, stats, cfg, ramp_val, cons_weight), (d, keep, ws, stats)
 
 
 def aug_consistency_backward(ctx, scalars, grad_out=None):
@@ -451,8 +450,8 @@ def aug_consistency_backward(ctx, scalars, grad_out=None):
     d, keep, _, _ = ctx
     if grad_out is None:
         grad_out = torch.zeros_like(keep[0])
-    elif grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(keep[0].shape) or not grad_out.is_contiguous():
-        raise ValueError('aug_consistency_backward: grad_out must be a contiguous f32 tensor of the logits\' shape')
+    else:
+        _check_grad_out('aug_consistency_backward', grad_out, keep[0])
     check(fn['cms_aug_bwd'](C.byref(d), _ptr(scalars), _ptr(grad_out), _stream()), 'cms_aug_bwd')
     return grad_out
 
@@ -475,39 +474,8 @@ def _ce_desc(logits, labels, ignore_index, out_size, align_corners):
     return d
 
 
-def ce_forward(logits, labels, out_size=None, ignore_index=255, align_corners=True, loss_weight=1.0, group=None,
-               sync_count=False):
-    """labels (N,H,W) uint8/int64. Returns (scalars f32[2] = [loss, grad_scale], ctx)."""
-    _need_cuda(logits, labels)
-    logits = _f32c(logits)
-    labels = labels.contiguous()
-    if labels.dim() == 4:
-        labels = labels[:, 0].contiguous()
-    if out_size is None:
-        out_size = labels.shape[1:3]
-    if tuple(labels.shape) != (logits.shape[0], int(out_size[0]), int(out_size[1])):
-        raise ValueError('ce: labels shape {} does not match (N,H,W)=({}, {}, {})'.format(
-            tuple(labels.shape), logits.shape[0], out_size[0], out_size[1]))
-    d = _ce_desc(logits, labels, ignore_index, out_size, align_corners)
-    dev = logits.device
-    ws = torch.empty(max(int(fn['cms_ce_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
-    stats = torch.empty(2, dtype=torch.float64, device=dev)
-    check(fn['cms_ce_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_ce_fwd')
-    if sync_count:
-        # exact global-batch semantics under data parallelism: divide by the mean valid count over ranks
-        import torch.distributed as dist
-        cnt = stats[1:2].clone()
-        if _allreduce_sum(cnt, group):
-            stats = torch.stack([stats[0], cnt[0] / dist.get_world_size(group)])
-    scalars = torch.empty(2, dtype=torch.float32, device=dev)
-    check(fn['cms_ce_finalize'](_ptr(stats), float(loss_weight), _ptr(scalars), _stream()), 'cms_ce_finalize')
-    return scalars, (d, (logits, labels), stats)
-
-
-def ce_fused(logits, labels, grad_out, out_size=None, ignore_index=255, align_corners=True, loss_weight=1.0, group=None,
-             sync_count=False):
-    """(round 6) `ce_forward` + `ce_backward` as ONE loss launch (cms_ce_fwd_bwd): returns the scalars f32[2] = [loss, grad_scale]
-    and ADDS the gradient to `grad_out` (f32 (N,C,h,w), rows ZERO on entry: the factor loss_weight / count is applied afterwards)."""
+def _ce_prepare(logits, labels, out_size, ignore_index, align_corners, grad_out=None):
+    """The checks and conversions in front of a cross-entropy launch: (descriptor, logits, labels)."""
     _need_cuda(logits, labels, grad_out)
     logits = _f32c(logits)
     labels = labels.contiguous()
@@ -518,24 +486,48 @@ def ce_fused(logits, labels, grad_out, out_size=None, ignore_index=255, align_co
     if tuple(labels.shape) != (logits.shape[0], int(out_size[0]), int(out_size[1])):
         raise ValueError('ce: labels shape {} does not match (N,H,W)=({}, {}, {})'.format(
             tuple(labels.shape), logits.shape[0], out_size[0], out_size[1]))
-    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != tuple(logits.shape) or not grad_out.is_contiguous():
-        raise ValueError('ce_fused: grad_out must be a contiguous f32 tensor of the logits\' shape')
-    d = _ce_desc(logits, labels, ignore_index, out_size, align_corners)
-    if not fn['cms_ce_fused_supported'](C.byref(d)):
-        sc, cctx = ce_forward(logits, labels, out_size, ignore_index, align_corners, loss_weight, group, sync_count)
-        ce_backward(cctx, sc, grad_out)
-        return sc
-    dev = logits.device
-    ws = torch.empty(max(int(fn['cms_ce_workspace_bytes'](C.byref(d))), 16), dtype=torch.uint8, device=dev)
-    stats = torch.empty(2, dtype=torch.float64, device=dev)
-    check(fn['cms_ce_fwd_bwd'](C.byref(d), _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()), 'cms_ce_fwd_bwd')
+    if grad_out is not None:
+        _check_grad_out('ce_fused', grad_out, logits)
+    return _ce_desc(logits, labels, ignore_index, out_size, align_corners), logits, labels
+
+
+def _ce_scalars(stats, loss_weight, group, sync_count):
+    """(scalars f32[2] = [loss, grad_scale], the loss sums they were finalised from)"""
     if sync_count:
+        # exact global-batch semantics under data parallelism: divide by the mean valid count over ranks
         import torch.distributed as dist
         cnt = stats[1:2].clone()
         if _allreduce_sum(cnt, group):
             stats = torch.stack([stats[0], cnt[0] / dist.get_world_size(group)])
-    scalars = torch.empty(2, dtype=torch.float32, device=dev)
+    scalars = torch.empty(2, dtype=torch.float32, device=stats.device)
     check(fn['cms_ce_finalize'](_ptr(stats), float(loss_weight), _ptr(scalars), _stream()), 'cms_ce_finalize')
+    return scalars, stats
+
+
+def ce_forward(logits, labels, out_size=None, ignore_index=255, align_corners=True, loss_weight=1.0, group=None,
+               sync_count=False):
+    """labels (N,H,W) uint8/int64. Returns (scalars f32[2] = [loss, grad_scale], ctx)."""
+    d, logits, labels = _ce_prepare(logits, labels, out_size, ignore_index, align_corners)
+    ws = _workspace('ce', d, logits.device)
+    stats = torch.empty(2, dtype=torch.float64, device=logits.device)
+    check(fn['cms_ce_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_ce_fwd')
+    scalars, stats = _ce_scalars(stats, loss_weight, group, sync_count)
+    return scalars, (d, (logits, labels), stats)
+
+
+def ce_fused(logits, labels, grad_out, out_size=None, ignore_index=255, align_corners=True, loss_weight=1.0, group=None,
+             sync_count=False):
+    """(round 6) `ce_forward` + `ce_backward` as ONE loss launch (cms_ce_fwd_bwd): returns the scalars f32[2] = [loss, grad_scale]
+    and ADDS the gradient to `grad_out` (f32 (N,C,h,w), rows ZERO on entry: the factor loss_weight / count is applied afterwards)."""
+    d, logits, labels = _ce_prepare(logits, labels, out_size, ignore_index, align_corners, grad_out)
+    if not fn['cms_ce_fused_supported'](C.byref(d)):
+        sc, cctx = ce_forward(logits, labels, out_size, ignore_index, align_corners, loss_weight, group, sync_count)
+        ce_backward(cctx, sc, grad_out)
+        return sc
+    ws = _workspace('ce', d, logits.device)
+    stats = torch.empty(2, dtype=torch.float64, device=logits.device)
+    check(fn['cms_ce_fwd_bwd'](C.byref(d), _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()), 'cms_ce_fwd_bwd')
+    scalars, _ = _ce_scalars(stats, loss_weight, group, sync_count)
     check(fn['cms_scale_by_scalar'](_ptr(grad_out), grad_out.numel(), _ptr(scalars), 1, 1.0, _stream()), 'cms_scale_by_scalar')
     return scalars
 

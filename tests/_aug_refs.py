@@ -128,7 +128,7 @@ def rot_scale_theta(deg, scale, tx=0.0, ty=0.0):
 
 
 # ---- tile facts: which route (teacher rectangle staged in LDS / gathered from global memory) the kernels take -----------------
-# A restatement of the host-side capacity rule of csrc/losses.hip (aug_tea_cap, fwd_tiles, tile_lds_bytes) and of the
+# A restatement of the host-side capacity rule of csrc/aug_loss.hip and csrc/loss_tiles.hpp (aug_tea_cap, fwd_tiles, tile_lds_bytes) and of the
 # per-workgroup decision (aug_tile_patch + aug_fits). The tile's box of teacher pixels comes from the product's own
 # aug_tile_box through tests/hostcheck_aug (`hc`), the rest is restated here with numpy float32 arithmetic.
 TILE_W, FWD_TILE_H, BWD_TILE_H = 64, 8, 4

@@ -312,7 +312,7 @@ def tile_lds_bytes(C, sy, sx, n_patches):
 
 
 def tile_facts(C, h, w, H, W, ac, n_patches):
-    """What the host side of csrc/losses.hip decides for a geometry, from fp32 taps. n_patches = 3 (consistency) or 1 (CE)."""
+    """What the host side of csrc/loss_tiles.hpp decides for a geometry, from fp32 taps. n_patches = 3 (consistency) or 1 (CE)."""
     sy, sx = _scale(h, H, ac), _scale(w, W, ac)
     i0, i1, _, _ = R.bilinear_taps(w, W, ac, np.float32)
     y0, y1, _, _ = R.bilinear_taps(h, H, ac, np.float32)
@@ -371,6 +371,11 @@ GEOS = {
     'c60':      (1, 60, 41, 41, 321, 321, True, 52, False, dict(loop='table', backward='tiled_optin', forward='tiled')),
     'near1':    (1, 21, 60, 60, 65, 65, True, 6, True, dict(loop='compare', backward='tiled_optin', forward='direct')),
     'toobig':   (1, 32, 60, 60, 65, 65, True, 1, False, dict(loop='compare', backward='error', forward='direct', fused=False)),
+    # the identity kernels (forward and backward, both losses) with a run-time class count; two tile columns' worth of pixels
+    'identc3':  (2, 3, 9, 70, 9, 70, True, 1, False, dict(loop='compare', backward='identity', forward='identity', fused=False)),
+    # the direct-gather forward of the CROSS ENTROPY (one rectangle: 46 x 9 x 62 floats = 100 KB > 96 KB), which only a run-time
+    # class count reaches; its backward and fused launch are tiled (147 KB). No consistency backward at this size (three rectangles)
+    'ce46':     (1, 46, 60, 60, 64, 64, True, 2, False, dict(loop='compare', backward='error', forward='direct', fused=False)),
 }
 # the dyadic geometries of the exact cases (C = 4, logits_var): every bilinear weight is a multiple of 2^-6
 EXACT_GEOS = {

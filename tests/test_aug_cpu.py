@@ -316,11 +316,19 @@ def test_gpu_geometries_reach_the_routes_they_are_meant_to(hc):
     tests/_aug_refs.py on the product's own aug_tile_box: which route each geometry of tests/test_gpu_aug.py takes."""
     from cutmix_semisup_seg_amd import ops
     import test_gpu_aug as gpu
+    assert {g['C'] for g in gpu.GEOS.values() if g['lo'] == g['hi']} == {2, 3}     # identity kernels: compile-time and run-time C
     for name, g in sorted(gpu.GEOS.items()):
         if g['lo'] == g['hi']:
             assert refs.tea_capacity(g['C'], g['lo'], g['hi'], g['ac'], False) is None      # identity geometry: the direct kernels
             continue
         xf = ops.aug_pixel_matrices(np.asarray(g['theta']), g['hi']).numpy()
+        if name == 'direct_rt':
+            # the student's rectangle alone is beyond the forward limit: the direct forward kernel (run-time C); the backward is
+            # tiled with what G, R and the student's rectangle leave for the teacher's -- too little for any of these tiles
+            assert g['C'] not in (2, 5, 19, 21) and refs.tea_capacity(g['C'], g['lo'], g['hi'], g['ac'], False) is None
+            f = refs.tile_facts(hc, xf, g['C'], g['lo'], g['hi'], g['ac'], True)
+            assert 0 < f['cap'] < 32 * 1024 // 4 and f['staged'] == 0 and f['global_'] > 0, (name, f)
+            continue
         for backward in (False, True):
             f = refs.tile_facts(hc, xf, g['C'], g['lo'], g['hi'], g['ac'], backward)
             assert f['cap'] == 32 * 1024 // 4                       # nothing else limits the capacity at these sizes

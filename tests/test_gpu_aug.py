@@ -33,6 +33,10 @@ R = refs.rot_scale_theta
 #   ident      h == H, w == W (the U-Nets): the direct kernels without upsampling, C = 2
 #   fallback   64 x 64 from 60 x 60 with 21 classes, 45 degrees: the teacher's rectangle of a tile exceeds the capacity, the
 #              taps are gathered from global memory (tests/test_aug_cpu.py asserts the route of every geometry here)
+#   direct_rt  64 x 64 from 60 x 60 with 46 (run-time) classes: the student's forward rectangle (46 x 9 x 62 floats = 100 KB)
+#              exceeds the 96 KB limit of the LDS-staged forward, which then gathers from global memory; the backward runs
+#              with 147 KB of LDS and 9 KB left for the teacher's rectangle. Four samples: 46 classes leave few confident pixels
+#   ident_rt   the identity kernels with a run-time class count, C = 3
 THREE = [R(8, 1.0, 0.06, -0.04), R(-33, 1.3, 0.0, 0.0), R(12, 0.9, 0.8, -0.7)]
 GEOS = {
     'tiles_align': dict(N=3, C=21, lo=(9, 19), hi=(70, 150), ac=True, theta=THREE, seed=29),
@@ -41,6 +45,8 @@ GEOS = {
     'c7': dict(N=3, C=7, lo=(6, 7), hi=(41, 50), ac=False, theta=THREE, seed=2),
     'ident': dict(N=2, C=2, lo=(24, 40), hi=(24, 40), ac=True, theta=[R(8, 1.0, 0.06, -0.04), R(-33, 1.3, 0.6, -0.5)], seed=1),
     'fallback': dict(N=2, C=21, lo=(60, 60), hi=(64, 64), ac=True, theta=[R(45, 1.0), R(45, 1.2, 0.7, 0.6)], seed=0),
+    'direct_rt': dict(N=4, C=46, lo=(60, 60), hi=(64, 64), ac=True, theta=THREE + [R(45, 1.2, 0.7, 0.6)], seed=3),
+    'ident_rt': dict(N=2, C=3, lo=(24, 40), hi=(24, 40), ac=True, theta=[R(8, 1.0, 0.06, -0.04), R(-33, 1.3, 0.6, -0.5)], seed=0),
 }
 ALL_LOSSES_AT = ('tiles_align', 'tiles_noalign', 'c5')
 

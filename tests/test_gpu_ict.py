@@ -25,13 +25,16 @@ DEV = 'cuda:0'
 TAU = 0.6
 MODES = {'default': (TAU, False), 'per_pixel': (TAU, True), 'no_thresh': (0.0, False)}
 
-# Tiles of the loss kernels (csrc/losses.hip): TILE_W = 64 columns; 8 rows in the forward, 4 in the backward.
+# Tiles of the loss kernels (csrc/loss_tiles.hpp): TILE_W = 64 columns; 8 rows in the forward, 4 in the backward.
 #   tiles      70 x 150 from 9 x 19: 3 tile columns (64 + 64 + 22) x 9 forward / 18 backward tile rows, the last ones partial
 #              (6 of 8 and 2 of 4 rows), compile-time C = 21, both align_corners
 #   c5 / c7    41 x 50 from 6 x 7: one partial tile column, compile-time C = 5 and run-time C = 7
 #   ident      h == H, w == W (the U-Nets): the direct kernels without upsampling, C = 2
 #   direct     64 x 64 from 60 x 60 with 21 classes: the forward rectangles (3 x 21 x 9 x 62 floats = 140 KB) exceed the 96 KB limit
 #              of the LDS-staged forward, which then gathers from global memory; the backward runs with 120 KB of LDS
+#   direct_rt  the same route with a run-time class count: one sample, C = 16 (3 x 16 x 9 x 62 floats = 105 KB)
+#   ident_rt   the identity kernels with a run-time class count, C = 3
+#              (tests/test_ict_cpu.py asserts the route of every geometry here)
 GEOS = {
     'tiles_align': dict(N=3, C=21, lo=(9, 19), hi=(70, 150), ac=True, lam=[0.0, 1.0, 0.37], seed=56),
     'tiles_noalign': dict(N=3, C=21, lo=(9, 19), hi=(70, 150), ac=False, lam=[0.81, 0.05, 0.5], seed=14),
@@ -39,6 +42,8 @@ GEOS = {
     'c7': dict(N=3, C=7, lo=(6, 7), hi=(41, 50), ac=False, lam=[0.37, 0.0, 1.0], seed=1),
     'ident': dict(N=2, C=2, lo=(24, 40), hi=(24, 40), ac=True, lam=[0.0, 0.63], seed=6),
     'direct': dict(N=2, C=21, lo=(60, 60), hi=(64, 64), ac=True, lam=[1.0, 0.2], seed=1),
+    'direct_rt': dict(N=1, C=16, lo=(60, 60), hi=(64, 64), ac=True, lam=[0.37], seed=0),
+    'ident_rt': dict(N=2, C=3, lo=(24, 40), hi=(24, 40), ac=True, lam=[0.0, 0.63], seed=0),
 }
 
 

@@ -119,7 +119,7 @@ def test_exact_gradient_on_dyadic_geometries(ops, name, mode, route):
 
 
 # ------------------------------------------------------------------------------------------------------------ bounded cases
-_CASES = [(n, c) for n in L.GEOS if n != 'toobig' for c in L.combos_of(n)]
+_CASES = [(n, c) for n in L.GEOS if L.GEOS[n][9]['backward'] != 'error' for c in L.combos_of(n)]     # (not 'toobig', 'ce46')
 
 
 @pytest.mark.parametrize('route', ROUTES)

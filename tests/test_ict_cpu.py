@@ -135,3 +135,22 @@ def test_ict_step_refuses_data_parallel_runs(monkeypatch):
     monkeypatch.setenv('WORLD_SIZE', '2')
     with pytest.raises(RuntimeError, match='one GPU'):
         ict.ICTMeanTeacherStep(None, None, None, None, ict.ICTConfig())
+
+
+def test_gpu_geometries_reach_the_routes_they_are_meant_to():
+    """Which forward / backward kernels each geometry of tests/test_gpu_ict.py runs (three staged rectangles, as the consistency:
+    tests/_loss_refs.tile_facts), with a compile-time (2, 5, 19, 21) and a run-time class count on every route."""
+    import _loss_refs as L
+    import test_gpu_ict as gpu
+    want = {'tiles_align': 'tiled', 'tiles_noalign': 'tiled', 'c5': 'tiled', 'c7': 'tiled', 'ident': 'identity',
+            'ident_rt': 'identity', 'direct': 'direct', 'direct_rt': 'direct'}
+    assert sorted(want) == sorted(gpu.GEOS)
+    seen = set()
+    for name, g in gpu.GEOS.items():
+        f = L.tile_facts(g['C'], g['lo'][0], g['lo'][1], g['hi'][0], g['hi'][1], g['ac'], 3)
+        assert f['forward'].replace('_optin', '') == want[name], (name, f)
+        assert f['backward'].replace('_optin', '') == ('identity' if want[name] == 'identity' else 'tiled'), (name, f)
+        seen.add((want[name], g['C'] in (2, 5, 19, 21)))
+    assert seen == {(r, ct) for r in ('tiled', 'identity', 'direct') for ct in (True, False)}
+    f = L.tile_facts(16, 60, 60, 64, 64, True, 3)
+    assert f['fwd_lds'] == 3 * 16 * 9 * 62 * 4 > L.FWD_PATCH_LDS_MAX >= L.tile_facts(14, 60, 60, 64, 64, True, 3)['fwd_lds']

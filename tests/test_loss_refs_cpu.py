@@ -161,6 +161,9 @@ def test_the_paths_of_the_issue_table():
     t3, t1 = F('toobig', 3), F('toobig', 1)
     assert t3['lds'] == 181632 > L.LDS_MAX and not t3['fused'] and t3['forward'] == 'direct' and t3['backward'] == 'error'
     assert t1['lds'] == 103552 and t1['fused'] and t1['backward'] == 'tiled_optin'
+    c1 = F('ce46', 1)
+    assert c1['fwd_lds'] == 46 * 9 * 62 * 4 > L.FWD_PATCH_LDS_MAX and c1['forward'] == 'direct' and c1['backward'] == 'tiled_optin' and c1['fused']
+    assert F('identc3', 1)['forward'] == F('identc3', 1)['backward'] == 'identity' and not F('identc3', 1)['fused']
     # class counts: the compile-time 2, 5, 19, 21 and generic ones, C = 1 among them
     assert {2, 5, 19, 21, 1, 3, 4, 40, 60, 32} <= {g[1] for g in L.GEOS.values()}
 

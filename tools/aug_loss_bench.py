@@ -1,5 +1,5 @@
-"""The fused affine-warp consistency loss (ops.aug_consistency_forward + aug_consistency_backward: csrc/aug_math.hpp, the
-augmentation section of csrc/losses.hip) at the Pascal configuration's geometry -- logits 10 x 21 x 41 x 41, loss at 321 x 321 --
+"""The fused affine-warp consistency loss (ops.aug_consistency_forward + aug_consistency_backward: csrc/aug_math.hpp,
+csrc/aug_loss.hip) at the Pascal configuration's geometry -- logits 10 x 21 x 41 x 41, loss at 321 x 321 --
 against the same loss written with torch ops on the device: materialised bilinear upsamples, F.affine_grid, three F.grid_sample
 calls, two softmaxes, the masked mean and autograd back to the low-resolution student logits (train_seg_semisup_aug_mt.py:302-398
 as the reference runs it). Per-sample warps: rotations within +-30 degrees, scales within 1/1.5 .. 1.5 (seeded).

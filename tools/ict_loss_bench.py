@@ -1,5 +1,5 @@
-"""The fused ICT loss (ops.ict_consistency_forward + ict_consistency_backward: csrc/ict_math.hpp, the ICT section of
-csrc/losses.hip) at the Pascal configuration's geometry -- logits 10 x 21 x 41 x 41, loss at 321 x 321 -- against the same loss
+"""The fused ICT loss (ops.ict_consistency_forward + ict_consistency_backward: csrc/ict_math.hpp,
+csrc/ict.hip) at the Pascal configuration's geometry -- logits 10 x 21 x 41 x 41, loss at 321 x 321 -- against the same loss
 written with torch ops on the device: materialised bilinear upsamples of the three logit tensors, three softmaxes, the blends, the
 masked mean and autograd back to the low-resolution student logits (train_seg_semisup_ict.py:320-391 as the reference runs it).
 Both legs run in one process, alternated round by round after warm-up; a leg's time is the host clock around `calls` forward +
