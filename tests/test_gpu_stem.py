@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _stem_refs as S
 import _stream_refs as R
 
 pytestmark = pytest.mark.gpu
@@ -45,10 +46,16 @@ def test_stem_forward_pool_and_backward(ops, shape, dtype):
     s = ops.stem_forward(cu(x.to(dtype)), w147, cu(scale), cu(bias), dtype)
     tol = 1e-5 if dtype == torch.float32 else 1e-2
     torch.testing.assert_close(s.float().cpu().permute(0, 3, 1, 2), s_ref.float().detach(), rtol=tol, atol=tol)
+    # ... and on every element within the derived bound of the plain fp64 reference (tests/_stem_refs.py; bf16 = the matrix cores)
+    bf = dtype == torch.bfloat16
+    tag = '{} {}x{}x{} (test_gpu_stem)'.format('bf16' if bf else 'fp32', N, H, W)
+    xn, wn, scn = x.numpy(), _pack49(w).numpy(), scale.numpy()
+    f_ref, f_A = S.stem_forward(xn, wn, scn, bias.numpy())
+    R.assert_within(s.double().cpu().numpy(), f_ref, S.forward_bound(f_A, f_ref, bf, mfma=bf), 'stem_fwd ' + tag)
     p, idx = ops.maxpool3x3s2_forward(s)
     # the pool is exact on whatever the stem produced
     assert torch.equal(p.float().permute(0, 3, 1, 2), F.max_pool2d(s.float().permute(0, 3, 1, 2), 3, 2, 1, ceil_mode=True))
-    if dtype != torch.float32:
+    if bf:
         # bf16 ties move the argmax away from the fp64 graph's: route dp by the kernel's OWN index map (tests/_stream_refs.py) --
         # independent of the tie rule -- and gate by s > 0. <= 4 window gradients summed in fp32 (d = 3), one bf16 rounding.
         dpn = dp.permute(0, 2, 3, 1).contiguous().to(dtype)
@@ -59,17 +66,27 @@ def test_stem_forward_pool_and_backward(ops, shape, dtype):
         ref = R.maxpool3x3s2_relu_backward(dpn.double().numpy(), idn, sn)
         A = R.maxpool3x3s2_relu_backward(dpn.double().abs().numpy(), idn, sn)
         R.assert_within(ds.double().cpu().numpy(), ref, R.bound(A, 3, ref, bf16_out=True), 'maxpool_bwd bf16 (test_gpu_stem)')
-        return
-    ds = ops.maxpool3x3s2_relu_backward(cu(dp.permute(0, 2, 3, 1).contiguous()), idx, s)
-    # d loss / d (conv * scale + bias) from the reference graph
-    ds_ref = torch.autograd.grad(p_ref, s_ref, dp.double(), retain_graph=True)[0] * (s_ref > 0)
-    torch.testing.assert_close(ds.cpu().permute(0, 3, 1, 2), ds_ref.float(), rtol=1e-5, atol=1e-6)
-    dw = torch.full((49, 64, 3), 0.25, device=DEV)
-    ops.stem_wgrad(cu(x), ds, dw, cu(scale))
-    want = _pack49(wd.grad.float()) + 0.25
-    assert float((dw.cpu() - want).abs().max()) <= 2e-4 * float(want.abs().max()) + 1e-5
+    else:
+        ds = ops.maxpool3x3s2_relu_backward(cu(dp.permute(0, 2, 3, 1).contiguous()), idx, s)
+        # d loss / d (conv * scale + bias) from the reference graph
+        ds_ref = torch.autograd.grad(p_ref, s_ref, dp.double(), retain_graph=True)[0] * (s_ref > 0)
+        torch.testing.assert_close(ds.cpu().permute(0, 3, 1, 2), ds_ref.float(), rtol=1e-5, atol=1e-6)
+    # weight and data gradient of the kernel's OWN dS (bf16 dS on the bf16 engine: stem_wgrad_mfma_kernel, stem_dgrad_kernel<bf16>),
+    # element-wise against tests/_stem_refs.py with the bounds of tests/test_gpu_stem_kernels.py (d: S.wgrad_depth, S.dgrad_bound)
+    dsn = ds.float().cpu().numpy()
+    dw = torch.full((49, 64, 3), S.PREFILL, device=DEV)
+    ops.stem_wgrad(cu(x.to(dtype)), ds, dw, cu(scale))
+    plan = S.wgrad_plan(bf, bf, N, H, W)
+    w_ref, w_A = S.stem_wgrad(xn, dsn, scn)
+    R.assert_within(dw.double().cpu().numpy(), S.PREFILL + w_ref, S.wgrad_bound(w_A, S.PREFILL, plan), 'stem_wgrad ' + tag)
     dx = ops.stem_dgrad(ds, w147, cu(scale), x.shape)
-    assert float((dx.cpu() - xd.grad.float()).abs().max()) <= 1e-4 * float(xd.grad.abs().max()) + 1e-6
+    d_ref, d_A, taps = S.stem_dgrad(dsn, wn, scn, (H, W))
+    R.assert_within(dx.double().cpu().numpy(), d_ref, S.dgrad_bound(d_A, taps), 'stem_dgrad ' + tag)
+    if not bf:
+        # the whole-tensor figures against the autograd graph, as before
+        want = _pack49(wd.grad.float()) + 0.25
+        assert float((dw.cpu() - want).abs().max()) <= 2e-4 * float(want.abs().max()) + 1e-5
+        assert float((dx.cpu() - xd.grad.float()).abs().max()) <= 1e-4 * float(xd.grad.abs().max()) + 1e-6
 
 
 def test_network_runs_without_library_convolutions(ops):
