@@ -122,6 +122,10 @@ class StageDesc(C.Structure):
                 ('n', c_int), ('n_entries', c_int), ('h', c_int), ('w', c_int), ('out_dtype', c_int)]
 
 
+class PdPatch(C.Structure):
+    _fields_ = [('img_off', C.c_longlong), ('hs', c_int), ('ws', c_int), ('cy', c_int), ('cx', c_int)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('scale', c_void_p),
                 ('ntaps', c_int), ('cout', c_int), ('cin', c_int), ('first_block', c_int)]
@@ -261,6 +265,16 @@ PROTOTYPES = {
     'cms_conv_wgrad_f32': (c_int, [_P(WgradDesc), c_void_p]),
     'cms_conv_pack_transpose_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'cms_conv_pack_transpose_batch_f32': (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    'cms_fft2': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'cms_pd_load_image': (c_int, [c_void_p, _P(StageEntry), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'cms_pd_load_patches': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cms_pd_patch_sqdiff': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cms_pd_spectrum_product': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cms_pd_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+    'cms_select_workspace_bytes': (c_size_t, [c_int]),
+    'cms_select_k_smallest': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, C.c_longlong, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
 }
 
 fn = {}

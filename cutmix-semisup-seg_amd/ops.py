@@ -1064,6 +1064,117 @@ def fill_holes(pred, out=None, truth=None, ignore_index=None, cm=None):
     return out, cm
 
 
+# ---------------------------------------------------------------------------------------------- fp64 FFT / patch distances
+_TWIDDLES = {}
+
+
+def fft_twiddles(n, device):
+    """exp(-2 pi i k / n), k < n / 2, built on the host in float64 and cached per (length, device): complex128 CUDA (n / 2,)"""
+    key = (int(n), str(device))
+    if key not in _TWIDDLES:
+        k = np.arange(n // 2, dtype=np.float64)
+        _TWIDDLES[key] = torch.from_numpy(np.exp(-2j * np.pi * k / n).astype(np.complex128)).to(device)
+    return _TWIDDLES[key]
+
+
+def fft_size(n):
+    """the FFT length that serves a padded extent n: the smallest power of two >= max(8, n), at most 4096"""
+    n = int(n)
+    size = 8
+    while size < n:
+        size *= 2
+    if size > 4096:
+        raise ValueError('fft_size: an extent of {} needs an FFT longer than 4096, which is not built'.format(n))
+    return size
+
+
+def fft2(x, inverse=False):
+    """2-D FFT over the last two axes of a contiguous complex128 CUDA (B, FH, FW) tensor, IN PLACE (csrc/fft.hip); power-of-two
+    lengths 8 ... 4096; the inverse is scaled by 1 / (FH * FW). Returns x."""
+    _need_cuda(x)
+    if x.dtype != torch.complex128 or x.dim() != 3 or not x.is_contiguous():
+        raise TypeError('fft2: a contiguous complex128 (B, FH, FW) tensor is required')
+    b, fh, fw = (int(v) for v in x.shape)
+    check(fn['cms_fft2'](_ptr(x), b, fh, fw, int(bool(inverse)), _ptr(fft_twiddles(fh, x.device)), _ptr(fft_twiddles(fw, x.device)),
+                         _stream()), 'cms_fft2')
+    return x
+
+
+def pd_load_image(pool_img, entry, patch_shape, fft_shape, planes, sq=None):
+    """pool entry (a _lib.StageEntry on the host) -> planes complex128 (3, FH, FW), sq int64 (Hs + ph - 1, Ws + pw - 1)"""
+    _need_cuda(pool_img, planes, sq)
+    check(fn['cms_pd_load_image'](_ptr(pool_img), C.byref(entry), int(patch_shape[0]), int(patch_shape[1]), int(fft_shape[0]),
+                                  int(fft_shape[1]), _ptr(planes), _ptr(sq), _stream()), 'cms_pd_load_image')
+
+
+def pd_load_patches(pool_img, patches, n, patch_shape, fft_shape, planes):
+    """patches: CUDA uint8 table of n cms_pd_patch -> planes complex128 ((n + 1) // 2, 3, FH, FW), flipped and packed in pairs"""
+    _need_cuda(pool_img, patches, planes)
+    check(fn['cms_pd_load_patches'](_ptr(pool_img), _ptr(patches), int(n), int(patch_shape[0]), int(patch_shape[1]), int(fft_shape[0]),
+                                    int(fft_shape[1]), _ptr(planes), _stream()), 'cms_pd_load_patches')
+
+
+def pd_patch_sqdiff(pool_img, a, b, n, patch_shape):
+    """int64 (n,): sum over each patch of (a - b)^2, or of a^2 with b None"""
+    _need_cuda(pool_img, a, b)
+    out = torch.empty((int(n),), dtype=torch.int64, device=pool_img.device)
+    check(fn['cms_pd_patch_sqdiff'](_ptr(pool_img), _ptr(a), _ptr(b), int(n), int(patch_shape[0]), int(patch_shape[1]), _ptr(out),
+                                    _stream()), 'cms_pd_patch_sqdiff')
+    return out
+
+
+def pd_spectrum_product(f_img, f_pairs, out):
+    _need_cuda(f_img, f_pairs, out)
+    check(fn['cms_pd_spectrum_product'](_ptr(f_img), _ptr(f_pairs), int(f_pairs.shape[0]), int(f_img.shape[-2]), int(f_img.shape[-1]),
+                                        _ptr(out), _stream()), 'cms_pd_spectrum_product')
+    return out
+
+
+def pd_finish(corr, p2, q2, residual_bits, d2=None, keys=None):
+    """corr complex128 (pairs, FH, FW), p2 int64 (H, W), q2 int64 (n,) -> d2 (n, H, W) and / or keys (n, H * W); residual_bits:
+    int64 (1,), max-accumulates the bit pattern of the largest |re - rint(re)|"""
+    _need_cuda(corr, p2, q2, residual_bits, d2, keys)
+    check(fn['cms_pd_finish'](_ptr(corr), _ptr(p2), _ptr(q2), int(q2.shape[0]), int(p2.shape[0]), int(p2.shape[1]), int(corr.shape[-2]),
+                              int(corr.shape[-1]), _ptr(d2), _ptr(keys), _ptr(residual_bits), _stream()), 'cms_pd_finish')
+
+
+def select_k_smallest(keys, k, mask=None, labels=None, cls=None, inter=False):
+    """
+    The k smallest candidate keys of each row of `keys` (int64 CUDA (N, M), non-negative, distinct within a row), by a radix select
+    on the device; the <= k survivors are then sorted. Candidates: `mask` (N, M) bool / uint8, or `labels` uint8 (M,) with `cls`
+    int32 (N,): label == cls[row], or with `inter` label != cls[row] and label != 255.
+    Returns (sorted int64 (N, k) with INT64_MAX past each row's count, int32 (N,) counts).
+    """
+    _need_cuda(keys, mask, labels, cls)
+    if keys.dtype != torch.int64 or keys.dim() != 2 or not keys.is_contiguous():
+        raise TypeError('select_k_smallest: keys must be a contiguous int64 (N, M) tensor')
+    n, m = int(keys.shape[0]), int(keys.shape[1])
+    k = int(k)
+    if k < 1:
+        raise ValueError('select_k_smallest: k must be positive')
+    if mask is not None:
+        if labels is not None or cls is not None:
+            raise ValueError('select_k_smallest: give a mask, or labels and cls')
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (n, m):
+            raise TypeError('select_k_smallest: mask must be bool / uint8 of the shape of keys')
+        mask, mode = mask.contiguous(), 0
+    else:
+        if labels is None or cls is None:
+            raise ValueError('select_k_smallest: give a mask, or labels and cls')
+        if labels.dtype != torch.uint8 or labels.numel() != m or cls.dtype != torch.int32 or cls.numel() != n:
+            raise TypeError('select_k_smallest: labels uint8 (M,) and cls int32 (N,) required')
+        labels, cls, mode = labels.contiguous(), cls.contiguous(), 2 if inter else 1
+    out = torch.empty((n, k), dtype=torch.int64, device=keys.device)
+    count = torch.empty((n,), dtype=torch.int32, device=keys.device)
+    nbytes = int(fn['cms_select_workspace_bytes'](n))
+    ws = torch.empty((nbytes // 8 + 1,), dtype=torch.int64, device=keys.device)
+    check(fn['cms_select_k_smallest'](_ptr(keys), _ptr(mask), _ptr(labels), _ptr(cls), mode, n, m, k, _ptr(out), _ptr(count), _ptr(ws),
+                                      nbytes, _stream()), 'cms_select_k_smallest')
+    return torch.sort(out, dim=1).values, torch.clamp(count, max=k)
+
+
 # ---------------------------------------------------------------------------------------------- BatchNorm (batch stats)
 def _world(group):
     import torch.distributed as dist

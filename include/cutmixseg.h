@@ -834,6 +834,61 @@ int cms_program_set_timing(cms_program* p, int every_k);
 int cms_program_read_timing(cms_program* p, double* sum_ms, double* sum_flops, long* launches, double* head_ms,
                             long* head_launches);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Batched 2-D complex fp64 FFT (csrc/fft.hip), the transform under the patch-distance analysis below.
+ *   data   (batch, fh, fw) interleaved complex128, transformed IN PLACE; fh, fw powers of two in 8 ... 4096, batch <= 65535
+ *   tw_h, tw_w   DEVICE tables of fh / 2 and fw / 2 complex128: exp(-2 pi i k / n), built by the caller in float64 (the same
+ *          table serves both directions; one table may be passed twice when fh == fw)
+ *   inverse != 0: the inverse transform, scaled by 1 / (fh * fw)
+ * Two stream-ordered launches (rows, then tiles of adjacent columns), both with their data in LDS.
+ * ------------------------------------------------------------------------------------------------------------ */
+int cms_fft2(void* data, int batch, int fh, int fw, int inverse, const void* tw_h, const void* tw_w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Patch distances (csrc/patchdist.hip): patch_dist.py:107-154 sliding_window_distance_to_patch[es_generator] and
+ * intra_inter_class_patch_dist.py:186-211, on exact integer grey levels. For a (ph, pw, 3) patch Q[n] and an image symmetric-padded
+ * by ((ph - 1) / 2, (pw - 1) / 2) (numpy's `symmetric`: the edge pixel repeats, any number of reflections):
+ *     D2[n,i,j] = P2[i,j] + Q2[n] - 2 PQ[n,i,j]       PQ = the `valid` cross-correlation, from the fp64 FFT, rounded to integers
+ * ph, pw odd; FFT sizes fh >= hs + ph - 1, fw >= ws + pw - 1 as cms_fft2 takes them. The call sequence per image and chunk of n
+ * patches: load_image, load_patches, cms_fft2 on both, spectrum_product, cms_fft2 inverse, finish, select_k_smallest.
+ *   cms_pd_load_image      pool entry (uint8 [hs][ws][3] at pool_img + entry_host->img_off; entry_host is a HOST pointer) ->
+ *                          planes (3, fh, fw) complex128: the padded image, imaginary part and everything past it zero;
+ *                          sq (hs + ph - 1, ws + pw - 1) int64 = sum over channels of the padded image squared, or NULL
+ *   cms_pd_load_patches    patches[n] = where patch n is cut: the pool entry and the centre (cy, cx) in it (cut from the padded
+ *                          entry, so any centre inside the entry is valid) -> planes ((n + 1) / 2, 3, fh, fw) complex128: pair k
+ *                          holds patch 2k FLIPPED in the real part and patch 2k + 1 flipped in the imaginary part (zero when
+ *                          n is odd and 2k + 1 == n), so that F_image * F_pair needs no conjugate
+ *   cms_pd_patch_sqdiff    out[n] = sum over the patch of (a[n] - b[n])^2, or of a[n]^2 when b is NULL (that is Q2), int64
+ *   cms_pd_spectrum_product out (n_pairs, fh, fw) = sum over the 3 channels of f_img[c] * f_pairs[k][c]
+ *   cms_pd_finish          corr = the inverse transform of that product; p2 (h, w) int64 box sums of sq; q2 (n) ->
+ *                          d2 (n, h, w) int64 and / or keys (n, h * w) int64 = D2 << 24 | flat index (h * w <= 2^24);
+ *                          *residual_bits = max(*residual_bits, bit pattern of the largest |re - rint(re)| of the launch): the
+ *                          caller zeroes it, and refuses the result when the value is not far below 0.5 (NaN if not finite)
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct cms_pd_patch {
+    long long img_off;          /* byte offset of the patch's pool entry in pool_img                */
+    int hs, ws;                 /* size of that entry                                               */
+    int cy, cx;                 /* centre of the patch in it                                        */
+} cms_pd_patch;
+int cms_pd_load_image(const uint8_t* pool_img, const cms_stage_entry* entry_host, int ph, int pw, int fh, int fw, void* planes,
+                      int64_t* sq, void* stream);
+int cms_pd_load_patches(const uint8_t* pool_img, const cms_pd_patch* patches, int n, int ph, int pw, int fh, int fw, void* planes,
+                        void* stream);
+int cms_pd_patch_sqdiff(const uint8_t* pool_img, const cms_pd_patch* a, const cms_pd_patch* b, int n, int ph, int pw, int64_t* out,
+                        void* stream);
+int cms_pd_spectrum_product(const void* f_img, const void* f_pairs, int n_pairs, int fh, int fw, void* out, void* stream);
+int cms_pd_finish(const void* corr, const int64_t* p2, const int64_t* q2, int n, int h, int w, int fh, int fw, int64_t* d2,
+                  int64_t* keys, uint64_t* residual_bits, void* stream);
+/* The k smallest masked keys of each of n rows of m non-negative int64 keys (radix select: eight 8-bit histogram passes find the
+ * k-th key, one pass compacts the keys <= it; no sort). The candidates of row r are, by `mode`:
+ *     0  mask[r][i] != 0 (mask (n, m) uint8)      1  labels[i] == cls[r]      2  labels[i] != cls[r] and labels[i] != 255
+ * (labels (m) uint8 shared by every row, cls (n) int32). out (n, k) int64: the selected keys of a row in NO particular order, the
+ * rest of the row INT64_MAX; count[r] = how many (min(k, candidates) when the keys of a row are distinct). workspace:
+ * cms_select_workspace_bytes(n) bytes. */
+size_t cms_select_workspace_bytes(int n);
+int cms_select_k_smallest(const int64_t* keys, const uint8_t* mask, const uint8_t* labels, const int32_t* cls, int mode, int n,
+                          long long m, int k, int64_t* out, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
