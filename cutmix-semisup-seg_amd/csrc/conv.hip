@@ -62,15 +62,13 @@ struct ConvArgs {
     int relu, mode;            // mode 0 = forward epilogue, 1 = dgrad epilogue
     int M;                     // N*Ho*Wo
     int ksplit;                // > 1: the taps are split across workgroups, fp32 output accumulated with atomics
-    int dbg;                   // profiling experiments only: 2 = skip the MFMA phase, 3 = skip the loads after the first
+    int plain;                 // 1x1, stride 1, tap (0, 0), output grid == input grid: GEMM row m IS input and output pixel m
+                               // (the 18th int, so that the tap tables start 8-byte aligned: 4 bytes earlier, the statistics
+                               // instantiation of conv_igemm_mixed_kernel spills a VGPR -- profiles/conv_variants_retired.md)
     short tap_dy[CMS_CONV_MAX_TAPS], tap_dx[CMS_CONV_MAX_TAPS];
     uint32_t* trace;        // diagnostic (variant 30): per-workgroup s_memtime stamps, CONV_TRACE_DWORDS each, or NULL
     int trace_wgs;          // workgroups the trace buffer holds
-    int stagger;            // != 0: co-resident workgroups of the first dispatch round start 1/4 K-step period apart (24 / 25)
     int n_main, rem_tile_base;   // conv_igemm_mixed_kernel: workgroups of the main tile shape, first pixel tile of the rest
-    int krot;               // != 0: workgroup (tile_m) starts its K loop krot * tile_m steps in and wraps (variant 20)
-    int plain;              // 1x1, stride 1, tap (0, 0), output grid == input grid: GEMM row m IS input and output pixel m
-    int nt_store;           // bf16 output rows as non-temporal stores (CMS_CONV_NT, A/B: streaming stores evicting re-read operands)
     uint8_t* mask_bits_out;       // forward + ReLU: bit (pixel, channel) = [y > 0], [out pixels][Cout / 8] bytes, or NULL
     const uint8_t* mask_bits;     // dgrad: the ReLU mask as such bits instead of mask_src, or NULL
     float* stats_out;             // [pixel tiles][2 slots][2][Cout] per-tile (sum, sum of squares) of the stored output, or NULL
@@ -84,8 +82,8 @@ struct ConvArgs {
 
 
 // Branch-free pointer select for the direct-to-LDS loads: `ok ? p : z` written as a ternary makes the compiler
-// duplicate the (side-effecting) load into both arms of a divergent branch, i.e. up to two load instructions where
-// the counted s_waitcnt of the ring kernels expects exactly one.
+// duplicate the (side-effecting) load into both arms of a divergent branch, i.e. up to two load instructions per row
+// piece instead of one.
 __device__ __forceinline__ const uint16_t* select_ptr(bool ok, const uint16_t* p, const uint16_t* z) {
     const uint64_t a = (uint64_t)p, b = (uint64_t)z;
     const uint64_t m = (uint64_t)0 - (uint64_t)ok;
@@ -123,8 +121,8 @@ struct RowInfo {            // one per pixel row of the workgroup tile, computed
 // The loads are issued from INLINE ASSEMBLY, on purpose: hipcc counts a direct-to-LDS load it knows about (the
 // __builtin_amdgcn_*_load_lds forms) as a pending LDS WRITE that any later ds_read may alias, and puts
 // `s_waitcnt vmcnt(0)` in front of the first LDS read that follows it in program order -- with more than one stage in
-// flight that drains the whole pipeline every K step (seen in the ISA of every stage-ring variant of rounds 1 and 2,
-// which is why none of them ever beat the single-stage kernel). Loads issued from asm are invisible to that
+// flight (the weight-gradient kernels below) that drains the whole pipeline every K step. Loads issued from asm are
+// invisible to that
 // bookkeeping; completion is counted by the kernels' own `s_waitcnt vmcnt(N)` statements + barrier.
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 struct buf_rsrc_t { i32x4_t w; };
@@ -150,22 +148,6 @@ __device__ __forceinline__ void buf_load_lds16(const buf_rsrc_t& r, const unsign
                    "s"(__builtin_amdgcn_readfirstlane((int)soff))
                  : "memory");
 }
-// four of them: LDS destinations lds + k * step (k = 0..3)
-__device__ __forceinline__ void buf_load_lds16_x4(const buf_rsrc_t& r, const unsigned char* lds, uint32_t step, uint32_t v0,
-                                                  uint32_t v1, uint32_t v2, uint32_t v3, uint32_t soff) {
-    unsigned keep;
-    const uint32_t l0 = lds_addr_of(lds);
-    asm volatile("s_mov_b32 %0, m0\n\t"
-                 "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %9, %10 offen lds\n\t"
-                 "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %9, %10 offen lds\n\t"
-                 "s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %7, %9, %10 offen lds\n\t"
-                 "s_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %8, %9, %10 offen lds\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(l0), "s"(l0 + step), "s"(l0 + 2 * step), "s"(l0 + 3 * step), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(r.w),
-                   "s"(soff)
-                 : "memory");
-}
 // flat form, 4 bytes per lane (64 floats per wave instruction)
 __device__ __forceinline__ void glds4_asm(const void* gsrc, const void* lds) {
     unsigned keep;
@@ -176,59 +158,44 @@ __device__ __forceinline__ void glds4_asm(const void* gsrc, const void* lds) {
 }
 #else
 __device__ __forceinline__ void buf_load_lds16(const buf_rsrc_t&, const unsigned char*, uint32_t, uint32_t) {}
-__device__ __forceinline__ void buf_load_lds16_x4(const buf_rsrc_t&, const unsigned char*, uint32_t, uint32_t, uint32_t, uint32_t,
-                                                  uint32_t, uint32_t) {}
 __device__ __forceinline__ void glds4_asm(const void*, const void*) {}
 #endif
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_lds() {
-    // this wave's direct-to-LDS loads except the N youngest have landed; LDS reads of the previous phase are done
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
-// OCC = workgroups per CU the register budget is declared for (0: the round-1 defaults). PF = the fragment reads of
-// K sub-step kk+1 are issued BEFORE the MFMAs of sub-step kk (register double buffer): without it every sub-step is
-// "4 ds_read_b128 -> s_waitcnt lgkmcnt(0) -> 4 MFMAs", i.e. the LDS latency of each sub-step is exposed to the wave.
+// conv_body<WN, WM, TN, TM, GLDS, BUFA, ST>: one workgroup of WN x WM waves, each wave TN x TM MFMA tiles of 32 x 32, i.e.
+// a tile of WN*TN*32 output channels x WM*TM*32 pixels, walked in K steps of CONV_BK = 64 elements through ONE LDS stage.
+// GLDS = false: register-staged loader (global -> registers -> ds_write; the next step's global loads are in flight
+// during the MFMA phase). GLDS = true: the direct-to-LDS loader described above, load -> barrier -> MFMA -> barrier;
+// memory and MFMA phases overlap ACROSS the (up to 4) workgroups of a CU. (Stage rings, two-stage loaders, 32-element
+// stages and a fragment register double buffer were all measured and none was faster: docs/DESIGN_HISTORY.md 4.1.)
 // BUFA = the direct-to-LDS loads use buffer addressing (buffer_load_dwordx4 ... offen lds): descriptor in SGPRs, one
 // 32-bit byte offset per lane and row piece (rewritten once per TAP), the K position in a scalar offset -- a K step then
 // issues its 8 pieces per wave with NO vector ALU instruction (the flat-address form spends ~5 per piece on 64-bit
 // pointer arithmetic, which tools/conv_trace.py shows as a 700..1450-cycle issue phase). Padding and rows past M are
-// out-of-range offsets: the hardware bounds check writes zeros, no zero page.
+// out-of-range offsets: the hardware bounds check writes zeros, no zero page. BUFA = false (flat 64-bit addresses) is
+// what tensors of 2 GB and more take.
 // The kernel body is a device function of (logical block id, number of blocks, first pixel tile), so that ONE launch
 // can run two tile shapes (conv_igemm_mixed_kernel below).
 // ST = the store loop can also take BatchNorm statistics (ConvArgs.stats_out, tile_stats.hpp): separate instantiations of the
 // default tiles, so that the statistics' ~40 registers cost the plain kernels nothing (the 32-channel tile went from 6 to 4
 // workgroups per CU with the code folded in).
-template <int WN, int WM, int TN, int TM, bool GLDS, int NS, int BK = CONV_BK, bool PF = false, int OCC = 0, bool BUFA = false,
-          bool ST = false>
+template <int WN, int WM, int TN, int TM, bool GLDS, bool BUFA = false, bool ST = false>
 __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, const int nblk_in, const int m_tile_base) {
-    // NS = LDS stages of the direct-to-LDS loader. 1: load -> barrier -> MFMA -> barrier; memory and MFMA phases only
-    // overlap ACROSS the (up to 4) workgroups of a CU. 2: the loads of K-step k+1 are in flight during the MFMAs of
-    // step k inside one workgroup -- what the DeepLab shapes need, whose grids are only ~2 workgroups per CU.
     constexpr int NW = WN * WM;         // waves per workgroup (4 or 8)
     constexpr int NT = 64 * NW;
     constexpr int BN = WN * TN * 32;    // output channels per workgroup
     constexpr int BM = WM * TM * 32;    // pixels per workgroup
-    // BK = K elements per stage. 64: 128-byte LDS rows (8 chunks of 16 B, swizzle (row>>1)&7). 32: 64-byte rows
-    // (4 chunks, swizzle (row>>2)&3) -- two stages of it fit the LDS footprint of one 64-wide stage, i.e. the loads of
-    // step k+1 overlap the MFMAs of step k WITHOUT giving up the 4 workgroups per CU.
-    constexpr int ROWB = BK * 2;        // LDS row pitch (bytes)
-    constexpr int CH = BK / 8;          // 16-byte chunks per row
-    constexpr int LRPI = 64 / CH;       // rows per wave-wide direct-to-LDS instruction (8 or 16)
-    constexpr int WSH = CH == 8 ? 1 : 2;                 // rows per 256-byte bank window = 1 << WSH
-    static_assert(BK == 64 || (BK == 32 && GLDS), "BK = 32 only with the direct-to-LDS loader");
-    constexpr int PA = BM / (LRPI * NW);   // loader passes over the pixel tile
-    constexpr int PB = BN / (LRPI * NW);
+    // LDS rows are CONV_ROW_BYTES = 128 bytes: 8 chunks of 16 B, swizzle (row >> 1) & 7; a wave-wide direct-to-LDS
+    // instruction fills 8 rows
+    constexpr int PA = BM / (8 * NW);   // loader passes over the pixel tile
+    constexpr int PB = BN / (8 * NW);
     static_assert(NW == 4 || NW == 8, "4 or 8 waves");
     static_assert(BM <= NT && PA >= 1 && PB >= 1, "tile too small for the loader");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int STAGE_BYTES = (BM + BN) * ROWB;
+    constexpr int STAGE_BYTES = (BM + BN) * CONV_ROW_BYTES;
     constexpr int EPI_BYTES = BM * BN * 2;                // epilogue tile (bf16 output / staged residual or mask)
-    static_assert(NS == 1 || (NS >= 2 && NS <= 4 && GLDS), "stage rings only with the direct-to-LDS loader");
-    constexpr int UNION_BYTES = NS * STAGE_BYTES > EPI_BYTES ? NS * STAGE_BYTES : EPI_BYTES;
-    unsigned char* lds_x = smem;                          // [NS][BM][128 B]   (stage s at + s * STAGE_BYTES)
-    unsigned char* lds_w = smem + BM * ROWB;              // [NS][BN][128 B]
+    constexpr int UNION_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
+    unsigned char* lds_x = smem;                          // [BM][128 B]
+    unsigned char* lds_w = smem + BM * CONV_ROW_BYTES;    // [BN][128 B]
     short* lds_tap = reinterpret_cast<short*>(smem + UNION_BYTES);                       // [2][CMS_CONV_MAX_TAPS]
     RowInfo* lds_row = reinterpret_cast<RowInfo*>(smem + UNION_BYTES + 80);              // [BM]
     float* lds_sb = reinterpret_cast<float*>(smem + UNION_BYTES + 80 + BM * 16);         // [2][BN]: BN scale, bias of the tile
@@ -273,7 +240,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
     // needs no division, the loader no table, and the first stage is issued BEFORE the tables are written; the first
     // barrier of the K loop publishes them (tools/conv_trace.py: 2100 cycles of table arithmetic + 1100 of barrier and
     // geometry + 1200 of tap offsets stood in front of the first load of every workgroup)
-    const bool plain = GLDS && BUFA && NS == 1 && a.plain != 0;
+    const bool plain = GLDS && BUFA && a.plain != 0;
     if (tid < BM) {
         const int m = m0 + tid;
         RowInfo ri;
@@ -339,13 +306,13 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
     }
 #pragma unroll
     for (int i = 0; i < PB; ++i) {
-        const int row = GLDS ? (NW * i + wave) * LRPI + lane / CH : lrow + RSTEP * i;
-        const int c = GLDS ? ((lane % CH) ^ ((row >> WSH) & (CH - 1))) : chunk;
+        const int row = GLDS ? (NW * i + wave) * 8 + lane / 8 : lrow + RSTEP * i;
+        const int c = GLDS ? ((lane % 8) ^ ((row >> 1) & 7)) : chunk;
         woff[i] = (uint32_t)(row * a.Cin + c * 8) * (BUFA ? 2u : 1u);     // elements (bytes under buffer addressing)
     }
     const uint32_t st_off = swz(lrow, chunk);            // rows lrow + RSTEP*i share the swizzle term (RSTEP % 16 == 0)
 
-    const int kc_per_tap = a.Cin / BK;
+    const int kc_per_tap = a.Cin / CONV_BK;
     const int taps_per_split = (a.ntaps + a.ksplit - 1) / a.ksplit;
     const int tap_begin = split * taps_per_split;
     const int tap_end = min(a.ntaps, tap_begin + taps_per_split);
@@ -353,10 +320,10 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
     const int ksteps = tap_end * kc_per_tap;        // exclusive end of this workgroup's K range
 
     u32x4 rx[GLDS ? 1 : PA], rw[GLDS ? 1 : PB];
-    auto load_tile = [&](int ks, int) {        // register-staged loader only (the direct-to-LDS cursor is below)
+    auto load_tile = [&](int ks) {             // register-staged loader only (the direct-to-LDS cursor is below)
         if constexpr (!GLDS) {
             const int tap = ks / kc_per_tap;                                  // wave-uniform
-            const int c0 = (ks - tap * kc_per_tap) * BK;
+            const int c0 = (ks - tap * kc_per_tap) * CONV_BK;
             const int dy = __builtin_amdgcn_readfirstlane((int)lds_tap[tap]);
             const int dx = __builtin_amdgcn_readfirstlane((int)lds_tap[CMS_CONV_MAX_TAPS + tap]);
             const int delta = (dy * a.W + dx) * a.Cin + c0;                   // scalar element offset of this tap / K chunk
@@ -394,32 +361,18 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
     uint32_t soff_x = 0, soff_w = 0;                 // BUFA: scalar byte offsets (K position; tap and channel tile of W)
     const buf_rsrc_t rsrc_x = make_buf_rsrc(a.x, BUFA ? a.N * a.H * a.W * a.Cin * 2 : 0);
     const buf_rsrc_t rsrc_w = make_buf_rsrc(a.w, BUFA ? a.ntaps * a.Cout * a.Cin * 2 : 0);
-    if (a.stagger != 0) {
-        // the first 1024 workgroups start at the same instant, 4 per CU, and would run their load and MFMA phases in
-        // lockstep; dispatch is round-robin over 8 XCDs x 32 CUs, so blockIdx / 256 is the slot on the CU
-        const int slot = (blockIdx.x >> 8) & 3;
-        for (int i = 0; i < slot; ++i) __builtin_amdgcn_s_sleep(27);
-    }
     int cur_tap = tap_begin, cur_kc = 0;
-    if (a.krot != 0 && ksteps > ks_begin) {
-        // K rotation: workgroups of different pixel tiles walk the (tap, chunk) sequence from different starting
-        // points, so at any instant they request DIFFERENT weight lines from L2 (fp32 accumulation: the sum only
-        // changes its order)
-        const int r = (int)(((unsigned)tile_m * (unsigned)a.krot) % (unsigned)(ksteps - ks_begin));
-        cur_tap = tap_begin + r / kc_per_tap;
-        cur_kc = r - (r / kc_per_tap) * kc_per_tap;
-    }
-    auto setup_tap = [&]() {
+    auto setup_tap = [&]() {                         // at K chunk 0 of cur_tap
         if constexpr (BUFA) {
             // (one formula for the scalar offsets on both paths: a value merged from two branches is no longer provably
             // wave-uniform for the "s" operand of the inline-asm loads)
-            soff_x = (uint32_t)(cur_kc * BK * 2);
-            soff_w = (uint32_t)((((cur_tap * a.Cout + co0) * a.Cin) + cur_kc * BK) * 2);
+            soff_x = 0;
+            soff_w = (uint32_t)(((cur_tap * a.Cout + co0) * a.Cin) * 2);
             if (plain) {                       // no table read: nothing here depends on the (not yet published) LDS tables
 #pragma unroll
                 for (int i = 0; i < PA; ++i) {
-                    const int row = (NW * i + wave) * LRPI + lane / CH;
-                    const int c = (lane % CH) ^ ((row >> WSH) & (CH - 1));
+                    const int row = (NW * i + wave) * 8 + lane / 8;
+                    const int c = (lane % 8) ^ ((row >> 1) & 7);
                     const int m = m0 + row;
                     xvoff[i] = m < a.M ? (uint32_t)(m * a.Cin + c * 8) * 2u : 0x80000000u;
                 }
@@ -429,8 +382,8 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
                 const int delta = (dy * a.W + dx) * a.Cin;                     // scalar element offset of this tap
 #pragma unroll
                 for (int i = 0; i < PA; ++i) {
-                    const int row = (NW * i + wave) * LRPI + lane / CH;
-                    const int c = (lane % CH) ^ ((row >> WSH) & (CH - 1));
+                    const int row = (NW * i + wave) * 8 + lane / 8;
+                    const int c = (lane % 8) ^ ((row >> 1) & 7);
                     const RowInfo ri = lds_row[row];
                     const uint32_t iy = (ri.yx >> 16) + (uint32_t)dy, ix = (ri.yx & 0xffffu) + (uint32_t)dx;
                     const bool ok = iy < (uint32_t)a.H && ix < (uint32_t)a.W;    // unsigned compare covers the negative side
@@ -442,51 +395,53 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
         const int dy = __builtin_amdgcn_readfirstlane((int)lds_tap[cur_tap]);
         const int dx = __builtin_amdgcn_readfirstlane((int)lds_tap[CMS_CONV_MAX_TAPS + cur_tap]);
         const int delta = (dy * a.W + dx) * a.Cin;                     // scalar element offset of this tap
-        wt = a.w + ((size_t)cur_tap * a.Cout + co0) * a.Cin + cur_kc * BK;   // scalar base (cur_kc != 0 only when rotated)
+        wt = a.w + ((size_t)cur_tap * a.Cout + co0) * a.Cin;           // scalar base
 #pragma unroll
         for (int i = 0; i < ((GLDS && !BUFA) ? PA : 0); ++i) {
-            const int row = (NW * i + wave) * LRPI + lane / CH;
-            const int c = (lane % CH) ^ ((row >> WSH) & (CH - 1));
+            const int row = (NW * i + wave) * 8 + lane / 8;
+            const int c = (lane % 8) ^ ((row >> 1) & 7);
             const RowInfo ri = lds_row[row];
             const uint32_t iy = (ri.yx >> 16) + (uint32_t)dy, ix = (ri.yx & 0xffffu) + (uint32_t)dx;
             const bool ok = iy < (uint32_t)a.H && ix < (uint32_t)a.W;    // unsigned compare covers the negative side
             xaddr[i] = select_ptr(ok, a.x + (size_t)(ri.in_off + (uint32_t)(c * 8) + (uint32_t)delta),
-                                  a.zeros + (lane & 7) * 8) + cur_kc * BK;
+                                  a.zeros + (lane & 7) * 8);
         }
     };
-    auto issue_loads = [&](int buf) {
+    auto issue_loads = [&]() {
         if constexpr (BUFA) {
 #pragma unroll
             for (int i = 0; i < PA; ++i)
-                buf_load_lds16(rsrc_x, lds_x + buf * STAGE_BYTES + (NW * i + wave_s) * 1024, xvoff[i], soff_x);
+                buf_load_lds16(rsrc_x, lds_x + (NW * i + wave_s) * 1024, xvoff[i], soff_x);
 #pragma unroll
             for (int i = 0; i < PB; ++i)
-                buf_load_lds16(rsrc_w, lds_w + buf * STAGE_BYTES + (NW * i + wave_s) * 1024, woff[i], soff_w);
+                buf_load_lds16(rsrc_w, lds_w + (NW * i + wave_s) * 1024, woff[i], soff_w);
             return;
         }
 #pragma unroll
         for (int i = 0; i < ((GLDS && !BUFA) ? PA : 0); ++i)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)xaddr[i],
-                                             (__attribute__((address_space(3))) void*)(lds_x + buf * STAGE_BYTES + (NW * i + wave_s) * 1024),
+                                             (__attribute__((address_space(3))) void*)(lds_x + (NW * i + wave_s) * 1024),
                                              16, 0, 0);
 #pragma unroll
         for (int i = 0; i < (GLDS ? PB : 0); ++i)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wt + woff[i]),
-                                             (__attribute__((address_space(3))) void*)(lds_w + buf * STAGE_BYTES + (NW * i + wave_s) * 1024),
+                                             (__attribute__((address_space(3))) void*)(lds_w + (NW * i + wave_s) * 1024),
                                              16, 0, 0);
     };
     auto advance = [&]() {
         if constexpr (BUFA) {
-            soff_x += BK * 2;
-            soff_w += BK * 2;
+            soff_x += CONV_BK * 2;
+            soff_w += CONV_BK * 2;
         } else {
-            wt += BK;
+            wt += CONV_BK;
 #pragma unroll
-            for (int i = 0; i < (GLDS ? PA : 0); ++i) xaddr[i] += BK;
+            for (int i = 0; i < (GLDS ? PA : 0); ++i) xaddr[i] += CONV_BK;
         }
         if (++cur_kc == kc_per_tap) {
+            // (no wrap: the K loop calls advance() only in front of the loads of a step ks + 1 < ksteps, so the cursor
+            // never moves past the last chunk of tap tap_end - 1)
             cur_kc = 0;
-            if (++cur_tap == tap_end) cur_tap = tap_begin;       // wraps only under K rotation (else this is past the last step)
+            ++cur_tap;
             setup_tap();
         }
     };
@@ -502,48 +457,19 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
     // fragment read address: row (lane & 31) of a 32-row tile, 16-byte chunk (kk*2 + lane>>5) ^ swizzle(row)
     //   = lane_frag ^ (kk * 32)   (the K sub-step only flips bits 5..6)
     const int frow = lane & 31, fhalf = lane >> 5;
-    const uint32_t lane_frag = (uint32_t)frow * ROWB | (uint32_t)(((fhalf ^ (frow >> WSH)) & (CH - 1)) << 4);
-    const unsigned char* fw_base = lds_w + wn * TN * 32 * ROWB;
-    const unsigned char* fx_base = lds_x + wm * TM * 32 * ROWB;
+    const uint32_t lane_frag = (uint32_t)frow * CONV_ROW_BYTES | (uint32_t)(((fhalf ^ (frow >> 1)) & 7) << 4);
+    const unsigned char* fw_base = lds_w + wn * TN * 32 * CONV_ROW_BYTES;
+    const unsigned char* fx_base = lds_x + wm * TM * 32 * CONV_ROW_BYTES;
 
-    auto mfma_phase = [&](int buf) {
-        if constexpr (PF) {
-            // register double buffer over the K sub-steps: reads of kk+1 in flight during the MFMAs of kk
-            constexpr int KK = BK / 16;
-            u32x4 fw[2][TN], fx[2][TM];
-            auto frag_read = [&](int kk, u32x4* w_, u32x4* x_) {
-                const uint32_t fo = (lane_frag ^ (uint32_t)(kk * 32)) + (uint32_t)(buf * STAGE_BYTES);
+    auto mfma_phase = [&]() {
 #pragma unroll
-                for (int i = 0; i < TN; ++i) w_[i] = *reinterpret_cast<const u32x4*>(fw_base + fo + i * 32 * ROWB);
-#pragma unroll
-                for (int j = 0; j < TM; ++j) x_[j] = *reinterpret_cast<const u32x4*>(fx_base + fo + j * 32 * ROWB);
-            };
-            frag_read(0, fw[0], fx[0]);
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) {
-                if (kk + 1 < KK) frag_read(kk + 1, fw[(kk + 1) & 1], fx[(kk + 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);           // keep the reads of kk+1 in front of the MFMAs of kk
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int i = 0; i < TN; ++i)
-#pragma unroll
-                    for (int j = 0; j < TM; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[kk & 1][i]),
-                                                                            __builtin_bit_cast(bf16x8, fx[kk & 1][j]),
-                                                                            acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_s_setprio(0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            return;
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK / 16; ++kk) {
+        for (int kk = 0; kk < CONV_BK / 16; ++kk) {
             u32x4 fw[TN], fx[TM];     // (arrays of __bf16 vectors are not promoted to registers by the compiler)
-            const uint32_t fo = (lane_frag ^ (uint32_t)(kk * 32)) + (uint32_t)(buf * STAGE_BYTES);
+            const uint32_t fo = lane_frag ^ (uint32_t)(kk * 32);
 #pragma unroll
-            for (int i = 0; i < TN; ++i) fw[i] = *reinterpret_cast<const u32x4*>(fw_base + fo + i * 32 * ROWB);
+            for (int i = 0; i < TN; ++i) fw[i] = *reinterpret_cast<const u32x4*>(fw_base + fo + i * 32 * CONV_ROW_BYTES);
 #pragma unroll
-            for (int j = 0; j < TM; ++j) fx[j] = *reinterpret_cast<const u32x4*>(fx_base + fo + j * 32 * ROWB);
+            for (int j = 0; j < TM; ++j) fx[j] = *reinterpret_cast<const u32x4*>(fx_base + fo + j * 32 * CONV_ROW_BYTES);
 #pragma unroll
             for (int i = 0; i < TN; ++i)
 #pragma unroll
@@ -557,57 +483,9 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
             stamp(14);                                     // barrier passed, loader geometry / accumulators set up
             setup_tap();
             stamp(15);                                     // first tap's offsets computed
-            issue_loads(0);
+            issue_loads();
         }
-    } else {
-        if (ks_begin < ksteps) load_tile(ks_begin, 0);
-    }
-    if constexpr (GLDS && NS >= 3) {
-        // Ring of NS stages, NS-1 of them in flight: counted s_waitcnt vmcnt (never 0 in the steady state) + a raw
-        // s_barrier, ONE barrier per K step. At the barrier of step k every wave has (a) waited for its own loads of
-        // stage k and (b) finished the fragment reads of step k-1, so the buffer refilled right after the barrier
-        // (stage k+NS-1 -> buffer (k-1) % NS) is free and the one the MFMAs read (k % NS) is complete.
-        constexpr int LPS = PA + PB;                           // direct-to-LDS instructions per wave per stage
-        static_assert(LPS * (NS - 2) <= 63, "vmcnt field");
-        const int total = ksteps - ks_begin;
-        for (int s = 1; s < NS - 1; ++s)
-            if (s < total) {
-                advance();
-                issue_loads(s);
-            }
-        int buf = 0;
-        for (int ks = ks_begin; ks < ksteps; ++ks) {
-            const int behind = ksteps - 1 - ks;                 // stages issued after stage ks that may stay in flight
-            if (behind >= NS - 2) wait_vmcnt_lds<LPS * (NS - 2)>();
-            else if (NS == 4 && behind == 1) wait_vmcnt_lds<LPS>();
-            else wait_vmcnt_lds<0>();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (ks + NS - 1 < ksteps) {
-                advance();
-                int nb = buf + NS - 1;
-                if (nb >= NS) nb -= NS;
-                issue_loads(nb);
-            }
-            mfma_phase(buf);
-            if (++buf == NS) buf = 0;
-        }
-        __syncthreads();                                        // the epilogue reuses the staging area
-    } else if constexpr (GLDS && NS == 2) {
-        int buf = 0;
-        for (int ks = ks_begin; ks < ksteps; ++ks, buf ^= 1) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's part of stage `buf` has landed in LDS
-            __syncthreads();                                    // ... everybody else's too, and all fragment reads of
-                                                                // the previous step (the other buffer) are done
-            if (ks + 1 < ksteps && a.dbg != 3) {                // in flight during the MFMAs below
-                advance();
-                issue_loads(buf ^ 1);
-            }
-            if (a.dbg != 2) mfma_phase(buf);
-        }
-        __syncthreads();                                        // the epilogue reuses the staging area
-    } else if constexpr (GLDS) {
-        stamp(4);                                               // prologue done (tables, first stage issued)
+        stamp(4);                                              // prologue done (tables, first stage issued)
         for (int ks = ks_begin; ks < ksteps; ++ks) {
             const int tb = 16 + (ks - ks_begin) * 6;
             stamp(tb);
@@ -615,24 +493,25 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
             stamp(tb + 1);
             __syncthreads();                                    // ... and everybody else's
             stamp(tb + 2);
-            if (a.dbg != 2) mfma_phase(0);
+            mfma_phase();
             stamp(tb + 3);
             __syncthreads();                                    // all fragment reads done: the buffer may be refilled
             stamp(tb + 4);
-            if (ks + 1 < ksteps && a.dbg != 3) {
+            if (ks + 1 < ksteps) {
                 advance();
-                issue_loads(0);
+                issue_loads();
             }
             stamp(tb + 5);
         }
         stamp(5);                                               // K loop done
     } else {
+        if (ks_begin < ksteps) load_tile(ks_begin);
         for (int ks = ks_begin; ks < ksteps; ++ks) {
             __syncthreads();            // previous stage's fragment reads are done
             store_tile();
             __syncthreads();
-            load_tile(ks + 1 < ksteps ? ks + 1 : ks, 0);   // in flight during the MFMA phase (last one: harmless re-load)
-            mfma_phase(0);
+            load_tile(ks + 1 < ksteps ? ks + 1 : ks);      // in flight during the MFMA phase (last one: harmless re-load)
+            mfma_phase();
         }
     }
 
@@ -932,11 +811,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
                 if (op != 0xffffffffu) {
                     const u32x4 val = *reinterpret_cast<const u32x4*>(smem + r * EROW + ((ch ^ (r & (CPR - 1))) << 4));
                     u32x4* dst = reinterpret_cast<u32x4*>(a.y + (size_t)op * a.Cout + co0 + ch * 8);
-#if defined(__HIP_DEVICE_COMPILE__)
-                    if (a.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(dst), "v"(val) : "memory");
-                    else
-#endif
-                        *dst = val;
+                    *dst = val;
                 }
             }
         } else {
@@ -953,11 +828,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
                     if (op != 0xffffffffu) {
                         const u32x4 val = *reinterpret_cast<const u32x4*>(smem + r * EROW + ((ch ^ (r & (CPR - 1))) << 4));
                         u32x4* dst = reinterpret_cast<u32x4*>(a.y + (size_t)op * a.Cout + co0 + ch * 8);
-#if defined(__HIP_DEVICE_COMPILE__)
-                        if (a.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(dst), "v"(val) : "memory");
-                        else
-#endif
-                            *dst = val;
+                        *dst = val;
                         if constexpr (KIND == 1) ts.template add<TWO>(val.x, val.y, val.z, val.w, (m0 + r) >= boundary);
                         if constexpr (KIND == 2) {
                             const u32x4 uv = *reinterpret_cast<const u32x4*>(a.bstats_u + (size_t)op * a.Cout + co0 + ch * 8);
@@ -1017,12 +888,10 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid_raw, 
     }
 }
 
-template <int WN, int WM, int TN, int TM, bool GLDS, int NS, int BK = CONV_BK, bool PF = false, int OCC = 0, bool BUFA = false,
-          bool ST = false>
-__global__ __launch_bounds__(64 * WN * WM, OCC > 0 ? (OCC * WN * WM + 3) / 4
-                                           : ((GLDS && WN * WM == 4 && TN * TM == 4) ? ((NS == 1 || BK == 32) ? 4 : 2)
-                                              : ((WN * WM == 4 && TN * TM == 8) ? 2 : 1))) void conv_igemm_kernel(ConvArgs a) {
-    conv_body<WN, WM, TN, TM, GLDS, NS, BK, PF, OCC, BUFA, ST>(a, (int)blockIdx.x, (int)gridDim.x, 0);
+template <int WN, int WM, int TN, int TM, bool GLDS, bool BUFA = false, bool ST = false>
+__global__ __launch_bounds__(64 * WN * WM, (GLDS && WN * WM == 4 && TN * TM == 4) ? 4
+                                           : ((WN * WM == 4 && TN * TM == 8) ? 2 : 1)) void conv_igemm_kernel(ConvArgs a) {
+    conv_body<WN, WM, TN, TM, GLDS, BUFA, ST>(a, (int)blockIdx.x, (int)gridDim.x, 0);
 }
 
 // Two tile shapes in one launch. A layer of T = pixel tiles x channel tiles workgroups of the 128 x 128 tile leaves
@@ -1034,10 +903,9 @@ __global__ __launch_bounds__(64 * WN * WM, OCC > 0 ? (OCC * WN * WM + 3) / 4
 template <bool BUFA, bool ST = false>
 __global__ __launch_bounds__(256, 4) void conv_igemm_mixed_kernel(ConvArgs a) {
     if ((int)blockIdx.x < a.n_main)
-        conv_body<2, 2, 2, 2, true, 1, CONV_BK, false, 0, BUFA, ST>(a, (int)blockIdx.x, a.n_main, 0);
+        conv_body<2, 2, 2, 2, true, BUFA, ST>(a, (int)blockIdx.x, a.n_main, 0);
     else
-        conv_body<1, 4, 1, 1, true, 1, CONV_BK, false, 0, BUFA, ST>(a, (int)blockIdx.x - a.n_main, (int)gridDim.x - a.n_main,
-                                                                   a.rem_tile_base);
+        conv_body<1, 4, 1, 1, true, BUFA, ST>(a, (int)blockIdx.x - a.n_main, (int)gridDim.x - a.n_main, a.rem_tile_base);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1185,55 +1053,28 @@ static int conv_check(const cms_conv_desc* d) {
     return CMS_OK;
 }
 
-// Pipelined variants of the direct-to-LDS kernel (cms_conv_desc.variant 10..14): NS ring stages of BK K-elements,
-// fragment double buffer, register budget declared for OCC workgroups per CU.
-template <int WN, int WM, int TN, int TM, int NS, int BK, int OCC, bool BUFA = false>
-static void conv_launch_ring(const ConvArgs& a, hipStream_t s) {
-    constexpr int BN = WN * TN * 32, BM = WM * TM * 32, NT = 64 * WN * WM;
-    const int grid = (a.Cout / BN) * ((a.M + BM - 1) / BM) * a.ksplit;
-    const size_t stage = (size_t)(BN + BM) * BK * 2 * NS, epi = (size_t)BM * BN * 2;
-    const size_t lds = (stage > epi ? stage : epi) + 80 + BM * 16 + 2 * BN * 4;
-    auto kern = conv_igemm_kernel<WN, WM, TN, TM, true, NS, BK, true, OCC, BUFA>;
-    static bool raised = false;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        raised = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, s, a);
-}
+enum ConvLoader { CONV_LOADER_REGISTERS, CONV_LOADER_FLAT, CONV_LOADER_BUFFER };      // the last two: direct-to-LDS
 
 template <int WN, int WM, int TN, int TM, bool STATS_TILE = false>
-static void conv_launch(const ConvArgs& a, hipStream_t s, int loader) {      // loader: 0 registers, 1 / 2 = glds stages,
-    constexpr int BN = WN * TN * 32, BM = WM * TM * 32;                       //         3 = two glds stages of BK = 32
+static void conv_launch(const ConvArgs& a, hipStream_t s, ConvLoader loader) {
+    constexpr int BN = WN * TN * 32, BM = WM * TM * 32;
     const int grid = (a.Cout / BN) * ((a.M + BM - 1) / BM) * a.ksplit;
-    const size_t stage = (size_t)(BN + BM) * CONV_ROW_BYTES * (loader == 2 ? 2 : 1), epi = (size_t)BM * BN * 2;
+    const size_t stage = (size_t)(BN + BM) * CONV_ROW_BYTES, epi = (size_t)BM * BN * 2;
     const size_t lds = (stage > epi ? stage : epi) + 80 + BM * 16 + 2 * BN * 4 + (a.trace ? CONV_TRACE_DWORDS * 4 : 0);
     constexpr int NT = 64 * WN * WM;
-    if (loader == 2) {
-        // two stages of the 128 x 128 tile need 66 KB of dynamic LDS: above the 64 KB a kernel gets without asking
-        static bool raised = false;
-        if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<WN, WM, TN, TM, true, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            raised = true;
-        }
-        hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, 2>), dim3(grid), dim3(NT), lds, s, a);
-    } else if (loader == 3 && BN % (16 * WN * WM) == 0 && BM % (16 * WN * WM) == 0) {
-        if constexpr (BN % (16 * WN * WM) == 0 && BM % (16 * WN * WM) == 0)       // 64-byte rows: 16 rows per wave load
-            hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, 2, 32>), dim3(grid), dim3(NT), lds, s, a);
-    } else if (STATS_TILE && a.stats_out != nullptr && (loader == 4 || loader == 1)) {     // (the caller has checked the loader)
+    if (STATS_TILE && a.stats_out != nullptr && loader != CONV_LOADER_REGISTERS) {      // (the caller has checked the loader)
         if constexpr (STATS_TILE) {
-            if (loader == 4)
-                hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, 1, CONV_BK, false, 0, true, true>), dim3(grid), dim3(NT), lds, s, a);
+            if (loader == CONV_LOADER_BUFFER)
+                hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, true, true>), dim3(grid), dim3(NT), lds, s, a);
             else
-                hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, 1, CONV_BK, false, 0, false, true>), dim3(grid), dim3(NT), lds, s, a);
+                hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, false, true>), dim3(grid), dim3(NT), lds, s, a);
         }
-    } else if (loader == 4) {                    // direct-to-LDS with buffer addressing
-        hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, 1, CONV_BK, false, 0, true>), dim3(grid), dim3(NT), lds, s, a);
-    } else if (loader == 1 || loader == 3) {
-        hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, 1>), dim3(grid), dim3(NT), lds, s, a);
+    } else if (loader == CONV_LOADER_BUFFER) {
+        hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, true>), dim3(grid), dim3(NT), lds, s, a);
+    } else if (loader == CONV_LOADER_FLAT) {
+        hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, true, false>), dim3(grid), dim3(NT), lds, s, a);
     } else {
-        hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, false, 1>), dim3(grid), dim3(NT), lds, s, a);
+        hipLaunchKernelGGL((conv_igemm_kernel<WN, WM, TN, TM, false>), dim3(grid), dim3(NT), lds, s, a);
     }
 }
 
@@ -1318,6 +1159,11 @@ extern "C" int cms_conv_igemm_stats_tile_rows(const cms_conv_desc* d) {
 extern "C" int cms_conv_igemm(const cms_conv_desc* d_in, void* stream) {
     int rc = conv_check(d_in);
     if (rc) return rc;
+    // an unknown code is an error: a tool that asks for a kernel that does not exist must not time the default one in its place
+    CMS_REQUIRE(d_in->variant == 0 || d_in->variant == 1 || d_in->variant == 30 || d_in->variant == 43 ||
+                    (d_in->variant >= 90 && d_in->variant <= 93) || d_in->variant == 99,
+                "conv: variant %d does not exist (0 = auto, 1 = register-staged loader, 30 = cycle trace, 43 = flat direct-to-LDS "
+                "addresses, 90..93 = eight-phase kernel, 99 = never the eight-phase kernel)", d_in->variant);
     if (d_in->variant >= 90 && d_in->variant <= 93)     // 92 / 93: 90 / 91 with cycle stamps into the cms_conv_set_trace buffer
         return cms::conv8_launch(d_in, (hipStream_t)stream, (d_in->variant - 90) & 1, 0,
                                  d_in->variant >= 92 ? g_conv_trace : nullptr, g_conv_trace_wgs);
@@ -1365,152 +1211,59 @@ extern "C" int cms_conv_igemm(const cms_conv_desc* d_in, void* stream) {
     a.zeros = (const uint16_t*)d->zeros;
     CMS_REQUIRE(d->zeros == nullptr || d->zeros_bytes >= 2 * d->cin + 128,
                 "conv: the zero run (%d bytes) must be at least 2 * Cin + 128 = %d bytes long", d->zeros_bytes, 2 * d->cin + 128);
-    // 20..23: the default kernel with K rotation (stride 1 / 3 / 5 / 11 K steps per pixel tile)
-    // 24: the default kernel with staggered starts of co-resident workgroups; 25: stagger + rotation by 3
-    a.krot = d->variant == 20 ? 1 : (d->variant == 21 ? 3 : (d->variant == 22 ? 5 : (d->variant == 23 ? 11 : (d->variant == 25 ? 3 : 0))));
-    a.stagger = (d->variant == 24 || d->variant == 25) ? 1 : 0;
     a.n_main = 0; a.rem_tile_base = 0;
-    static int env_nt = -1;
-    if (env_nt < 0) {
-        const char* e = getenv("CMS_CONV_NT");          // A/B switch, read once
-        env_nt = e ? atoi(e) : 0;
-    }
-    a.nt_store = env_nt;
     // pointwise fast path of the prologue (conv_body: `plain`)
     a.plain = (d->ntaps == 1 && d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->stride == 1 && d->h == d->ho &&
-               d->w_in == d->wo && d->out_stride == 1 && d->out_h == d->ho && d->out_w == d->wo && a.ksplit == 1 && a.krot == 0 &&
+               d->w_in == d->wo && d->out_stride == 1 && d->out_h == d->ho && d->out_w == d->wo && a.ksplit == 1 &&
                (size_t)a.M * d->cin * 2 < (1ull << 31)) ? 1 : 0;
     // 30: the default kernel with per-workgroup cycle stamps into the buffer given to cms_conv_set_trace
-    a.trace = (d->variant == 30 || d->variant == 41) ? g_conv_trace : nullptr;      // 41: trace of variant 40
+    a.trace = d->variant == 30 ? g_conv_trace : nullptr;
     a.trace_wgs = g_conv_trace_wgs;
-    a.dbg = (d->variant == 2 || d->variant == 3) ? d->variant : (d->variant == 6 ? 2 : (d->variant == 7 ? 3 : 0));
-    // variant 0: direct-to-LDS, one stage, up to 4 workgroups per CU (default); 1: register-staged loader;
-    // 4: direct-to-LDS, two stages, 2 workgroups per CU -- measured 10 % faster on grids of exactly <= 2 workgroups per
-    // CU, 20 % slower on everything else (tools/tail_probe.py): co-resident workgroups hide more than the second stage;
-    // 2 / 3: ablation switches of the default kernel (no MFMA / no loads after the first stage)
-    // 5: direct-to-LDS, two stages of 32 K-elements each (same LDS footprint and occupancy as the default)
-    // 6 / 7: the ablation switches applied to the two-stage kernel (variant 4)
-    // default (and 40 / 41): direct-to-LDS with buffer addressing when both tensors are below 2 GB; 43 forces the flat
-    // 64-bit addresses of round 1 (A/B: profiles/r02o_*)
+    // loader: register-staged without a zero run (the C ABI's zeros == NULL) or as variant 1; else direct-to-LDS, with buffer
+    // addressing when both tensors are below 2 GB and with flat 64-bit addresses above (variant 43: the flat loader at any size)
     const bool small = (size_t)d->n * d->h * d->w_in * d->cin * 2 < (1ull << 31) &&
                        (size_t)d->ntaps * d->cout * d->cin * 2 < (1ull << 31);
-    const int glds = (d->zeros == nullptr || d->variant == 1) ? 0
-                     : ((d->variant == 4 || d->variant == 6 || d->variant == 7) ? 2
-                        : (d->variant == 5 ? 3 : ((small && d->variant != 43) ? 4 : 1)));      // 43: flat addresses (round-1 loader)
+    const ConvLoader loader = (d->zeros == nullptr || d->variant == 1) ? CONV_LOADER_REGISTERS
+                              : ((small && d->variant != 43) ? CONV_LOADER_BUFFER : CONV_LOADER_FLAT);
     const int tile = d->tile;   // 0 = auto
-    CMS_REQUIRE(d->stats_out == nullptr || glds == 4 || glds == 1, "conv: stats_out needs the direct-to-LDS kernels (a zero run in the descriptor)");
-    if (d->variant >= 80 && d->variant <= 85) {
-        // Round 3 experiment: 256 (co) x 128 (pixels) on FOUR waves (each 128 co x 64 pixels): 48 KB staged and 96 KB of fragment
-        // reads per 2x the MFMA work of the default tile, one workgroup per CU for layers of ~263 pixel tiles
-        CMS_REQUIRE(d->zeros != nullptr && small && d->cout % 256 == 0, "conv: variants 80..85 need the zero run, tensors below 2 GB, Cout %% 256 == 0");
-        switch (d->variant) {
-        case 80: conv_launch_ring<2, 2, 4, 2, 1, 64, 1, true>(a, s); break;
-        case 81: conv_launch_ring<2, 2, 4, 2, 2, 64, 1, true>(a, s); break;
-        case 82: conv_launch_ring<2, 2, 4, 2, 3, 64, 1, true>(a, s); break;
-        case 83: conv_launch_ring<2, 2, 4, 2, 3, 32, 1, true>(a, s); break;
-        case 84: conv_launch_ring<2, 2, 4, 2, 4, 32, 1, true>(a, s); break;
-        default: conv_launch_ring<2, 2, 4, 2, 2, 64, 2, true>(a, s); break;
-        }
-        return launch_status("cms_conv_igemm");
-    }
-    if (d->variant >= 60 && d->variant <= 75) {
-        // Round 3 experiment: the stage rings on WIDE tiles with buffer-addressed asm loads (the wide rings 10..14 of round 2
-        // used the builtin loads the compiler drains): 60..63 = 128 (co) x 256 (pixels) on 8 waves; 70..73 = 256 x 256 on 8
-        // waves (each wave 128 co x 64 pixels: 6 fragment reads per 8 MFMAs, 64 KB staged per 4x the work of the default tile)
-        CMS_REQUIRE(d->zeros != nullptr && small, "conv: variants 60..75 need the zero run and tensors below 2 GB");
-        if (d->variant < 70) {
-            CMS_REQUIRE(d->cout % 128 == 0, "conv: variants 60..63 need Cout %% 128 == 0");
-            switch (d->variant) {
-            case 60: conv_launch_ring<2, 4, 2, 2, 1, 64, 2, true>(a, s); break;
-            case 61: conv_launch_ring<2, 4, 2, 2, 2, 64, 1, true>(a, s); break;
-            case 62: conv_launch_ring<2, 4, 2, 2, 3, 32, 2, true>(a, s); break;
-            default: conv_launch_ring<2, 4, 2, 2, 4, 32, 1, true>(a, s); break;
-            }
-        } else {
-            CMS_REQUIRE(d->cout % 256 == 0, "conv: variants 70..73 need Cout %% 256 == 0");
-            switch (d->variant) {
-            case 70: conv_launch_ring<2, 4, 4, 2, 1, 64, 1, true>(a, s); break;
-            case 71: conv_launch_ring<2, 4, 4, 2, 2, 64, 1, true>(a, s); break;
-            case 72: conv_launch_ring<2, 4, 4, 2, 3, 32, 1, true>(a, s); break;
-            default: conv_launch_ring<2, 4, 4, 2, 4, 32, 1, true>(a, s); break;
-            }
-        }
-        return launch_status("cms_conv_igemm");
-    }
-    if (d->variant >= 50 && d->variant <= 54) {
-        // 50..54: the stage rings 10..14 of the 128 x 128 tile with buffer addressing
-        CMS_REQUIRE(d->zeros != nullptr && small && d->cout % 128 == 0 && (tile == 0 || tile == 128),
-                    "conv: variants 50..54 need the zero run, tensors below 2 GB and the 128-channel tile");
-        switch (d->variant) {
-        case 50: conv_launch_ring<2, 2, 2, 2, 1, 64, 4, true>(a, s); break;
-        case 51: conv_launch_ring<2, 2, 2, 2, 2, 64, 2, true>(a, s); break;
-        case 52: conv_launch_ring<2, 2, 2, 2, 3, 32, 3, true>(a, s); break;
-        case 53: conv_launch_ring<2, 2, 2, 2, 4, 32, 2, true>(a, s); break;
-        default: conv_launch_ring<2, 2, 2, 2, 3, 64, 1, true>(a, s); break;
-        }
-        return launch_status("cms_conv_igemm");
-    }
-    if (d->variant >= 10 && d->variant <= 14) {
-        // pipelined kernels (ring of LDS stages with counted vmcnt, fragment double buffer), 128 x 128 tile on 4 waves or
-        // 128 (co) x 256 (pixels) on 8 waves:  10: 1 stage of 64   11: 2 x 64   12: 3 x 32   13: 4 x 32   14: 3 x 64
-        CMS_REQUIRE(d->zeros != nullptr, "conv: variants 10..14 need the zero run (direct-to-LDS loader)");
-        CMS_REQUIRE(d->cout % 128 == 0 && (tile == 0 || tile == 128 || tile == 256),
-                    "conv: variants 10..14 exist for the 128-channel tiles (tile 0 / 128 / 256)");
-        if (tile == 256) {
-            switch (d->variant) {
-            case 10: conv_launch_ring<2, 4, 2, 2, 1, 64, 2>(a, s); break;
-            case 11: conv_launch_ring<2, 4, 2, 2, 2, 64, 1>(a, s); break;
-            case 12: conv_launch_ring<2, 4, 2, 2, 3, 32, 2>(a, s); break;
-            case 13: conv_launch_ring<2, 4, 2, 2, 4, 32, 1>(a, s); break;
-            default: conv_launch_ring<2, 4, 2, 2, 3, 64, 1>(a, s); break;
-            }
-        } else {
-            switch (d->variant) {
-            case 10: conv_launch_ring<2, 2, 2, 2, 1, 64, 4>(a, s); break;
-            case 11: conv_launch_ring<2, 2, 2, 2, 2, 64, 2>(a, s); break;
-            case 12: conv_launch_ring<2, 2, 2, 2, 3, 32, 3>(a, s); break;
-            case 13: conv_launch_ring<2, 2, 2, 2, 4, 32, 2>(a, s); break;
-            default: conv_launch_ring<2, 2, 2, 2, 3, 64, 1>(a, s); break;
-            }
-        }
-        return launch_status("cms_conv_igemm");
-    }
+    CMS_REQUIRE(d->stats_out == nullptr || loader != CONV_LOADER_REGISTERS,
+                "conv: stats_out needs the direct-to-LDS kernels (a zero run in the descriptor)");
     if (tile == 256) {                         // 8 waves: 128 co x 256 pixels (more reuse of the weight tile)
         CMS_REQUIRE(d->cout % 128 == 0, "conv: tile 256 needs Cout %% 128 == 0");
-        conv_launch<2, 4, 2, 2>(a, s, glds);
+        conv_launch<2, 4, 2, 2>(a, s, loader);
     } else if (tile == 2256) {                 // 4 waves, each 64 co x 128 pixels: 6 fragment reads per 8 MFMAs
         CMS_REQUIRE(d->cout % 128 == 0, "conv: tile 2256 needs Cout %% 128 == 0");
-        conv_launch<2, 2, 2, 4>(a, s, glds);
+        conv_launch<2, 2, 2, 4>(a, s, loader);
     } else if (tile == 1128) {                 // 8 waves on the 128 x 128 tile (each wave 64 co x 32 pixels)
         CMS_REQUIRE(d->cout % 128 == 0, "conv: tile 1128 needs Cout %% 128 == 0");
-        conv_launch<2, 4, 2, 1>(a, s, glds);
+        conv_launch<2, 4, 2, 1>(a, s, loader);
     } else if ((tile == 0 && d->cout % 128 == 0) || tile == 128) {
         // default: 128 co x 128 pixels, 4 waves of 64 x 64 (the 8-wave layouts above measured within +-5 % of it on
-        // the DeepLab v2 layer shapes and no better end to end, tools/conv_ablate.py)
+        // the DeepLab v2 layer shapes and no better end to end, docs/DESIGN_HISTORY.md 4.1)
         CMS_REQUIRE(d->cout % 128 == 0, "conv: tile 128 needs Cout %% 128 == 0");
         // balanced launch (conv_igemm_mixed_kernel): when the 128 x 128 grid is a few workgroups more than a multiple of
         // the 256 CUs, those few are cut into 32-channel slices.
         const int ntn = d->cout / 128, mtiles = (a.M + 127) / 128, total = mtiles * ntn;
         const int rounds = total / 256, rem = total % 256;
-        if (tile == 0 && d->variant == 0 && (glds == 4 || glds == 1) && a.ksplit == 1 && 256 % ntn == 0 &&
+        if (tile == 0 && d->variant == 0 && loader != CONV_LOADER_REGISTERS && a.ksplit == 1 && 256 % ntn == 0 &&
             rounds >= 1 && rounds <= 9 && rem > 0 && rem <= 100) {
             a.n_main = rounds * 256;
             a.rem_tile_base = a.n_main / ntn;
             const int n_rem = (mtiles - a.rem_tile_base) * (d->cout / 32);
             const size_t lds = 32768 + 80 + 128 * 16 + 2 * 128 * 4 + (a.trace ? CONV_TRACE_DWORDS * 4 : 0);
             if (a.stats_out) {
-                if (glds == 4) hipLaunchKernelGGL((conv_igemm_mixed_kernel<true, true>), dim3(a.n_main + n_rem), dim3(256), lds, s, a);
+                if (loader == CONV_LOADER_BUFFER) hipLaunchKernelGGL((conv_igemm_mixed_kernel<true, true>), dim3(a.n_main + n_rem), dim3(256), lds, s, a);
                 else hipLaunchKernelGGL((conv_igemm_mixed_kernel<false, true>), dim3(a.n_main + n_rem), dim3(256), lds, s, a);
-            } else if (glds == 4) hipLaunchKernelGGL(conv_igemm_mixed_kernel<true>, dim3(a.n_main + n_rem), dim3(256), lds, s, a);
+            } else if (loader == CONV_LOADER_BUFFER) hipLaunchKernelGGL(conv_igemm_mixed_kernel<true>, dim3(a.n_main + n_rem), dim3(256), lds, s, a);
             else hipLaunchKernelGGL(conv_igemm_mixed_kernel<false>, dim3(a.n_main + n_rem), dim3(256), lds, s, a);
             return launch_status("cms_conv_igemm");
         }
-        conv_launch<2, 2, 2, 2, true>(a, s, glds);
+        conv_launch<2, 2, 2, 2, true>(a, s, loader);
     } else if ((tile == 0 && d->cout % 64 == 0) || tile == 64) {
         CMS_REQUIRE(d->cout % 64 == 0, "conv: tile 64 needs Cout %% 64 == 0");
-        conv_launch<1, 4, 2, 1, true>(a, s, glds);     // 64 co x 128 pixels
+        conv_launch<1, 4, 2, 1, true>(a, s, loader);     // 64 co x 128 pixels
     } else {
-        conv_launch<1, 4, 1, 1, true>(a, s, glds);     // 32 co x 128 pixels
+        conv_launch<1, 4, 1, 1, true>(a, s, loader);     // 32 co x 128 pixels
     }
     return launch_status("cms_conv_igemm");
 }

@@ -376,13 +376,14 @@ typedef struct cms_conv_desc {
     const void* zeros;     /* a run of zero bytes in device memory, at least 2 * cin + 128 long: enables the
                               direct-to-LDS loader (padded / out-of-range rows are fetched from it, advancing through
                               it like a live pixel's channel run); NULL = register-staged loader                 */
-    int variant;           /* 0 = auto (direct-to-LDS, 1 stage), 1 = register-staged loader, 4 = direct-to-LDS with
-                              two stages, 5 = two stages of 32 K-elements; 2 / 3 = ablation switches (no MFMA / no
-                              loads) of variant 0, 6 / 7 = the same of variant 4 (tools/conv_ablate*.py); 10..14 = stage
-                              rings, 20..25 = K rotation / staggered starts, 30 = cycle trace (all measured, none
-                              faster: DESIGN.md section 4.1); 90 = the eight-phase 256 x 256 kernel, one whole tile
-                              per workgroup; 91 = the same, persistent with a stream-K round (needs `workspace`);
-                              99 = never the eight-phase kernel                                                 */
+    int variant;           /* 0 = auto (direct-to-LDS, buffer-addressed below 2 GB per tensor, flat addresses above),
+                              1 = register-staged loader, 30 = variant 0 with cycle stamps (cms_conv_set_trace), 43 = the
+                              flat-address direct-to-LDS loader at any size; 90 = the eight-phase 256 x 256 kernel, one
+                              whole tile per workgroup; 91 = the same, persistent with a stream-K round (needs
+                              `workspace`); 92 / 93 = 90 / 91 with cycle stamps; 99 = never the eight-phase kernel.
+                              Any other code is an error (the stage rings, two-stage loaders, K rotation and ablation
+                              switches that once had codes were measured, none faster, and removed: DESIGN.md
+                              section 4.1)                                                                        */
     int zeros_bytes;       /* length of the `zeros` run (checked against 2 * cin + 128)                          */
     void* workspace;       /* optional scratch of the eight-phase 256 x 256 kernel (csrc/conv8.hip; variant 90 / 91 or
                               the automatic choice for Cout % 256 == 0 layers with >= 8 K tiles), at least
