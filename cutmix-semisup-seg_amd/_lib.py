@@ -275,6 +275,9 @@ PROTOTYPES = {
     'cms_select_workspace_bytes': (c_size_t, [c_int]),
     'cms_select_k_smallest': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, C.c_longlong, c_int, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
+    'cms_pd_box_sum': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'cms_pd_neighbour_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'cms_pd_neighbour_maps': (c_int, [c_void_p, _P(StageEntry), c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 fn = {}

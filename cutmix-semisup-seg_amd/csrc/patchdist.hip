@@ -13,6 +13,9 @@
 //             pattern of a non-negative double)
 //   select    radix select of the k smallest masked keys: eight 8-bit histogram passes find the k-th key, one pass compacts the
 //             keys <= it. No sort of the map; the caller sorts the <= k survivors.
+// and, without the FFT, patch_dist.py:39-104 (the distance of a patch to the patches centred on its four neighbours):
+//   squares   squared neighbour differences of the symmetric extension of a pool entry, two int32 planes
+//   box sum   exact separable running sums in int64, loads per output independent of the box
 #include "common.hpp"
 
 namespace cms {
@@ -271,6 +274,154 @@ __global__ void select_init(SelectState* state, unsigned int* hist, int* count, 
 
 static size_t select_workspace(int n) { return n > 0 ? (size_t)n * (sizeof(SelectState) + 256 * sizeof(unsigned int)) : 0; }
 
+// ------------------------------------------------------------------------------------------- neighbouring-patch distances
+// patch_dist.py:57-104: the distance of the patch centred on a pixel to the patches centred on its four neighbours. Moving a patch
+// by one pixel turns the sum over the patch of (c - neighbour)^2 into a box sum of squared neighbour DIFFERENCES of the padded
+// image, so nothing here multiplies patches: one pass writes the squared differences, an exact separable box sum finishes them.
+// With a = (ph - 1) / 2, b = (pw - 1) / 2, I the symmetric extension of the entry and (y, x) over the (hs + ph - 1, ws + pw - 1)
+// domain of the centre view:
+//     hq[y][x] = sum_c (I[y-a][x-b] - I[y-a][x-b-1])^2    x <= wp: left = box(hq)[:, :ws],  right = box(hq)[:, 1:]
+//     vq[y][x] = sum_c (I[y-a][x-b] - I[y-a-1][x-b])^2    y <= hp: up   = box(vq)[:hs, :],  down  = box(vq)[1:, :]
+// (the right neighbour's difference at x is the left one's at x + 1, reflections at the edge included).
+
+// grid (blocks over x, rows): one thread per (y, x) of the (hp + 1, wp + 1) domain both planes fit in
+__global__ void pd_neighbour_squares(const uint8_t* __restrict__ img, int hs, int ws, int pad_h, int pad_w, int hp, int wp,
+                                     int* __restrict__ hq, int* __restrict__ vq) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x > wp) return;
+    const int sx = sym_index(x - pad_w, ws), sl = sym_index(x - pad_w - 1, ws);
+    for (int y = blockIdx.y; y <= hp; y += gridDim.y) {
+        const uint8_t* row = img + (size_t)sym_index(y - pad_h, hs) * ws * 3;
+        const uint8_t* above = img + (size_t)sym_index(y - pad_h - 1, hs) * ws * 3;
+        int h2 = 0, v2 = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int v = row[(size_t)sx * 3 + c];
+            const int dh = v - row[(size_t)sl * 3 + c], dv = v - above[(size_t)sx * 3 + c];
+            h2 += dh * dh;
+            v2 += dv * dv;
+        }
+        if (y < hp) hq[(size_t)y * (wp + 1) + x] = h2;
+        if (x < wp) vq[(size_t)y * wp + x] = v2;
+    }
+}
+
+// The box sum is separable, and each pass is a running sum: a window moved by one gains one element and loses one, so an output
+// costs two loads whatever the window. A line is cut into segments that run in parallel; a segment starts from a window summed
+// directly, and the host sizes the segments by the window so that this start stays a bounded number of loads per output (at most
+// 4 more in pass 1, 1 more in pass 2), however large the window.
+//
+// pass 1, down the columns: tmp[i][x] = sum_{u < ph} in[i + u][x]. One thread per column and segment of `seg` output rows: lanes
+// are adjacent columns, so every load and store of a wave is one contiguous row piece. grid (blocks over x, segments)
+template <class T>
+__global__ void pd_box_columns(const T* __restrict__ in, int wp, int ho, int ph, int seg, long long* __restrict__ tmp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= wp) return;
+    for (long long first = (long long)blockIdx.y * seg; first < ho; first += (long long)gridDim.y * seg) {
+        const int i0 = (int)first, i1 = (int)min(first + seg, (long long)ho);
+        const T* p = in + (size_t)i0 * wp + x;
+        long long acc = 0;
+#pragma unroll 8
+        for (int u = 0; u < ph; ++u) acc += (long long)p[(size_t)u * wp];       // (unrolled: the loads of a thread are in flight together)
+        long long* o = tmp + (size_t)i0 * wp + x;
+        o[0] = acc;
+#pragma unroll 4
+        for (int i = i0 + 1; i < i1; ++i) {
+            acc += (long long)p[(size_t)(ph - 1 + i - i0) * wp] - (long long)p[(size_t)(i - 1 - i0) * wp];
+            o[(size_t)(i - i0) * wp] = acc;
+        }
+    }
+}
+
+struct BoxOut {                      // where the box sums go: value (i, j) of the (ho, wo) result is written to
+    long long* a;                    //   a[i * ld + j]                 if i < ha and j < wa
+    long long* b;                    //   b[(i - di) * ld + (j - dj)]   if b, i >= di and j >= dj: the same plane seen one step on
+    int ld, ha, wa, di, dj;
+};
+
+// pass 2, along the rows: out[i][j] = sum_{v < pw} tmp[i][j + v]. One WAVE per row and segment of `seg` outputs, lanes adjacent
+// outputs: out[j0 + m] = window(j0) + sum_{k <= m} (tmp[j0 + pw - 1 + k] - tmp[j0 + k - 1]), the sum being a wave-wide inclusive
+// scan of 64 differences (six shuffle steps) plus the carry of the chunks before. All loads and stores are contiguous per wave
+// and nothing passes through LDS.
+__global__ __launch_bounds__(256) void pd_box_rows(const long long* __restrict__ tmp, int wp, int ho, int wo, int pw, int seg,
+                                                   int n_seg, BoxOut out) {
+    const int lane = threadIdx.x & 63;
+    const long long items = (long long)ho * n_seg;
+    const long long step = (long long)gridDim.x * (blockDim.x >> 6);
+    for (long long item = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); item < items; item += step) {
+        const int i = (int)(item / n_seg);
+        const int j0 = (int)(item % n_seg) * seg, j1 = min(j0 + seg, wo);
+        const long long* row = tmp + (size_t)i * wp;
+        long long window = 0;
+        for (int v = lane; v < pw; v += 64) window += row[j0 + v];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) window += __shfl_xor(window, off, 64);
+        for (int m0 = 0; j0 + m0 < j1; m0 += 64) {
+            const int j = j0 + m0 + lane;
+            const bool live = j < j1;
+            long long d = 0;
+            if (live && j > j0) d = row[j + pw - 1] - row[j - 1];
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const long long below = __shfl_up(d, off, 64);
+                if (lane >= off) d += below;
+            }
+            const long long v = window + d;
+            window += __shfl(d, 63, 64);
+            if (live) {
+                if (i < out.ha && j < out.wa) out.a[(size_t)i * out.ld + j] = v;
+                if (out.b && i >= out.di && j >= out.dj) out.b[(size_t)(i - out.di) * out.ld + (j - out.dj)] = v;
+            }
+        }
+    }
+}
+
+constexpr int kBoxMinSegment = 32;       // output rows per thread of pass 1, at least
+constexpr int kBoxMinRowSegment = 256;   // outputs per wave of pass 2, at least
+
+// the two passes of one plane (hp, wp) -> (hp - ph + 1, wp - pw + 1); tmp holds (hp - ph + 1) * wp int64
+template <class T>
+static void box_sum_launch(const T* in, int hp, int wp, int ph, int pw, long long* tmp, const BoxOut& out, hipStream_t s) {
+    const int ho = hp - ph + 1, wo = wp - pw + 1;
+    // a segment no shorter than a quarter of the window: the direct sum that starts it adds at most 4 loads per output
+    const int seg = max(kBoxMinSegment, (ph + 3) / 4);
+    const int n_seg = (ho + seg - 1) / seg;
+    hipLaunchKernelGGL(pd_box_columns<T>, dim3((wp + 63) / 64, min(n_seg, 65535)), dim3(64), 0, s, in, wp, ho, ph, seg, tmp);
+    // a wave sums its first window 64 elements at a time: a segment as long as the window makes that one more load per output
+    const int row_seg = max(kBoxMinRowSegment, (pw + 63) / 64 * 64);
+    const int n_row_seg = (wo + row_seg - 1) / row_seg;
+    const long long waves = (long long)ho * n_row_seg;
+    hipLaunchKernelGGL(pd_box_rows, dim3((unsigned)min((waves + 3) / 4, (long long)(256 * 16))), dim3(256), 0, s, tmp, wp, ho, wo,
+                       pw, row_seg, n_row_seg, out);
+}
+
+constexpr long long kBoxMaxElements = 1LL << 30;     // of a plane: rows and columns stay ints with room to spare, offsets are size_t
+
+static int box_geometry_ok(long long hp, long long wp, int ph, int pw) {
+    return ph > 0 && pw > 0 && hp >= ph && wp >= pw && hp * wp < kBoxMaxElements;
+}
+
+static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+struct NeighbourLayout {             // the workspace of cms_pd_neighbour_maps: tmp | hq | vq
+    int hp, wp;
+    size_t tmp_bytes, hq_bytes, vq_bytes;
+    size_t total() const { return tmp_bytes + hq_bytes + vq_bytes; }
+};
+
+static int neighbour_layout(int hs, int ws, int ph, int pw, NeighbourLayout* l) {
+    if (hs <= 0 || ws <= 0 || ph <= 0 || pw <= 0 || !(ph & 1) || !(pw & 1)) return 0;
+    const long long hp = (long long)hs + ph - 1, wp = (long long)ws + pw - 1;
+    if ((hp + 1) * (wp + 1) >= kBoxMaxElements) return 0;
+    l->hp = (int)hp;
+    l->wp = (int)wp;
+    const size_t th = (size_t)hs * (size_t)(wp + 1), tv = (size_t)(hs + 1) * (size_t)wp;
+    l->tmp_bytes = align16((th > tv ? th : tv) * sizeof(long long));
+    l->hq_bytes = align16((size_t)hp * (size_t)(wp + 1) * sizeof(int));
+    l->vq_bytes = align16((size_t)(hp + 1) * (size_t)wp * sizeof(int));
+    return 1;
+}
+
 static int patch_geometry_ok(int ph, int pw, int fh, int fw) {
     return ph > 0 && pw > 0 && (ph & 1) && (pw & 1) && fh >= 8 && fw >= 8 && fh <= 4096 && fw <= 4096 && !(fh & (fh - 1)) &&
            !(fw & (fw - 1));
@@ -365,4 +516,46 @@ extern "C" int cms_select_k_smallest(const int64_t* keys, const uint8_t* mask, c
     hipLaunchKernelGGL(select_compact, grid, dim3(kSelectThreads), 0, s, (const unsigned long long*)keys, km, (size_t)m, state, (unsigned)k,
                        (long long*)out, count);
     return launch_status("cms_select_k_smallest");
+}
+
+extern "C" int cms_pd_box_sum(const void* in, int in_is_int64, int hp, int wp, int ph, int pw, void* work, int64_t* out, void* stream) {
+    CMS_REQUIRE(in && work && out, "pd_box_sum: NULL pointer");
+    CMS_REQUIRE(box_geometry_ok(hp, wp, ph, pw), "pd_box_sum: a box of %d x %d in a plane of %d x %d (fewer than 2^30 elements) required",
+                ph, pw, hp, wp);
+    BoxOut o;
+    o.a = (long long*)out; o.b = NULL;
+    o.ha = hp - ph + 1; o.wa = o.ld = wp - pw + 1; o.di = o.dj = 0;
+    if (in_is_int64) box_sum_launch((const long long*)in, hp, wp, ph, pw, (long long*)work, o, (hipStream_t)stream);
+    else box_sum_launch((const int*)in, hp, wp, ph, pw, (long long*)work, o, (hipStream_t)stream);
+    return launch_status("cms_pd_box_sum");
+}
+
+extern "C" size_t cms_pd_neighbour_workspace_bytes(int hs, int ws, int ph, int pw) {
+    NeighbourLayout l;
+    return neighbour_layout(hs, ws, ph, pw, &l) ? l.total() : 0;
+}
+
+extern "C" int cms_pd_neighbour_maps(const uint8_t* pool_img, const cms_stage_entry* entry_host, int ph, int pw, void* work,
+                                     int64_t* out_d2, void* stream) {
+    CMS_REQUIRE(pool_img && entry_host && work && out_d2, "pd_neighbour_maps: NULL pointer");
+    CMS_REQUIRE(ph > 0 && pw > 0 && (ph & 1) && (pw & 1), "pd_neighbour_maps: odd patch sizes required (got %d x %d)", ph, pw);
+    const int hs = entry_host->hs, ws = entry_host->ws;
+    CMS_REQUIRE(hs > 0 && ws > 0 && entry_host->img_off >= 0, "pd_neighbour_maps: bad pool entry");
+    NeighbourLayout l;
+    CMS_REQUIRE(neighbour_layout(hs, ws, ph, pw, &l), "pd_neighbour_maps: the padded image (%d + %d) x (%d + %d) must stay below 2^30 pixels",
+                hs, ph, ws, pw);
+    hipStream_t s = (hipStream_t)stream;
+    long long* tmp = (long long*)work;
+    int* hq = (int*)((char*)work + l.tmp_bytes);
+    int* vq = (int*)((char*)work + l.tmp_bytes + l.hq_bytes);
+    hipLaunchKernelGGL(pd_neighbour_squares, dim3((l.wp + 1 + 255) / 256, min(l.hp + 1, 65535)), dim3(256), 0, s,
+                       pool_img + entry_host->img_off, hs, ws, (ph - 1) / 2, (pw - 1) / 2, l.hp, l.wp, hq, vq);
+    const size_t map = (size_t)hs * ws;
+    BoxOut o;
+    o.ld = ws; o.ha = hs; o.wa = ws;
+    o.a = (long long*)out_d2; o.b = (long long*)out_d2 + map; o.di = 0; o.dj = 1;                  // left, right
+    box_sum_launch(hq, l.hp, l.wp + 1, ph, pw, tmp, o, s);
+    o.a = (long long*)out_d2 + 2 * map; o.b = (long long*)out_d2 + 3 * map; o.di = 1; o.dj = 0;    // up, down
+    box_sum_launch(vq, l.hp + 1, l.wp, ph, pw, tmp, o, s);
+    return launch_status("cms_pd_neighbour_maps");
 }

@@ -1138,6 +1138,49 @@ def pd_finish(corr, p2, q2, residual_bits, d2=None, keys=None):
                               int(corr.shape[-1]), _ptr(d2), _ptr(keys), _ptr(residual_bits), _stream()), 'cms_pd_finish')
 
 
+def _int64_buffer(what, t, numel, device):
+    """a caller's int64 buffer of at least `numel` elements, or a fresh one (the kernels initialise nothing they do not write)"""
+    if t is None:
+        return torch.empty((max(int(numel), 1),), dtype=torch.int64, device=device)
+    _need_cuda(t)
+    if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < numel:
+        raise TypeError('{}: a contiguous int64 CUDA tensor of at least {} elements is required'.format(what, numel))
+    return t
+
+
+def pd_box_sum(x, box, out=None, work=None):
+    """int32 or int64 CUDA plane (hp, wp) -> int64 (hp - bh + 1, wp - bw + 1): the exact sum of every bh x bw window, by two
+    running-sum passes (csrc/patchdist.hip). `out` and `work` ((hp - bh + 1) * wp int64) may be given; neither needs a value."""
+    _need_cuda(x)
+    if x.dtype not in (torch.int32, torch.int64) or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError('pd_box_sum: a contiguous int32 or int64 (H, W) tensor is required')
+    hp, wp, bh, bw = int(x.shape[0]), int(x.shape[1]), int(box[0]), int(box[1])
+    if bh < 1 or bw < 1 or bh > hp or bw > wp:
+        raise ValueError('pd_box_sum: a box of {} x {} does not fit a plane of {} x {}'.format(bh, bw, hp, wp))
+    ho, wo = hp - bh + 1, wp - bw + 1
+    out = _int64_buffer('pd_box_sum: out', out, ho * wo, x.device)
+    work = _int64_buffer('pd_box_sum: work', work, ho * wp, x.device)
+    check(fn['cms_pd_box_sum'](_ptr(x), int(x.dtype == torch.int64), hp, wp, bh, bw, _ptr(work), _ptr(out), _stream()), 'cms_pd_box_sum')
+    return out[:ho * wo].view(ho, wo)
+
+
+def pd_neighbour_workspace(hs, ws, patch_shape):
+    """int64 elements of the workspace of pd_neighbour_maps"""
+    return (int(fn['cms_pd_neighbour_workspace_bytes'](int(hs), int(ws), int(patch_shape[0]), int(patch_shape[1]))) + 7) // 8
+
+
+def pd_neighbour_maps(pool_img, entry, patch_shape, out=None, work=None):
+    """pool entry (a _lib.StageEntry on the host) -> int64 (4, Hs, Ws): the exact squared distance, in grey levels, of the patch
+    centred on each pixel to the patches centred on its left, right, upper and lower neighbour"""
+    _need_cuda(pool_img)
+    hs, ws = int(entry.hs), int(entry.ws)
+    out = _int64_buffer('pd_neighbour_maps: out', out, 4 * hs * ws, pool_img.device)
+    work = _int64_buffer('pd_neighbour_maps: work', work, pd_neighbour_workspace(hs, ws, patch_shape), pool_img.device)
+    check(fn['cms_pd_neighbour_maps'](_ptr(pool_img), C.byref(entry), int(patch_shape[0]), int(patch_shape[1]), _ptr(work), _ptr(out),
+                                      _stream()), 'cms_pd_neighbour_maps')
+    return out[:4 * hs * ws].view(4, hs, ws)
+
+
 def select_k_smallest(keys, k, mask=None, labels=None, cls=None, inter=False):
     """
     The k smallest candidate keys of each row of `keys` (int64 CUDA (N, M), non-negative, distinct within a row), by a radix select

@@ -11,6 +11,10 @@ with PQ a `valid` cross-correlation from an fp64 FFT (csrc/fft.hip), a few 1e-6 
 (csrc/patchdist.hip). The reference's distance is sqrt(D2) / 255. Every call reports the largest distance from an integer it saw
 (`last_rounding_residual()`) and raises when that exceeds 0.25: exactness would no longer be certain.
 
+The distance of a patch to the patches centred on its four neighbours (neighbouring_patch_distance_maps, the input-distribution
+figure) needs no FFT: shifting a patch by one pixel makes D2 a p_h x p_w box sum of squared neighbour differences of the image
+padded by (p - 1) // 2 + 1, which two running-sum passes in int64 give exactly (neighbour_sqr_distance_maps, csrc/patchdist.hip).
+
 Deviations from the reference, all deliberate:
   * patch sizes are odd on both axes (ValueError otherwise): the reference's even-size geometry is off by one and nothing uses it
   * the FFT size per axis is the smallest power of two >= max(8, H + p - 1), at most 4096 (ValueError beyond)
@@ -18,9 +22,12 @@ Deviations from the reference, all deliberate:
     by ascending flat pixel index i * W + j (the selection key is D2 << 24 | flat index, hence H * W <= 2^24 and
     3 * 255^2 * p_h * p_w < 2^39)
   * sliding_window_distance_to_patch[es_generator] take uint8 arrays; a float image is a TypeError
-  * neighbouring_patch_distance_maps, patch_average_distance_map and box_sum (a box filter for one figure) are not built
+  * neighbouring_patch_distance_maps and patch_average_distance_map take a uint8 image (a float image is a TypeError) and odd
+    patch sizes, as above
+  * a neighbouring-patch distance that is exactly 0 is returned as 0.0: the reference's float64 summed-area table of img_as_float
+    values cancels to about +-1e-13 there, which its square root turns into noise of about 1e-6 or into NaN
 
-Host functions (numpy) keep the reference's names and conventions: neighbouring_pixels_class_change, boundary_pixels,
+Host functions (numpy) keep the reference's names and conventions: neighbouring_pixels_class_change, boundary_pixels, box_sum,
 extract_patch, and choose_anchors_and_negatives, which is the closure of intra_inter_class_patch_dist.py:46-104 made a function.
 """
 import numpy as np
@@ -55,6 +62,22 @@ def boundary_pixels(y):
     """(H, W) bool: the pixel has a neighbour of another class in at least one direction (patch_dist.py:27-36)"""
     left, right, up, down = neighbouring_pixels_class_change(y)
     return left | right | up | down
+
+
+def box_sum(x, box_size):
+    """(H, W) -> (H + 1 - b_h, W + 1 - b_w): the sum of every b_h x b_w window, from a summed-area table (patch_dist.py:39-54).
+    Integer and bool input is summed in int64 or uint64, where the table is exact; float input in its own type, as the reference
+    does."""
+    x = np.asarray(x)
+    bh, bw = int(box_size[0]), int(box_size[1])
+    if x.ndim != 2 or bh < 1 or bw < 1 or bh > x.shape[0] or bw > x.shape[1]:
+        raise ValueError('box_sum: a box of {} x {} does not fit an array of shape {}'.format(bh, bw, x.shape))
+    if x.dtype.kind in 'bi':
+        x = x.astype(np.int64)
+    elif x.dtype.kind == 'u':
+        x = x.astype(np.uint64)
+    s = np.pad(np.cumsum(np.cumsum(x, axis=1), axis=0), [[1, 0], [1, 0]], mode='constant')
+    return s[bh:, bw:] - s[:-bh, bw:] - s[bh:, :-bw] + s[:-bh, :-bw]
 
 
 def extract_patch(image, patch_shape, yx):
@@ -270,6 +293,17 @@ def sqr_distance_maps(pool, sample_i, patches, chunk_size=DEFAULT_CHUNK):
     return d2
 
 
+def neighbour_sqr_distance_maps(pool, sample_i, patch_shape):
+    """int64 CUDA (4, H, W): the exact squared distance, in grey levels, between the patch centred on every pixel of sample
+    `sample_i` of `pool` and the patches centred on its left, right, upper and lower neighbour (NEIGHBOUR_OFFSETS order), all cut
+    from the sample symmetric-padded by (p - 1) // 2 + 1. Integer sums, no atomics: exact, and equal on every call."""
+    from . import ops, _lib
+    patch_shape = check_patch_shape(patch_shape)
+    t = pool.table[int(pool.entries_of([sample_i])[0])]
+    entry = _lib.StageEntry(int(t['img_off']), int(t['lab_off']), int(t['hs']), int(t['ws']))
+    return ops.pd_neighbour_maps(pool.image_buffer, entry, patch_shape)
+
+
 class Neighbours(object):
     """class_neighbours' result for N patches: sorted keys (N, k) int64 (D2 << 24 | y * W + x, KEY_SENTINEL past the count) and
     counts (N,), for the same-class (`intra`) and the other-class (`inter`) pixels of one image of width `width`"""
@@ -357,3 +391,25 @@ def sliding_window_distance_to_patch(image, patch):
     """one patch (p_h, p_w, 3): the (H, W) map (patch_dist.py:107-127)"""
     patch = _need_uint8('patch', patch)
     return next(sliding_window_distance_to_patches_generator(image, patch[None]))
+
+
+def neighbouring_patch_distance_maps(x, patch_size):
+    """uint8 image (H, W, 3) -> (left, right, up, down): four float64 (H, W) maps, the Euclidean distance, in the units of
+    img_as_float, between the patch centred on a pixel and the patch centred on its neighbour in that direction
+    (patch_dist.py:57-87). Exactly sqrt(D2) / 255 of the integer D2, so 0.0 where the two patches are equal."""
+    import torch
+    from .resident_pool import ResidentPool, ArraySource
+    x = _need_uint8('image', x)
+    patch_size = check_patch_shape(patch_size)
+    if x.ndim != 3 or x.shape[2] != 3:
+        raise ValueError('image must be (H, W, 3)')
+    dev = torch.device('cuda', torch.cuda.current_device())
+    pool = ResidentPool(ArraySource([x]), [0], dev, with_labels=False)
+    d2 = neighbour_sqr_distance_maps(pool, 0, patch_size).cpu().numpy()
+    return tuple(np.sqrt(d2[k].astype(np.float64)) / 255.0 for k in range(4))
+
+
+def patch_average_distance_map(x, patch_size):
+    """the mean of the four maps of neighbouring_patch_distance_maps, added in the reference's order (patch_dist.py:90-104)"""
+    left_d, right_d, up_d, down_d = neighbouring_patch_distance_maps(x, patch_size)
+    return (left_d + right_d + up_d + down_d) * 0.25

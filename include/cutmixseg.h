@@ -890,6 +890,25 @@ size_t cms_select_workspace_bytes(int n);
 int cms_select_k_smallest(const int64_t* keys, const uint8_t* mask, const uint8_t* labels, const int32_t* cls, int mode, int n,
                           long long m, int k, int64_t* out, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Neighbouring-patch distances (patch_dist.py:39-104 box_sum, neighbouring_patch_distance_maps): for every pixel of a pool entry the
+ * squared distance, in integer grey levels, between the (ph, pw, 3) patch centred on it and the patches centred on its left, right,
+ * upper and lower neighbour, all cut from the entry symmetric-padded by ((ph - 1) / 2 + 1, (pw - 1) / 2 + 1). Shifting a patch by
+ * one pixel makes that a ph x pw box sum of squared neighbour differences; integer arithmetic throughout, no atomics: the results
+ * are exact and the same on every run. The reference's distance is sqrt(D2) / 255.
+ *   cms_pd_box_sum   in: a plane (hp, wp) of int32 (in_is_int64 == 0) or int64 -> out (hp - ph + 1, wp - pw + 1) int64, the sum of
+ *                    every ph x pw window (any ph <= hp, pw <= wp, even ones too; hp * wp < 2^30); sums wrap at 64 bits. Two
+ *                    separable running-sum passes: the loads per output do not grow with the box. work: (hp - ph + 1) * wp int64,
+ *                    need not be initialised
+ *   cms_pd_neighbour_workspace_bytes   bytes of `work` below; 0 for sizes cms_pd_neighbour_maps refuses
+ *   cms_pd_neighbour_maps   entry_host as for cms_pd_load_image; ph, pw odd -> out_d2 int64 [4][hs][ws] in the order left, right,
+ *                    up, down (< 2^39 for the patch sizes patch_dist accepts). work need not be initialised. Five stream-ordered
+ *                    launches: the squared differences (two int32 planes), then two passes per plane pair
+ * Bad sizes or NULL pointers return CMS_EINVAL and launch nothing. */
+int cms_pd_box_sum(const void* in, int in_is_int64, int hp, int wp, int ph, int pw, void* work, int64_t* out, void* stream);
+size_t cms_pd_neighbour_workspace_bytes(int hs, int ws, int ph, int pw);
+int cms_pd_neighbour_maps(const uint8_t* pool_img, const cms_stage_entry* entry_host, int ph, int pw, void* work, int64_t* out_d2,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
