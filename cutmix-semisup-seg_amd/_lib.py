@@ -278,6 +278,8 @@ PROTOTYPES = {
     'cms_pd_box_sum': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'cms_pd_neighbour_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cms_pd_neighbour_maps': (c_int, [c_void_p, _P(StageEntry), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'cms_downsample_image_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cms_downsample_labels_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 fn = {}

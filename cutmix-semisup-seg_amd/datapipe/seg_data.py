@@ -1,7 +1,7 @@
 """
 The parts of the reference's datapipe/seg_data.py the device-side data path needs: the `DataSource` base (prediction files,
-default statistics), the endless sampler and -- in place of `DataLoader` + `SegCollate` -- the index streams and the canvas
-geometry of variable-sized evaluation batches.
+default statistics), `ZipDataSource` (samples that are members of one ZIP archive, read from many threads), the endless sampler
+and -- in place of `DataLoader` + `SegCollate` -- the index streams and the canvas geometry of variable-sized evaluation batches.
 
 Index streams. The reference samples with `RepeatSampler(SubsetRandomSampler(ndx))` through a `DataLoader`
 (train_seg_semisup_mask_mt.py:203-212, 251-253): an endless chain of `torch.randperm` permutations drawn from torch's GLOBAL
@@ -33,6 +33,108 @@ class DataSource(object):
     def get_mean_std(self):
         """ImageNet channel statistics, the default of every source"""
         return np.array([0.485, 0.456, 0.406]), np.array([0.229, 0.224, 0.225])
+
+
+_PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
+
+
+def labels_from_pil(img, name):
+    """A decoded label image -> uint8 (H, W), the values it stores. 8-bit greyscale / palette PNGs and 16- / 32-bit integer ones
+    both occur (the reference's Cityscapes converter saved a uint32 array); a value that does not fit a byte is refused, naming
+    the member."""
+    if img.mode not in ('L', 'P', 'I', 'I;16', 'I;16B', 'I;16L'):
+        raise ValueError('{}: a greyscale, palette or integer label map is expected, got mode {}'.format(name, img.mode))
+    arr = np.asarray(img)
+    if arr.dtype != np.uint8:
+        if arr.size and (int(arr.max()) > 255 or int(arr.min()) < 0):
+            raise ValueError('{}: label values {}..{} do not fit a byte (0..255 is what the label pipeline carries)'.format(
+                name, int(arr.min()), int(arr.max())))
+        arr = arr.astype(np.uint8)
+    return np.ascontiguousarray(arr)
+
+
+def png_size(head):
+    """(H, W) from the first 24 bytes of a PNG file, or None when they are not a PNG header"""
+    import struct
+    if len(head) >= 24 and head[:8] == _PNG_SIGNATURE and head[12:16] == b'IHDR':
+        w, h = struct.unpack('>II', head[16:24])
+        return int(h), int(w)
+    return None
+
+
+class ZipDataSource(DataSource):
+    """A data source whose samples are members of one ZIP archive (seg_data.py:156-173): the base of the CamVid, Cityscapes and
+    ISIC 2017 sources. A subclass fills `x_names` / `y_names` (member names, one per sample) and may override `map_labels`.
+
+    The pool decodes on up to 16 threads at once. One `ZipFile` serves them all: the raw bytes of a member are read under a
+    lock, and the decoding -- where the time goes, and where PIL lets go of the interpreter lock -- runs outside it."""
+
+    def __init__(self, zip_path):
+        import threading
+        import zipfile
+        self.zip_path = zip_path
+        self.zip_file = zipfile.ZipFile(zip_path, 'r')
+        self._zip_lock = threading.Lock()
+
+    def __len__(self):
+        return len(self.x_names)
+
+    def _read_file_from_zip_as_bytes(self, name, n_bytes=-1):
+        """the first `n_bytes` of a member (all of it with -1)"""
+        with self._zip_lock:
+            with self.zip_file.open(name) as f:
+                return f.read(n_bytes)
+
+    def get_pil_image(self, name):
+        import io
+        img = Image.open(io.BytesIO(self._read_file_from_zip_as_bytes(name)))
+        img.load()
+        return img
+
+    def get_image_size(self, sample_i):
+        return self.member_size(self.x_names[sample_i])
+
+    def member_size(self, name):
+        """-> (H, W) of an image member from its PNG header (the first 24 bytes): nothing is decoded"""
+        size = png_size(self._read_file_from_zip_as_bytes(name, 24))
+        if size is None:                                        # not a PNG: let PIL find the size in the whole member
+            import io
+            with Image.open(io.BytesIO(self._read_file_from_zip_as_bytes(name))) as img:
+                size = int(img.size[1]), int(img.size[0])
+        return size
+
+    def get_image_arr(self, sample_i):
+        """-> uint8 (H, W, 3) RGB"""
+        img = self.get_pil_image(self.x_names[sample_i])
+        return np.ascontiguousarray(np.asarray(img.convert('RGB'), dtype=np.uint8))
+
+    def get_raw_labels_arr(self, sample_i):
+        """-> uint8 (H, W): the values stored in the label member (labels_from_pil)"""
+        name = self.y_names[sample_i]
+        return labels_from_pil(self.get_pil_image(name), name)
+
+    def map_labels(self, y):
+        """stored values -> class indices (255 = void); the identity here"""
+        return y
+
+    def get_labels_arr(self, sample_i):
+        """-> uint8 (H, W) class indices, 255 = void"""
+        return np.ascontiguousarray(self.map_labels(self.get_raw_labels_arr(sample_i)), dtype=np.uint8)
+
+
+def hold_out_split(train_ndx, val_ndx, n_val, val_rng, trainval_perm):
+    """The hold-out rule the Cityscapes and ISIC 2017 sources share (cityscapes_dataset.py:90-108): `trainval_perm` re-orders the
+    training list; with n_val > 0 the validation list becomes the TEST set and the last n_val of the training list -- in that order,
+    or else in one drawn from val_rng -- the validation set. -> (train_ndx, val_ndx, test_ndx or None)"""
+    if trainval_perm is not None:
+        if len(trainval_perm) != len(train_ndx):
+            raise ValueError('trainval_perm has {} entries, the training list {}'.format(len(trainval_perm), len(train_ndx)))
+        train_ndx = train_ndx[np.asarray(trainval_perm)]
+    elif n_val > 0:
+        train_ndx = train_ndx[val_rng.permutation(len(train_ndx))]
+    if n_val > 0:
+        return train_ndx[:-n_val], train_ndx[-n_val:], val_ndx
+    return train_ndx, val_ndx, None
 
 
 class RepeatSampler(Sampler):

@@ -10,8 +10,8 @@ the cross-image lists keep a running best `--n_neighbours` per patch ordered by 
 same-image lists are replaced, as in the reference.
 
 Deviations from the reference:
-  * only `--dataset pascal` and `pascal_aug` are built and the default is `pascal_aug`, not `cityscapes`; any other choice stops
-    with the trainers' data set refusal before the GPU is touched
+  * only `--dataset pascal` and `pascal_aug` are built here and the default is `pascal_aug`, not `cityscapes`; any other choice
+    stops with a refusal before the GPU is touched (the trainers do read camvid, cityscapes and isic2017)
   * `--patch_size` must be odd; an even one is refused the same way (the reference's even-size geometry is off by one)
   * `--show_progress` falls back to no bar when tqdm is not importable
   * equal distances are ordered by pixel index, not by an unstable argsort
@@ -46,9 +46,9 @@ def intra_inter_class_patch_dist(out_path, dataset, patch_size, n_patches, n_nei
     from .datapipe import datasets
 
     # refusals come first: nothing below them has touched the GPU
-    if dataset not in datasets.BUILT:
-        raise SystemExit('The data set path is built for {} only; `{}` is not (its ZIP readers and load-time resizing are out of '
-                         'scope).'.format(' and '.join(datasets.BUILT), dataset))
+    if dataset not in datasets.TREE_SETS:
+        raise SystemExit('The patch-distance analysis is built for {} only; `{}` is not (the trainers read it, this program does '
+                         'not).'.format(' and '.join(datasets.TREE_SETS), dataset))
     if patch_size < 1 or patch_size % 2 == 0:
         raise SystemExit('--patch_size must be odd (got {}): the even-size patch geometry of the reference is off by one and is not '
                          'built.'.format(patch_size))

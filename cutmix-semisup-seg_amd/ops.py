@@ -1064,6 +1064,37 @@ def fill_holes(pred, out=None, truth=None, ignore_index=None, cm=None):
     return out, cm
 
 
+# ---------------------------------------------------------------------------------------------- converter downsampling
+def _downsample_u8(name, src, d, out, channels):
+    _need_cuda(src, out)
+    dims = 4 if channels == 3 else 3
+    if src.dtype != torch.uint8 or src.dim() != dims or (channels == 3 and int(src.shape[-1]) != 3):
+        raise TypeError('{}: a uint8 {} tensor is expected'.format(name, '(N,H,W,3)' if channels == 3 else '(N,H,W)'))
+    src = src.contiguous()
+    n, h, w, d = int(src.shape[0]), int(src.shape[1]), int(src.shape[2]), int(d)
+    if d < 1 or h % d or w % d:
+        raise ValueError('{}: {}x{} is not divisible by d={}'.format(name, h, w, d))
+    shape = (n, h // d, w // d) + ((3,) if channels == 3 else ())
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise TypeError('{}: out must be a contiguous uint8 tensor of shape {}'.format(name, shape))
+    check(fn[name](_ptr(src), n, h, w, d, _ptr(out), _stream()), name)
+    return out
+
+
+def downsample_image_u8(src, d, out=None):
+    """uint8 CUDA (N,H,W,3) -> (N,H/d,W/d,3): the mean of each d x d block per channel, truncated (the converter's
+    downscale_local_mean(...).astype(uint8), exactly floor(sum / d^2)). d in 1..8 divides H and W."""
+    return _downsample_u8('cms_downsample_image_u8', src, d, out, 3)
+
+
+def downsample_labels_u8(src, d, out=None):
+    """uint8 CUDA (N,H,W) -> (N,H/d,W/d): the most frequent value of each d x d block, the lowest value winning ties (the
+    converter's one-hot sum and argmax)."""
+    return _downsample_u8('cms_downsample_labels_u8', src, d, out, 1)
+
+
 # ---------------------------------------------------------------------------------------------- fp64 FFT / patch distances
 _TWIDDLES = {}
 

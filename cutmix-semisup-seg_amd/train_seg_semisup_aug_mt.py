@@ -6,7 +6,7 @@ lines, driving the MI355X iteration of aug.py.
 `--synthetic` (plus `--synthetic_n_classes`, `--synthetic_val_batches`) trains on synthetic tensors of the crop shape: the two
 views of an unsupervised batch are independent synthetic images, the PAIR GEOMETRY (xf0_to_1) is drawn by aug_pairs.py with the
 reference's draws for the given --aug_* options, and the validity masks are all-valid. `--compute_dtype` as in the other trainers.
-Without `--synthetic`, `--dataset pascal` / `pascal_aug` train on Pascal VOC from `./semantic_segmentation.cfg` through the
+Without `--synthetic`, `--dataset` (Pascal VOC, CamVid, Cityscapes, ISIC 2017) trains on what `./semantic_segmentation.cfg` locates, through the
 data set path the four trainers share (trainer_common.open_dataset / DatasetRun, as in train_seg_semisup_mask_mt.py): the
 reference's splits and index streams on the host, every image decoded once into an HBM-resident pool, training crops and padded
 evaluation batches gathered on the device; VAL mIoU every epoch, `--save_preds`, FINAL TEST with `--n_val`. One GPU, a
@@ -47,7 +47,7 @@ def train_seg_semisup_aug_mt(submit_config, dataset, model, arch, freeze_bn,
     from .aug_pairs import PairGeometry
 
     crop = tc.parse_crop_size(crop_size)
-    # Without --synthetic: the Pascal VOC data set path the four trainers share (trainer_common.py); refusals come first
+    # Without --synthetic: the data set path the four trainers share (trainer_common.py); refusals come first
     ds_dict = tc.open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
     # inherited, not chosen: the step has no data-parallel form, so more than one process is refused
     world, _, torch_device = tc.setup_process('train_seg_semisup_aug_mt', data_parallel=False,

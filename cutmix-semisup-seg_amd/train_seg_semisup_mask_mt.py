@@ -6,12 +6,13 @@ same 56 command-line options (names and defaults, train_seg_semisup_mask_mt.py:5
 Differences, all additive:
   * `--synthetic` (plus `--synthetic_n_classes`, `--synthetic_val_batches`) trains on synthetic tensors of the crop
     shape. Synthetic runs use `pretrained=False`.
-  * without `--synthetic`, `--dataset pascal` / `pascal_aug` train on Pascal VOC from `./semantic_segmentation.cfg`
+  * without `--synthetic`, `--dataset pascal` / `pascal_aug` / `camvid` / `cityscapes` / `isic2017` train on the data set that
+    `./semantic_segmentation.cfg` locates (a directory tree for Pascal VOC, one ZIP file each for the others)
     (settings.py, datapipe/; trainer_common.open_dataset / DatasetRun, shared by the four trainers): the reference's splits and
     index streams on the host, every image decoded once into an HBM-resident pool (resident_pool.py), training crops and padded evaluation batches gathered on the device
     (device_pipeline.DeviceAugmenter.stage / stage_eval, csrc/stage.hip); VAL mIoU every epoch, FINAL TEST with
     `--n_val`. One GPU, a `--crop_size` is required, weights from the package's initialisation (no pretrained
-    files here). The other three data sets stop with a clear message. On this path `--synthetic_source_size`,
+    files here). A data set whose location is not configured stops with a clear message. On this path `--synthetic_source_size`,
     `--synthetic_n_classes` and `--synthetic_val_batches` have no effect (sizes, classes and the validation set are the
     data set's), `--num_workers` is accepted and unused, and the crop / flip / colour / mask draws are unseeded numpy
     streams as in the reference (the index streams follow `torch.manual_seed`).
@@ -64,7 +65,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
 
     crop = tc.parse_crop_size(crop_size)
 
-    # Without --synthetic: the reference's data set path (:64-72) for Pascal VOC, shared by the four trainers (trainer_common.py)
+    # Without --synthetic: the reference's data set path (:64-72), shared by the four trainers (trainer_common.py)
     ds_dict = tc.open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
 
     world, rank, torch_device = tc.setup_process('train_seg_semisup_mask_mt', data_parallel=True)

@@ -4,7 +4,7 @@ command-line options (names and defaults, train_seg_semisup_vat_mt.py:592-644), 
 lines, driving the MI355X VAT iteration (vat.py). SURVEY.md 8(f) rank 2.
 
 `--synthetic` (plus `--synthetic_n_classes`, `--synthetic_val_batches`) trains on synthetic tensors of the crop shape, one
-process per GPU under torchrun; `--compute_dtype` as in the other trainers. Without `--synthetic`, `--dataset pascal` / `pascal_aug` train on Pascal VOC from `./semantic_segmentation.cfg` through the
+process per GPU under torchrun; `--compute_dtype` as in the other trainers. Without `--synthetic`, `--dataset` (Pascal VOC, CamVid, Cityscapes, ISIC 2017) trains on what `./semantic_segmentation.cfg` locates, through the
 data set path the four trainers share (trainer_common.open_dataset / DatasetRun, as in train_seg_semisup_mask_mt.py): the
 reference's splits and index streams on the host, every image decoded once into an HBM-resident pool, training crops and padded
 evaluation batches gathered on the device; VAL mIoU every epoch, `--save_preds`, FINAL TEST with `--n_val`. One GPU, a
@@ -43,7 +43,7 @@ def train_seg_semisup_vat_mt(submit_config, dataset, model, arch, freeze_bn,
     from .vat import VATMeanTeacherStep, VATConfig, VATUnsupBatch
 
     crop = tc.parse_crop_size(crop_size)
-    # Without --synthetic: the Pascal VOC data set path the four trainers share (trainer_common.py); refusals come first
+    # Without --synthetic: the data set path the four trainers share (trainer_common.py); refusals come first
     ds_dict = tc.open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
     world, rank, torch_device = tc.setup_process('train_seg_semisup_vat_mt', data_parallel=True)
 

@@ -1,9 +1,9 @@
 """
 What the four semi-supervised trainers (train_seg_semisup_mask_mt / _vat_mt / _ict / _aug_mt) have in common: the shared blocks
-of the reference's option tables, process and device set-up, networks and optimisers, synthetic data, the Pascal VOC data set
-path (pool, index streams, staged evaluation, prediction files, FINAL TEST), and the epoch loop with its bookkeeping and log
-lines. A trainer file keeps what is its own: its options, its config / step / batch construction and how
-it saves.
+of the reference's option tables, process and device set-up, networks and optimisers, synthetic data, the data set path of
+Pascal VOC, CamVid, Cityscapes and ISIC 2017 (pool, index streams, staged evaluation, prediction files, FINAL TEST), and the
+epoch loop with its bookkeeping and log lines. A trainer file keeps what is its own: its options, its config / step / batch
+construction and how it saves.
 
 Plain functions and one small class; what differs between trainers is a keyword argument or a callable passed in. torch is
 imported inside the functions, as in the trainers: importing a trainer (its command line, its configuration errors) loads no
@@ -128,7 +128,8 @@ def parse_crop_size(crop_size):
 
 def open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path):
     """The checks of a trainer's data before anything touches the GPU -> None with `--synthetic`, else the reference's data set
-    dictionary (datapipe.datasets.load_dataset: Pascal VOC, the splits made on the host exactly as the reference makes them).
+    dictionary (datapipe.datasets.load_dataset: any of the five data sets, the splits made on the host exactly as the reference makes
+    them).
     Whatever keeps the data set path from starting is a JobNotRun that says so and names `--synthetic`: no log is left behind."""
     import os
     if not synthetic:
@@ -273,7 +274,7 @@ class SyntheticData(object):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the data set path (Pascal VOC): what the reference's trainers do between `load_dataset` and `FINAL TEST`
+# the data set path (any source of datapipe.datasets.load_dataset): what the reference's trainers do between `load_dataset` and `FINAL TEST`
 def augmenter_options(settings):
     """The `--aug_*` options of a trainer (its `settings`) as the keyword arguments of device_pipeline.DeviceAugmenter."""
     s = settings
@@ -372,7 +373,7 @@ class DatasetRun(object):
         return lambda evaluator: self.staged_eval(eval_net, step, self.val_ndx, evaluator)
 
     def finish(self, eval_net, step, save_preds, submit_config, bin_fill_holes):
-        """After the last epoch: prediction files with `--save_preds` (the Pascal source inherits
+        """After the last epoch: prediction files with `--save_preds` (every source inherits
         DataSource.save_prediction_by_index), then the held-out test set and `FINAL TEST` when `--n_val` left one."""
         import os
         from . import evaluation

@@ -909,6 +909,17 @@ size_t cms_pd_neighbour_workspace_bytes(int hs, int ws, int ph, int pw);
 int cms_pd_neighbour_maps(const uint8_t* pool_img, const cms_stage_entry* entry_host, int ph, int pw, void* work, int64_t* out_d2,
                           void* stream);
 
+/* Downsampling of the Cityscapes converter (convert_cityscapes.py:17-24, 44-46), uint8 in and out, dense tensors:
+ *   cms_downsample_image_u8    (n, h, w, 3) -> (n, h / d, w / d, 3): the mean of each d x d block per channel, truncated, which is
+ *                    exactly floor(sum / d^2)
+ *   cms_downsample_labels_u8   (n, h, w) -> (n, h / d, w / d): the most frequent value of each d x d block, the lowest value among
+ *                    equally frequent ones (the reference's one-hot sum and argmax); any byte value is a label
+ * d = 1 copies. Integer arithmetic, no atomics: the results are the same on every run. NULL pointers, n < 1, d outside 1..8,
+ * h or w not divisible by d, or more than 2^31 - 1 bytes per tensor return CMS_EINVAL, decided before any HIP call; nothing is
+ * launched. src and dst must not overlap. */
+int cms_downsample_image_u8(const uint8_t* src, int n, int h, int w, int d, uint8_t* dst, void* stream);
+int cms_downsample_labels_u8(const uint8_t* src, int n, int h, int w, int d, uint8_t* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
