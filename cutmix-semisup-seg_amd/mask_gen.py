@@ -10,6 +10,9 @@ boxes, bit for bit), but what travels to the device is the (N, n_boxes, 4) int32
 [y0, y1, x0, x1]; kernels rasterise it on the fly (csrc/boxmask.hip, csrc/losses.hip). `generate_params` still
 returns the reference's float64 (N,1,H,W) array for drop-in use; `generate_ranges` + `torch_masks_from_params`
 is the device path.
+
+CowMaskGenerator is not in the reference, which only carries its scaffolding (the abstract `torch_masks_from_params`,
+`gaussian_kernels`): host draws of (p, sigma) per sample, the masks themselves made on the device (csrc/cowmask.hip).
 """
 import numpy as np
 import torch
@@ -34,8 +37,8 @@ class MaskGenerator(object):
 
 def gaussian_kernels(sigma, max_sigma=None, truncate=4.0):
     """Rows of normalised 1-D Gaussian kernels, one per entry of `sigma` ((N,) array), all of the width the LARGEST sigma asks
-    for (radius = int(truncate * max_sigma + 0.5)) -- mask_gen.py:26-43 of the reference, a host-side helper of its mask
-    generators that the CutMix trainer itself never calls; kept so that `import mask_gen` offers the reference's names."""
+    for (radius = int(truncate * max_sigma + 0.5)) -- mask_gen.py:26-43 of the reference, a host-side helper that nothing there
+    calls; here it is the tap table of CowMaskGenerator."""
     sigma = np.asarray(sigma, dtype=np.float64)
     if max_sigma is None:
         max_sigma = sigma.max()
@@ -134,6 +137,94 @@ class BoxMaskGenerator(MaskGenerator):
                 and t_params.shape[-1] == 4:
             return ops.boxmask_rasterize(t_params.to(torch_device), mask_shape, self.invert)
         return t_params
+
+
+class CowMaskGenerator(MaskGenerator):
+    """
+    CowMask (French, Oliver, Salimans, "Milking CowMask for semi-supervised image classification"): N(0,1) noise smoothed with a
+    Gaussian of a random sigma and thresholded so that a random share p of the pixels is 1. The family that the reference's abstract
+    `torch_masks_from_params` and its unused `gaussian_kernels` were scaffolding for; the reference itself has no such generator.
+
+    Host draws, one RandomState, in this order: p = uniform(p_lo, p_hi, N); sigma = exp(uniform(log s_lo, log s_hi, N)). The noise
+    is drawn on the device, and the blur, the statistics and the compare run there in fp64 (ops.cowmask, csrc/cowmask.hip):
+        s = taps (*)_y (taps (*)_x noise), zero padded;  mask = [s <= mean(s) + std(s) * Phi^-1(p)]
+    1 means "take image 1" in mix mode and "keep" in zero mode, like the default (inverted) box mask; there is no `invert`.
+    """
+
+    MAX_RADIUS = 128
+
+    def __init__(self, prop_range, sigma_range, truncate=4.0):
+        if isinstance(prop_range, (int, float)):
+            prop_range = (float(prop_range), float(prop_range))
+        if isinstance(sigma_range, (int, float)):
+            sigma_range = (float(sigma_range), float(sigma_range))
+        p_lo, p_hi = float(prop_range[0]), float(prop_range[1])
+        s_lo, s_hi = float(sigma_range[0]), float(sigma_range[1])
+        if not (0.0 <= p_lo <= p_hi <= 1.0):
+            raise ValueError('CowMaskGenerator: prop_range {}:{} is not inside [0, 1]'.format(p_lo, p_hi))
+        if not (s_lo > 0.0 and s_lo <= s_hi):
+            raise ValueError('CowMaskGenerator: sigma_range {}:{} needs 0 < lo <= hi'.format(s_lo, s_hi))
+        if not truncate > 0.0:
+            raise ValueError('CowMaskGenerator: truncate must be positive')
+        self.prop_range = (p_lo, p_hi)
+        self.sigma_range = (s_lo, s_hi)
+        self.truncate = float(truncate)
+        self.radius = int(self.truncate * s_hi + 0.5)
+        if self.radius > self.MAX_RADIUS:
+            raise ValueError('CowMaskGenerator: sigma up to {} at truncate {} needs a radius of {}; at most {} is built'.format(
+                s_hi, truncate, self.radius, self.MAX_RADIUS))
+
+    # ------------------------------------------------------------------ host
+    def generate_scalars(self, n_masks, rng=None):
+        """(p, sigma), float64 (N,) each: the only host draws."""
+        if rng is None:
+            rng = np.random
+        p = rng.uniform(self.prop_range[0], self.prop_range[1], size=(n_masks,))
+        sigma = np.exp(rng.uniform(np.log(self.sigma_range[0]), np.log(self.sigma_range[1]), size=(n_masks,)))
+        return p, sigma
+
+    def generate_params(self, n_masks, mask_shape, rng=None):
+        """float64 (N, 2) rows [p, sigma]: parameters on the host, masks from parameters on the device."""
+        p, sigma = self.generate_scalars(n_masks, rng)
+        return np.stack([p, sigma], axis=1)
+
+    def kernel_table(self, sigma):
+        """(taps float64 (N, 2R+1), R): every row as wide as the largest sigma of the RANGE asks for, normalised over that window"""
+        return gaussian_kernels(sigma, max_sigma=self.sigma_range[1], truncate=self.truncate), self.radius
+
+    @staticmethod
+    def threshold_factors(p):
+        """Phi^-1(p) in float64 (statistics.NormalDist); 0 at the end points p <= 0 and p >= 1, which are filled explicitly"""
+        from statistics import NormalDist
+        nd = NormalDist()
+        return np.array([nd.inv_cdf(float(v)) if 0.0 < v < 1.0 else 0.0 for v in p], dtype=np.float64)
+
+    # ------------------------------------------------------------------ device
+    def torch_masks_from_params(self, t_params, mask_shape, torch_device, noise=None, generator=None):
+        """(N, 2) [p, sigma] -> f32 (N,1,H,W) on `torch_device`. `noise`: f32 (N,1,H,W) standard normal; drawn with
+        torch.randn(generator=generator) on the device when not given."""
+        if torch.is_tensor(t_params):
+            t_params = t_params.detach().cpu().numpy()
+        params = np.asarray(t_params, dtype=np.float64)
+        if params.ndim != 2 or params.shape[1] != 2:
+            raise ValueError('CowMaskGenerator: params must be (N, 2) rows of [p, sigma], got {}'.format(params.shape))
+        p, sigma = params[:, 0], params[:, 1]
+        n, (H, W) = len(p), (int(mask_shape[0]), int(mask_shape[1]))
+        if not (np.all(sigma > 0.0) and np.all(sigma <= self.sigma_range[1] * (1.0 + 1e-12))):
+            raise ValueError('CowMaskGenerator: sigma outside (0, {}]'.format(self.sigma_range[1]))
+        taps, _ = self.kernel_table(sigma)
+        factors = self.threshold_factors(p)
+        if noise is None:
+            noise = torch.randn((n, 1, H, W), generator=generator, device=torch_device, dtype=torch.float32)
+        elif tuple(noise.shape) != (n, 1, H, W):
+            raise ValueError('CowMaskGenerator: noise has shape {}, {} expected'.format(tuple(noise.shape), (n, 1, H, W)))
+        masks = ops.cowmask(noise, taps, factors)
+        # the end points explicitly, not through infinite thresholds
+        for i in np.nonzero(p <= 0.0)[0]:
+            masks[int(i)].zero_()
+        for i in np.nonzero(p >= 1.0)[0]:
+            masks[int(i)].fill_(1.0)
+        return masks
 
 
 class AddMaskParamsToBatch(object):

@@ -1095,6 +1095,58 @@ def downsample_labels_u8(src, d, out=None):
     return _downsample_u8('cms_downsample_labels_u8', src, d, out, 1)
 
 
+# ---------------------------------------------------------------------------------------------- CowMask
+_COW_WORKSPACE = {}
+
+
+def _f64_on(t, device, shape, what):
+    """numpy / tensor -> contiguous float64 tensor of `shape` on `device`"""
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError('cowmask: {} has shape {}, {} expected'.format(what, tuple(t.shape), tuple(shape)))
+    if not t.is_cuda:
+        t = t.to(torch.float64).contiguous().pin_memory()          # as ranges_to_device: a copy the host does not wait for
+    return t.to(device=device, dtype=torch.float64, non_blocking=True).contiguous()
+
+
+def cowmask(noise, taps, thresh_factor, out=None, stats=None):
+    """noise f32 CUDA (N,1,H,W) or (N,H,W); taps float64 (N, 2R+1), one row of 1-D blur weights per sample; thresh_factor float64
+    (N,) -> f32 (N,1,H,W) mask = [s <= mean(s) + std(s) * thresh_factor], s = the noise blurred with the taps along x and along y
+    under zero padding, everything in fp64 (csrc/cowmask.hip). `taps` and `thresh_factor` may be numpy arrays (copied to the
+    device). `stats`: optional float64 CUDA (N, 2) that receives each sample's mean and std. Deterministic; R <= 128."""
+    _need_cuda(noise, out, stats)
+    if noise.dtype != torch.float32 or noise.dim() not in (3, 4) or (noise.dim() == 4 and noise.shape[1] != 1):
+        raise TypeError('cowmask: noise must be a float32 (N,1,H,W) or (N,H,W) tensor')
+    noise = noise.contiguous()
+    n, h, w = int(noise.shape[0]), int(noise.shape[-2]), int(noise.shape[-1])
+    k = int(taps.shape[-1])
+    if k < 1 or k % 2 == 0:
+        raise ValueError('cowmask: taps must have an odd number of columns (2R+1), got {}'.format(k))
+    radius = (k - 1) // 2
+    if radius > 128:
+        raise ValueError('cowmask: a radius of {} is not built (at most 128)'.format(radius))
+    taps = _f64_on(taps, noise.device, (n, k), 'taps')
+    thresh_factor = _f64_on(thresh_factor, noise.device, (n,), 'thresh_factor')
+    if out is None:
+        out = torch.empty((n, 1, h, w), dtype=torch.float32, device=noise.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, 1, h, w):
+        raise TypeError('cowmask: out must be a contiguous float32 tensor of shape {}'.format((n, 1, h, w)))
+    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or tuple(stats.shape) != (n, 2)):
+        raise TypeError('cowmask: stats must be a contiguous float64 tensor of shape {}'.format((n, 2)))
+    need = int(fn['cms_cowmask_workspace_bytes'](n, h, w))
+    if need == 0:
+        raise ValueError('cowmask: {} x {} x {} is more than the kernel takes'.format(n, h, w))
+    # one workspace per device, grown on demand: launches are stream-ordered, and a trainer makes its masks on one stream
+    key = str(noise.device)
+    ws = _COW_WORKSPACE.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _COW_WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=noise.device)
+    check(fn['cms_cowmask'](_ptr(noise), _ptr(taps), _ptr(thresh_factor), n, h, w, radius, _ptr(out), _ptr(stats), _ptr(ws),
+                            C.c_size_t(ws.numel()), _stream()), 'cms_cowmask')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- fp64 FFT / patch distances
 _TWIDDLES = {}
 

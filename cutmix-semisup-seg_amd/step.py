@@ -67,15 +67,21 @@ class StepConfig(object):
 class UnsupBatch(object):
     """
     One unsupervised batch in the reference's layout. `ranges` replaces the full-resolution
-    `mask_params`; `*_stu` default to the teacher images (no colour augmentation pair).
+    `mask_params`; `*_stu` default to the teacher images (no colour augmentation pair). Exactly one of `ranges` (an int32 (N, nb, 4)
+    box table, rasterised inside the kernels under `cfg.cons.invert`) and `mask` (a materialised f32 (N,1,H,W) mask, 1 = "take
+    image 1" / "keep", used as it is: `invert` does not apply -- mask_gen.CowMaskGenerator) is given: both are refused here, neither
+    by the paste of the step that is handed the batch (host-side callers build batches without either to ask about shapes).
     """
 
-    def __init__(self, x0_tea, ranges, um0=None, x1_tea=None, um1=None, x0_stu=None, x1_stu=None):
+    def __init__(self, x0_tea, ranges=None, um0=None, x1_tea=None, um1=None, x0_stu=None, x1_stu=None, mask=None):
+        if ranges is not None and mask is not None:
+            raise ValueError('UnsupBatch: give exactly one of ranges / mask')
         self.x0_tea, self.x1_tea = x0_tea, x1_tea
         self.x0_stu = x0_tea if x0_stu is None else x0_stu
         self.x1_stu = x1_tea if x1_stu is None else x1_stu
         self.um0, self.um1 = um0, um1
         self.ranges = ranges
+        self.mask = mask
 
 
 # ---------------------------------------------------------------------------------------------- shared with the VAT step (vat.py)
@@ -377,8 +383,8 @@ class CutMixMeanTeacherStep(object):
     def _student_inputs(self, ub):
         cfg = self.cfg
         if cfg.mix:
-            return ops.cutmix_paste(ub.x0_stu, ub.x1_stu, ranges=ub.ranges, invert=cfg.cons.invert)
-        return ops.cutmix_paste(None, ub.x0_stu, ranges=ub.ranges, invert=cfg.cons.invert)      # x * m
+            return ops.cutmix_paste(ub.x0_stu, ub.x1_stu, ranges=ub.ranges, invert=cfg.cons.invert, mask=ub.mask)
+        return ops.cutmix_paste(None, ub.x0_stu, ranges=ub.ranges, invert=cfg.cons.invert, mask=ub.mask)      # x * m
 
     # ------------------------------------------------------------------------------------------ separate passes (+ hipGraph replay)
     def _separate_passes(self, sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup, allow_overlap=True):
@@ -413,7 +419,7 @@ class CutMixMeanTeacherStep(object):
                 ls = self.student.forward_lowres(x_stu)
                 if overlap and bi == 0:
                     main.wait_stream(side)
-                sc, cctx = ops.consistency_forward(cfg.cons, ls.detach(), l0, l1, out_size, ranges=ub.ranges,
+                sc, cctx = ops.consistency_forward(cfg.cons, ls.detach(), l0, l1, out_size, ranges=ub.ranges, mask=ub.mask,
                                                    um0=ub.um0, um1=ub.um1, ramp_val=ramp,
                                                    cons_weight=cfg.cons_weight, group=self.group)
                 ls.backward(ops.consistency_backward(cctx, sc).to(ls.dtype))
@@ -440,13 +446,13 @@ class CutMixMeanTeacherStep(object):
             return self._separate_passes(sup_x, sup_y, unsup_batches, ramp, out_size, use_unsup)
         flat = [sup_x, sup_y]
         for u in (unsup_batches if use_unsup else ()):
-            flat += [u.x0_tea, u.x1_tea, u.x0_stu, u.x1_stu, u.ranges, u.um0, u.um1]
+            flat += [u.x0_tea, u.x1_tea, u.x0_stu, u.x1_stu, u.ranges, u.um0, u.um1, u.mask]
         extra = (float(ramp), tuple(out_size), bool(use_unsup), self.student.training, self.teacher.training,
                  getattr(self.student, 'compute_dtype', None), getattr(self.teacher, 'compute_dtype', None))
 
         def passes(ts, capturing):
-            ubs = [UnsupBatch(x0t, rg, um0=m0, x1_tea=x1t, um1=m1, x0_stu=x0s, x1_stu=x1s)
-                   for x0t, x1t, x0s, x1s, rg, m0, m1 in (ts[i:i + 7] for i in range(2, len(ts), 7))]
+            ubs = [UnsupBatch(x0t, rg, um0=m0, x1_tea=x1t, um1=m1, x0_stu=x0s, x1_stu=x1s, mask=mk)
+                   for x0t, x1t, x0s, x1s, rg, m0, m1, mk in (ts[i:i + 8] for i in range(2, len(ts), 8))]
             # the teacher's passes fork to their side stream inside the capture too (one fork, one join: 353 -> 413 img/s on the
             # ResNet-50 U-Net, 119 -> 140 on the DenseNet-161 U-Net; CMS_STEP_GRAPH_OVERLAP=0: one stream)
             overlap = not capturing or os.environ.get('CMS_STEP_GRAPH_OVERLAP', '1') != '0'
@@ -522,7 +528,7 @@ class CutMixMeanTeacherStep(object):
                 t_off += 2 * n if cfg.mix else n
                 # grad_lo's rows are zero here (filled above, disjoint per branch)
                 sc = ops.consistency_fused(cfg.cons, lo_det[s_off:s_off + n], l0, l1, out_size, grad_lo[s_off:s_off + n],
-                                           ranges=ub.ranges, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
+                                           ranges=ub.ranges, mask=ub.mask, um0=ub.um0, um1=ub.um1, ramp_val=ramp,
                                            cons_weight=cfg.cons_weight, group=self.group)
                 s_off += n
                 if split and isinstance(sc, torch.Tensor):

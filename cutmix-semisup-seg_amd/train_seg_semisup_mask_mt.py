@@ -20,6 +20,8 @@ Differences, all additive:
   * one process per GPU under torchrun (RANK / LOCAL_RANK / WORLD_SIZE); the reference is single-GPU (`cuda:0`, :58).
   * losses are accumulated on the device and read back once per epoch instead of three host syncs per iteration;
     the NaN bail (:469-472) fires one iteration late.
+  * the job body (`mask_mt_job`) is shared with train_seg_semisup_cowmask_mt.py, which differs in its mask generator and in the
+    options that generator reads; this command's option table, settings line and log are what they were.
 """
 import click
 
@@ -48,6 +50,42 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     settings = locals().copy()
     del settings['submit_config']
 
+    common = {k: v for k, v in settings.items() if not k.startswith('boxmask_')}
+
+    def box_masks(prop_range):
+        from . import mask_gen
+        return mask_gen.BoxMaskGenerator(prop_range=prop_range, n_boxes=boxmask_n_boxes,
+                                         random_aspect_ratio=not boxmask_fixed_aspect_ratio, prop_by_area=not boxmask_by_size,
+                                         within_bounds=not boxmask_outside_bounds, invert=not boxmask_no_invert)
+
+    # inherited, not chosen: only a NaN SUPERVISED loss ends the job, and the step's NaN flag is polled every iteration (the other
+    # three trainers check both losses and do not poll)
+    return mask_mt_job('train_seg_semisup_mask_mt', submit_config, settings, box_masks, invert=not boxmask_no_invert,
+                       nan_checks_consistency=False, polls_step_nan=True, **common)
+
+
+def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, nan_checks_consistency, polls_step_nan,
+                dataset, model, arch, freeze_bn,
+                opt_type, sgd_momentum, sgd_nesterov, sgd_weight_decay,
+                learning_rate, lr_sched, lr_step_epochs, lr_step_gamma, lr_poly_power,
+                teacher_alpha, bin_fill_holes,
+                crop_size, aug_hflip, aug_vflip, aug_hvflip, aug_scale_hung, aug_max_scale,
+                aug_scale_non_uniform, aug_rot_mag,
+                aug_strong_colour, aug_colour_brightness, aug_colour_contrast, aug_colour_saturation,
+                aug_colour_hue, aug_colour_prob, aug_colour_greyscale_prob,
+                mask_mode, mask_prop_range,
+                cons_loss_fn, cons_weight, conf_thresh, conf_per_pixel, rampup, unsup_batch_ratio,
+                num_epochs, iters_per_epoch, batch_size,
+                n_sup, n_unsup, n_val, split_seed, split_path, val_seed, save_preds, save_model,
+                num_workers,
+                synthetic=False, synthetic_n_classes=21, synthetic_val_batches=2, compute_dtype='bf16',
+                no_fuse_batches=False, synthetic_source_size='', deterministic=False,
+                allreduce_dtype='fp32', **mask_options):
+    """The body of the mask-driven mean-teacher commands: this one (box masks: CutMix / Cutout) and
+    train_seg_semisup_cowmask_mt (CowMix / CowOut). `settings` is what the command prints; `make_mask_generator(prop_range)` -> the
+    command's mask_gen.MaskGenerator. A generator with `generate_ranges` sends an int32 box table per batch (rasterised inside the
+    kernels under `invert`); any other makes its masks on the device from host parameters (`torch_masks_from_params`) and the step
+    takes the materialised mask. `mask_options`: options of the command that only its generator reads."""
     if ':' in mask_prop_range:
         lo, hi = mask_prop_range.split(':')
         mask_prop_range = (float(lo.strip()), float(hi.strip()))
@@ -60,7 +98,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     import os
     import numpy as np
     import torch
-    from . import mask_gen, lr_schedules, ops
+    from . import lr_schedules, ops
     from .step import CutMixMeanTeacherStep, StepConfig, UnsupBatch
 
     crop = tc.parse_crop_size(crop_size)
@@ -68,7 +106,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     # Without --synthetic: the reference's data set path (:64-72), shared by the four trainers (trainer_common.py)
     ds_dict = tc.open_dataset(synthetic, crop, dataset, n_val, val_seed, n_sup, n_unsup, split_seed, split_path)
 
-    world, rank, torch_device = tc.setup_process('train_seg_semisup_mask_mt', data_parallel=True)
+    world, rank, torch_device = tc.setup_process(job_name, data_parallel=True)
 
     n_classes = int(synthetic_n_classes)
     run = None
@@ -81,10 +119,8 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         return
     student_net, teacher_net, eval_net, student_optim, teacher_optim, dtype = nets
 
-    mask_generator = mask_gen.BoxMaskGenerator(prop_range=mask_prop_range, n_boxes=boxmask_n_boxes,
-                                               random_aspect_ratio=not boxmask_fixed_aspect_ratio,
-                                               prop_by_area=not boxmask_by_size,
-                                               within_bounds=not boxmask_outside_bounds, invert=not boxmask_no_invert)
+    mask_generator = make_mask_generator(mask_prop_range)
+    box_tables = hasattr(mask_generator, 'generate_ranges')
 
     if iters_per_epoch == -1:
         iters_per_epoch = 1000 if run is None else run.iters_per_epoch(iters_per_epoch)
@@ -94,7 +130,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
 
     step_cfg = StepConfig(mask_mode=mask_mode, cons_loss_fn=cons_loss_fn, cons_weight=cons_weight,
                           conf_thresh=conf_thresh, conf_per_pixel=conf_per_pixel, rampup=rampup,
-                          unsup_batch_ratio=unsup_batch_ratio, invert=not boxmask_no_invert,
+                          unsup_batch_ratio=unsup_batch_ratio, invert=invert,
                           fuse_batches=not no_fuse_batches, compute_dtype=dtype,
                           deterministic=deterministic, allreduce_dtype=allreduce_dtype)
     step = CutMixMeanTeacherStep(student_net, teacher_net, student_optim, teacher_optim, step_cfg)
@@ -103,6 +139,8 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     H, W = crop
     gen = torch.Generator(device=torch_device).manual_seed(12345 + rank)
     mask_rng = np.random.RandomState(12345 + rank)
+    # masks made on the device draw their noise from a generator of their own (the data stream above stays what it is)
+    noise_gen = None if box_tables else torch.Generator(device=torch_device).manual_seed(12345 + rank)
     data = tc.SyntheticData(gen, batch_size, crop, n_classes, dtype)
 
     # `--synthetic_source_size h,w`: the synthetic samples are uint8 SOURCE images of that size resident in HBM and every
@@ -113,6 +151,8 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         # the data set path: the same staging, every sample gathered from its own (variable-sized) pool entry. The reference
         # seeds none of its numpy draws; neither does this path. The two unsupervised streams share one sampler (:203-212)
         mask_rng = np.random.RandomState()
+        if noise_gen is not None:
+            noise_gen.seed()
         augment = run.make_streams(student_net, (H, W), dtype, settings,
                                    0 if cons_weight <= 0.0 else (2 if step_cfg.mix else 1))
     elif synthetic_source_size:
@@ -137,6 +177,13 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
     else:
         sup_iter, unsup_iter_0, unsup_iter_1 = (run.print_sizes_and_start(n_sup) + [None, None])[:3]
 
+    def make_mask():
+        """one batch of masks, outside any graph capture -> the `ranges=` or `mask=` argument of UnsupBatch"""
+        if box_tables:
+            return dict(ranges=ops.ranges_to_device(mask_generator.generate_ranges(batch_size, (H, W), rng=mask_rng), torch_device))
+        params = mask_generator.generate_params(batch_size, (H, W), rng=mask_rng)
+        return dict(mask=mask_generator.torch_masks_from_params(params, (H, W), torch_device, generator=noise_gen))
+
     def make_batch():
         if run is not None:
             sb = augment.stage(run.pool, next(sup_iter), True)
@@ -149,8 +196,7 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
         unsup = []
         if cons_weight > 0.0:
             for _r in range(unsup_batch_ratio):
-                rng_np = mask_generator.generate_ranges(batch_size, (H, W), rng=mask_rng)
-                ranges = ops.ranges_to_device(rng_np, torch_device)
+                mask_arg = make_mask()
                 if augment is not None:
                     if run is not None:
                         u0 = augment.stage(run.pool, next(unsup_iter_0), False)
@@ -158,25 +204,23 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                     else:
                         u0 = staged(False)
                         u1 = staged(False) if step_cfg.mix else None
-                    unsup.append(UnsupBatch(u0['image'], ranges, um0=u0['mask'],
+                    unsup.append(UnsupBatch(u0['image'], um0=u0['mask'],
                                             x1_tea=None if u1 is None else u1['image'],
                                             um1=None if u1 is None else u1['mask'], x0_stu=u0.get('image_stu'),
-                                            x1_stu=None if u1 is None else u1.get('image_stu')))
+                                            x1_stu=None if u1 is None else u1.get('image_stu'), **mask_arg))
                     continue
                 x0 = data.images()
                 x1 = data.images() if step_cfg.mix else None
                 x0s = data.images() if aug_strong_colour else None
                 x1s = data.images() if (aug_strong_colour and step_cfg.mix) else None
-                unsup.append(UnsupBatch(x0, ranges, x1_tea=x1, x0_stu=x0s, x1_stu=x1s))
+                unsup.append(UnsupBatch(x0, x1_tea=x1, x0_stu=x0s, x1_stu=x1s, **mask_arg))
         return batch_x, batch_y, unsup
 
     evaluate = run.evaluate_with(eval_net, step) if run is not None else data.evaluate_with(eval_net, step, synthetic_val_batches)
-    # inherited, not chosen: only a NaN SUPERVISED loss ends the job, and the step's NaN flag is polled every iteration (the other
-    # three trainers check both losses and do not poll); the confusion matrix is all_reduced and only rank 0 prints; this is
-    # the one trainer with the img/s line
+    # inherited, not chosen: the confusion matrix is all_reduced and only rank 0 prints; these are the trainers with the img/s line
     if not tc.run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, schedulers, num_epochs,
                          iters_per_epoch, freeze_bn, rampup, conf_thresh, n_classes, bin_fill_holes, torch_device,
-                         data_parallel=True, rank=rank, nan_checks_consistency=False, polls_step_nan=True,
+                         data_parallel=True, rank=rank, nan_checks_consistency=nan_checks_consistency, polls_step_nan=polls_step_nan,
                          img_per_s_of=(batch_size, world)):
         return
 

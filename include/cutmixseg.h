@@ -920,6 +920,22 @@ int cms_pd_neighbour_maps(const uint8_t* pool_img, const cms_stage_entry* entry_
 int cms_downsample_image_u8(const uint8_t* src, int n, int h, int w, int d, uint8_t* dst, void* stream);
 int cms_downsample_labels_u8(const uint8_t* src, int n, int h, int w, int d, uint8_t* dst, void* stream);
 
+/* CowMask (csrc/cowmask.hip): Gaussian-smoothed noise thresholded so that a chosen share of the pixels is 1.
+ *   noise          (n, h, w) f32
+ *   taps           (n, 2 * radius + 1) double: one row of 1-D weights per sample, applied along x and along y with ZERO padding
+ *   thresh_factor  (n) double: tau = mean(s) + std(s) * thresh_factor, the statistics over the sample's smoothed plane s, ddof = 0
+ *   mask_out       (n, h, w) f32 = [s <= tau]
+ *   stats_out      optional (n, 2) double = { mean, std }
+ *   workspace      cms_cowmask_workspace_bytes(n, h, w) bytes of device memory, need not be initialised; that function returns 0
+ *                  for sizes cms_cowmask refuses
+ * Everything after the f32 noise is fp64. Three stream-ordered launches, no atomics, every sum in a fixed order: the same input
+ * gives the same bits, and a sample's mask does not depend on the rest of its batch. NULL pointers (stats_out excepted),
+ * n, h or w < 1, radius < 0 or > 128, more than 2^31 - 1 pixels or a workspace that is too small return CMS_EINVAL, decided before
+ * any HIP call; nothing is launched. */
+size_t cms_cowmask_workspace_bytes(int n, int h, int w);
+int cms_cowmask(const float* noise, const double* taps, const double* thresh_factor, int n, int h, int w, int radius,
+                float* mask_out, double* stats_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
