@@ -126,6 +126,16 @@ class PdPatch(C.Structure):
     _fields_ = [('img_off', C.c_longlong), ('hs', c_int), ('ws', c_int), ('cy', c_int), ('cx', c_int)]
 
 
+TTA_MAX_VIEWS = 16
+
+
+class TtaDesc(C.Structure):
+    _fields_ = [('logits', c_void_p * TTA_MAX_VIEWS), ('h', c_int * TTA_MAX_VIEWS), ('w', c_int * TTA_MAX_VIEWS),
+                ('flip', c_int * TTA_MAX_VIEWS),
+                ('n', c_int), ('c', c_int), ('H', c_int), ('W', c_int), ('k', c_int), ('align_corners', c_int),
+                ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int), ('cm', c_void_p), ('pred_out', c_void_p)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('scale', c_void_p),
                 ('ntaps', c_int), ('cout', c_int), ('cin', c_int), ('first_block', c_int)]
@@ -283,6 +293,8 @@ PROTOTYPES = {
     'cms_cowmask_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cms_cowmask': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                             c_void_p]),
+    'cms_tta_resize': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'cms_tta_vote': (c_int, [_P(TtaDesc), c_void_p]),
 }
 
 fn = {}

@@ -1,0 +1,132 @@
+"""
+Score a trained model: `python eval_seg.py MODEL.pth --dataset pascal_aug [--subset val|test] [--scales 0.5,0.75,1,1.25,1.5,1.75]
+[--flip] [--batch_size 10] [--n_val -1] [--val_seed 131] [--split_path FILE] [--bin_fill_holes] [--save_preds DIR]
+[--compute_dtype bf16|fp32]`.
+
+The reference has no such program: it evaluates inside a training run only, at one scale without a flip. MODEL.pth is the whole-module
+pickle a trainer writes with `--save_model` (or the reference's own). The data set is opened exactly as the trainers open it
+(datapipe.datasets.load_dataset, `./semantic_segmentation.cfg`), so the same `--n_val` / `--val_seed` / `--split_path` give the same
+validation and test sets; only the chosen subset is decoded into the HBM-resident pool. Every batch goes through
+trainer_common.DatasetRun.staged_eval: whole images on a padded canvas, one forward pass per view (tta.TTA), one launch of the vote
+kernel (csrc/tta.hip). The output is the trainers': `VAL mIoU=...` (or `TEST mIoU=...`) and the `-- ` per-class line; with the defaults
+(`--scales 1`, no `--flip`) the numbers are bit for bit those of the trainer's last evaluation of that model.
+
+What keeps the program from starting is said before the GPU is touched: a model file that does not load, a data set that is not
+configured, `--subset test` without a held-out set, `--bin_fill_holes` on more than two classes, a model of another class count, bad
+`--scales`, more than one process.
+"""
+import os
+
+import click
+
+
+class EvalNotRun(click.ClickException):
+    """Why eval_seg does not start; click prints it and exits non-zero."""
+
+
+def model_num_classes(net):
+    """The class count of a loaded network: its `num_classes`, else the width of its last convolution."""
+    import torch
+    n = getattr(net, 'num_classes', None)
+    if n is not None:
+        return int(n)
+    convs = [m for m in net.modules() if isinstance(m, torch.nn.Conv2d)]
+    if not convs:
+        raise EvalNotRun('the model has no convolution to read a class count from')
+    return int(convs[-1].out_channels)
+
+
+def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes):
+    """Everything that can refuse, on the host -> (tta, net on the CPU, ds_dict, ndx)."""
+    from . import tta as tta_mod
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise EvalNotRun('eval_seg runs on one GPU: start one process (WORLD_SIZE={})'.format(os.environ['WORLD_SIZE']))
+    try:
+        tta = tta_mod.TTA(tta_mod.parse_scales(scales), flip)
+    except ValueError as e:
+        raise EvalNotRun(str(e))
+
+    from . import checkpoint, job_helper, settings
+    import torch
+    try:
+        net = checkpoint.load_model(model_path)
+    except Exception as e:           # whatever the file is instead of a module pickle
+        raise EvalNotRun('the model file {} does not load: {}: {}'.format(model_path, type(e).__name__, e))
+    if not isinstance(net, torch.nn.Module) or not hasattr(net, 'forward_lowres'):
+        raise EvalNotRun('the model file {} holds a {}, not a whole network of this project (a trainer writes one with '
+                         '--save_model)'.format(model_path, type(net).__name__))
+
+    from .datapipe import datasets
+    try:
+        ds_dict = datasets.load_dataset(dataset, n_val, val_seed, -1, -1, 12345, split_path)
+    except (settings.DataPathError, job_helper.JobNotRun) as e:
+        raise EvalNotRun(str(e))
+    ndx = ds_dict['val_ndx_tgt'] if subset == 'val' else ds_dict['test_ndx_tgt']
+    if ndx is None:
+        raise EvalNotRun('--subset test: --n_val {} leaves no test set (with --n_val > 0 the official validation list becomes '
+                         'the test set)'.format(n_val))
+    if len(ndx) == 0:
+        raise EvalNotRun('--subset {}: the set is empty'.format(subset))
+    n_classes = ds_dict['ds_src'].num_classes
+    if bin_fill_holes and n_classes != 2:
+        raise EvalNotRun('--bin_fill_holes: binary hole filling needs a binary (2-class) data set, {} has {} classes'.format(
+            dataset, n_classes))
+    if model_num_classes(net) != n_classes:
+        raise EvalNotRun('the model predicts {} classes, the data set {} has {}'.format(model_num_classes(net), dataset, n_classes))
+    return tta, net, ds_dict, ndx
+
+
+def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_size=10, n_val=-1, val_seed=131, split_path=None,
+             bin_fill_holes=False, save_preds=None, compute_dtype='bf16'):
+    """-> the per-class IoU (numpy); prints the trainers' lines."""
+    tta, net, ds_dict, ndx = prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes)
+
+    import types
+    import torch
+    from . import evaluation, trainer_common as tc
+    if not torch.cuda.is_available():
+        raise RuntimeError('eval_seg needs a GPU; there is no CPU fallback')
+    torch.cuda.set_device(0)
+    torch_device = torch.device('cuda', 0)
+    dtype = torch.bfloat16 if compute_dtype == 'bf16' else torch.float32
+    net = net.to(torch_device)
+    net.compute_dtype = dtype
+    for p in net.parameters():
+        p.requires_grad = False
+    net.eval()
+
+    run = tc.DatasetRun.for_evaluation(ds_dict, ndx, net, torch_device, batch_size, dtype)
+    step = types.SimpleNamespace(align_corners=getattr(net, 'upsample_align_corners', True))
+    if save_preds is not None:
+        os.makedirs(save_preds, exist_ok=True)
+    iou_eval = evaluation.EvaluatorIoU(run.n_classes, bin_fill_holes)
+    run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta)
+    iou = iou_eval.score()
+    print('{} mIoU={:.3%}'.format('VAL' if subset == 'val' else 'TEST', iou.mean()))
+    print('-- {}'.format(', '.join(['{:.3%}'.format(x) for x in iou])))
+    return iou
+
+
+@click.command()
+@click.argument('model_path', type=click.Path())
+@click.option('--dataset', type=click.Choice(['camvid', 'cityscapes', 'pascal', 'pascal_aug', 'isic2017']), default='pascal_aug')
+@click.option('--subset', type=click.Choice(['val', 'test']), default='val')
+@click.option('--scales', type=str, default='1')
+@click.option('--flip', is_flag=True, default=False)
+@click.option('--batch_size', type=int, default=10)
+@click.option('--n_val', type=int, default=-1)
+@click.option('--val_seed', type=int, default=131)
+@click.option('--split_path', type=click.Path(readable=True, exists=True))
+@click.option('--bin_fill_holes', is_flag=True, default=False)
+@click.option('--save_preds', type=click.Path(file_okay=False), default=None)
+@click.option('--compute_dtype', type=click.Choice(['bf16', 'fp32']), default='bf16')
+def experiment(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
+               compute_dtype):
+    if batch_size < 1:
+        raise EvalNotRun('--batch_size must be at least 1')
+    evaluate(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
+             compute_dtype)
+
+
+if __name__ == '__main__':
+    experiment()

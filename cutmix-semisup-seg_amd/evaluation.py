@@ -88,6 +88,17 @@ class EvaluatorIoU(object):
         ops.argmax_confusion(logits, truth, self.num_classes, out_size, ignore_index=ignore_value,
                              align_corners=align_corners, cm=self._cm())
 
+    def sample_logits_tta(self, logits_list, flips, truth, out_size, ignore_value=255, align_corners=True):
+        """sample_logits over the views of a batch (tta.TTA): the vote of ops.tta_vote in the place of the argmax."""
+        if self.fill_holes:
+            _, pred = ops.tta_vote(logits_list, flips, self.num_classes, out_size, align_corners=align_corners, want_pred=True)
+            t = truth[:, 0] if truth.dim() == 4 else truth
+            ops.fill_holes(pred, out=pred, truth=_to_u8_cuda(t, pred.device, 'truth'), ignore_index=ignore_value,
+                           cm=self._cm())
+            return
+        ops.tta_vote(logits_list, flips, self.num_classes, out_size, labels=truth, ignore_index=ignore_value,
+                     align_corners=align_corners, cm=self._cm())
+
     # reference attributes (float arrays, evaluation.py:49-51)
     @property
     def cm(self):

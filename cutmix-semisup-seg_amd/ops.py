@@ -1064,6 +1064,108 @@ def fill_holes(pred, out=None, truth=None, ignore_index=None, cm=None):
     return out, cm
 
 
+# ---------------------------------------------------------------------------------------------- test-time augmentation
+def _size2(size, what):
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise TypeError('{} must be a pair of integers, got {!r}'.format(what, size))
+    if h < 1 or w < 1:
+        raise ValueError('{} must be at least 1 x 1, got {} x {}'.format(what, h, w))
+    return h, w
+
+
+def tta_resize(image, size, flip=False, out=None):
+    """One view's input: image (N,C,H,W) fp32 / bf16 CUDA -> (N,C,Hs,Ws) of the same dtype, bilinear under align_corners=False
+    without antialiasing, mirrored along x with `flip` (csrc/tta.hip). `out`: a contiguous tensor of that shape and dtype to fill."""
+    if not torch.is_tensor(image) or image.dim() != 4:
+        raise TypeError('tta_resize: image must be an (N,C,H,W) tensor')
+    dtype = _dtype_code(image)
+    hs, ws = _size2(size, 'tta_resize: size')
+    _need_cuda(image, out)
+    image = image.contiguous()
+    n, c, h, w = (int(s) for s in image.shape)
+    if min(n, c, h, w) < 1:
+        raise ValueError('tta_resize: empty image {}'.format(tuple(image.shape)))
+    if n * c * max(h * w, hs * ws) > 2 ** 31 - 1:
+        raise ValueError('tta_resize: more than 2^31 - 1 elements')
+    if out is None:
+        out = torch.empty((n, c, hs, ws), dtype=image.dtype, device=image.device)
+    elif out.dtype != image.dtype or not out.is_contiguous() or tuple(out.shape) != (n, c, hs, ws):
+        raise TypeError('tta_resize: out must be a contiguous {} tensor of shape {}'.format(image.dtype, (n, c, hs, ws)))
+    check(fn['cms_tta_resize'](_ptr(image), _ptr(out), n, c, h, w, hs, ws, dtype, int(bool(flip)), _stream()), 'cms_tta_resize')
+    return out
+
+
+def tta_vote(logits_list, flips, num_classes, out_size, labels=None, ignore_index=255, align_corners=True, cm=None,
+             want_pred=False, pred=None):
+    """
+    The vote over the views of a batch (csrc/tta.hip): logits_list[i] (N,C,h_i,w_i) fp32 CUDA, flips[i] true where view i was
+    computed on the mirrored input. One view: upsample + argmax, exactly argmax_confusion; more: the softmax probabilities of the
+    views, each upsampled to `out_size` (a mirrored view read mirrored), summed in view order, argmax. labels (N,H,W) / (N,1,H,W)
+    uint8 / int64 or None. `pred`: a contiguous uint8 (N,H,W) tensor to fill (implies want_pred). Returns (cm int64 (C,C) CUDA
+    [accumulated into `cm` when given; None without labels], pred | None).
+    """
+    logits_list = list(logits_list)
+    flips = [bool(f) for f in flips]
+    k = len(logits_list)
+    if k < 1 or k > _lib.TTA_MAX_VIEWS:
+        raise ValueError('tta_vote: {} views, 1 to {} are built'.format(k, _lib.TTA_MAX_VIEWS))
+    if len(flips) != k:
+        raise ValueError('tta_vote: {} views but {} flips'.format(k, len(flips)))
+    if any(not torch.is_tensor(t) or t.dim() != 4 for t in logits_list):
+        raise TypeError('tta_vote: every view must be an (N,C,h,w) tensor')
+    num_classes = int(num_classes)
+    if num_classes < 1 or num_classes > 64:
+        raise ValueError('tta_vote: 1 <= num_classes <= 64, got {}'.format(num_classes))
+    H, W = _size2(out_size, 'tta_vote: out_size')
+    n = int(logits_list[0].shape[0])
+    for t in logits_list:
+        if int(t.shape[0]) != n or int(t.shape[1]) != num_classes or min(int(s) for s in t.shape) < 1:
+            raise ValueError('tta_vote: a view of shape {} among views of {} samples and {} classes'.format(
+                tuple(t.shape), n, num_classes))
+    if n * H * W > 2 ** 31 - 1:
+        raise ValueError('tta_vote: more than 2^31 - 1 output pixels')
+    if labels is not None:
+        if not torch.is_tensor(labels) or labels.dtype not in (torch.uint8, torch.int64):
+            raise TypeError('tta_vote: labels must be a uint8 or int64 tensor')
+        if labels.dim() == 4:
+            labels = labels[:, 0]
+        if tuple(labels.shape) != (n, H, W):
+            raise ValueError('tta_vote: labels of shape {}, {} expected'.format(tuple(labels.shape), (n, H, W)))
+    if cm is not None:
+        if labels is None:
+            raise ValueError('tta_vote: cm given without labels')
+        if cm.dtype != torch.int64 or tuple(cm.shape) != (num_classes, num_classes) or not cm.is_contiguous():
+            raise TypeError('tta_vote: cm must be a contiguous int64 ({0},{0}) matrix'.format(num_classes))
+    if pred is not None:
+        if not torch.is_tensor(pred) or pred.dtype != torch.uint8 or not pred.is_contiguous() or tuple(pred.shape) != (n, H, W):
+            raise TypeError('tta_vote: pred must be a contiguous uint8 tensor of shape {}'.format((n, H, W)))
+        want_pred = True
+    if labels is None and not want_pred:
+        raise ValueError('tta_vote: nothing to produce (no labels and want_pred is False)')
+    _need_cuda(labels, cm, pred, *logits_list)
+    views = [_f32c(t) for t in logits_list]         # kept alive until the launch is queued
+    dev = views[0].device
+    if labels is not None:
+        labels = labels.contiguous()
+        if cm is None:
+            cm = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=dev)
+    if want_pred and pred is None:
+        pred = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    d = _lib.TtaDesc()
+    for i, t in enumerate(views):
+        d.logits[i], d.h[i], d.w[i], d.flip[i] = t.data_ptr(), int(t.shape[2]), int(t.shape[3]), int(flips[i])
+    d.n, d.c, d.H, d.W, d.k, d.align_corners = n, num_classes, H, W, k, int(bool(align_corners))
+    d.labels = labels.data_ptr() if labels is not None else None
+    d.label_dtype = _lib.LABEL_I64 if labels is not None and labels.dtype == torch.int64 else _lib.LABEL_U8
+    d.ignore_index = -1 if ignore_index is None else int(ignore_index)
+    d.cm = cm.data_ptr() if cm is not None else None
+    d.pred_out = pred.data_ptr() if pred is not None else None
+    check(fn['cms_tta_vote'](C.byref(d), _stream()), 'cms_tta_vote')
+    return cm, pred
+
+
 # ---------------------------------------------------------------------------------------------- converter downsampling
 def _downsample_u8(name, src, d, out, channels):
     _need_cuda(src, out)

@@ -308,6 +308,26 @@ class DatasetRun(object):
         print('Resident pool: {} samples, {:.1f} MB in HBM, decoded in {:.1f}s'.format(
             len(self.pool), self.pool.nbytes() / 1e6, time.time() - t0))
 
+    @classmethod
+    def for_evaluation(cls, ds_dict, ndx, net, torch_device, batch_size, dtype):
+        """A run that only evaluates `net` over the samples `ndx` (eval_seg): the pool holds nothing else, and the augmenter is
+        what make_streams builds (statistics from the network, else the source), with no training crop and no index streams."""
+        from .resident_pool import ResidentPool
+        from .device_pipeline import DeviceAugmenter
+        run = cls.__new__(cls)
+        run.ds_src = ds_dict['ds_src']
+        run.val_ndx, run.test_ndx = ds_dict['val_ndx_tgt'], ds_dict['test_ndx_tgt']
+        run.sup_ndx, run.unsup_ndx = ds_dict['sup_ndx'], ds_dict['unsup_ndx']
+        run.n_classes = run.ds_src.num_classes
+        run.batch_size = batch_size
+        run.pool = ResidentPool(run.ds_src, list(ndx), torch_device)
+        mean, std = run.ds_src.get_mean_std()
+        mean = net.MEAN if net.MEAN is not None else mean
+        std = net.STD if net.STD is not None else std
+        run.student_net = net
+        run.augment = DeviceAugmenter((1, 1), mean, std, out_dtype=dtype)
+        return run
+
     def iters_per_epoch(self, iters_per_epoch):
         """`--iters_per_epoch -1` is len(unsup_ndx) // batch_size in all four reference trainers."""
         if iters_per_epoch != -1:
@@ -347,9 +367,10 @@ class DatasetRun(object):
             print('sup_ndx={}'.format(self.sup_ndx.tolist()))
         return [iter(st) for st in self._streams]
 
-    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None):
+    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None):
         """The reference's evaluation loop over `ndx` in index order: whole images, centred on a padded canvas per batch
-        (stage_eval); padding carries label 255 and is ignored."""
+        (stage_eval); padding carries label 255 and is ignored. With a `tta.TTA` every batch is evaluated as the vote over its
+        views (eval_seg); `step` is read for `align_corners` only."""
         import numpy as np
         import torch
         from . import ops
@@ -357,13 +378,19 @@ class DatasetRun(object):
         with torch.no_grad():
             for batch_ndx in seg_data.eval_batches(ndx, self.batch_size):
                 ev = self.augment.stage_eval(self.pool, batch_ndx, self.student_net.BLOCK_SIZE)
-                logits = eval_net.forward_lowres(ev['image'])
-                if evaluator is not None:
-                    evaluator.sample_logits(logits, ev['labels'], ev['canvas'], ignore_value=255,
-                                            align_corners=step.align_corners)
+                if tta is not None:
+                    _, pred = tta.predict(eval_net, ev['image'], ev['canvas'], step.align_corners, labels=ev['labels'],
+                                          ignore_index=255, want_pred=preds_dir is not None,
+                                          block_size=self.student_net.BLOCK_SIZE, evaluator=evaluator)
+                else:
+                    logits = eval_net.forward_lowres(ev['image'])
+                    if evaluator is not None:
+                        evaluator.sample_logits(logits, ev['labels'], ev['canvas'], ignore_value=255,
+                                                align_corners=step.align_corners)
+                    if preds_dir is not None:
+                        _, pred = ops.argmax_confusion(logits, None, self.n_classes, ev['canvas'],
+                                                       align_corners=step.align_corners, want_pred=True)
                 if preds_dir is not None:
-                    _, pred = ops.argmax_confusion(logits, None, self.n_classes, ev['canvas'],
-                                                   align_corners=step.align_corners, want_pred=True)
                     pred = pred.cpu().numpy()
                     for k, sample_ndx in enumerate(batch_ndx):
                         self.ds_src.save_prediction_by_index(preds_dir, pred[k].astype(np.uint32), sample_ndx)

@@ -936,6 +936,46 @@ size_t cms_cowmask_workspace_bytes(int n, int h, int w);
 int cms_cowmask(const float* noise, const double* taps, const double* thresh_factor, int n, int h, int w, int radius,
                 float* mask_out, double* stats_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Test-time augmentation (csrc/tta.hip): the inputs of the scaled / mirrored views of an evaluation batch, and the vote that fuses
+ * the views' low-resolution logits into one prediction. The reference evaluates at one scale without a flip; this goes beyond it.
+ *
+ * cms_tta_resize: one view's input.
+ *   src            (n, c, H, W), dst (n, c, Hs, Ws), both of `dtype` (CMS_F32 / CMS_BF16), dense; must not overlap
+ *   dst[.., y, xd] the bilinear sample of src at output pixel (y, x) under align_corners=False (no antialiasing; up- and
+ *                  down-scaling alike), xd = flip ? Ws - 1 - x : x. The sample position (y + 0.5) * H / Hs - 0.5 is worked out exactly
+ *                  in integers; the interpolation is fp32 in the order of the upsampling kernels, rounded once to `dtype`. Every
+ *                  element of dst is written.
+ * NULL pointers, a size below 1, an unknown dtype or more than 2^31 - 1 elements in src or dst return CMS_EINVAL.
+ *
+ * cms_tta_vote: per output pixel (y, x) of (n, H, W), with v_ic the bilinear sample (under `align_corners`) of view i's logits of
+ * class c, a flipped view read mirrored along x:
+ *   k == 1   score_c = v_0c: prediction, histogram and the identity-size fast path are bit for bit cms_argmax_confusion's, NaN rule
+ *            included
+ *   k >= 2   score_c = p_0c + p_1c + ..., p_i = softmax(v_i) (max, exponentials summed in class order, one reciprocal, rounded
+ *            products), summed in view order in fp32; non-finite logits are outside the contract
+ *   pred     the first index of the largest score
+ *   logits[i]      (n, c, h[i], w[i]) f32, i < k <= CMS_TTA_MAX_VIEWS; flip[i] != 0: the view was computed on the mirrored input
+ *   labels         optional (n, H, W) uint8 / int64 (label_dtype); needed with cm
+ *   cm             optional int64 (c, c) += histogram of (label, pred) over pixels with label != ignore_index (< 0: none)
+ *   pred_out       optional uint8 (n, H, W)
+ * One launch; the histogram is integer (LDS atomics, one 64-bit atomic per non-empty bin): the same input gives the same bits, and
+ * a sample's prediction does not depend on the rest of its batch. A NULL descriptor, k outside 1..16, c outside 1..64, any of n, H,
+ * W, h[i], w[i] below 1, a NULL logits[i], cm without labels, neither cm nor pred_out, an unknown label_dtype with labels, or more
+ * than 2^31 - 1 output pixels return CMS_EINVAL, decided before any HIP call; nothing is launched. */
+#define CMS_TTA_MAX_VIEWS 16
+typedef struct {
+    const float* logits[CMS_TTA_MAX_VIEWS];
+    int h[CMS_TTA_MAX_VIEWS], w[CMS_TTA_MAX_VIEWS], flip[CMS_TTA_MAX_VIEWS];
+    int n, c, H, W, k, align_corners;
+    const void* labels;
+    int label_dtype;      /* CMS_LABEL_U8 / CMS_LABEL_I64 */
+    int ignore_index;
+    int64_t* cm;
+    uint8_t* pred_out;
+} cms_tta_desc;
+int cms_tta_resize(const void* src, void* dst, int n, int c, int H, int W, int Hs, int Ws, int dtype, int flip, void* stream);
+int cms_tta_vote(const cms_tta_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
