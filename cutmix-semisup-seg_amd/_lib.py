@@ -136,6 +136,13 @@ class TtaDesc(C.Structure):
                 ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int), ('cm', c_void_p), ('pred_out', c_void_p)]
 
 
+class ClassMixDesc(C.Structure):
+    _fields_ = [('logits', c_void_p), ('valid', c_void_p), ('keys', c_void_p),
+                ('n', c_int), ('c', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int), ('align_corners', c_int),
+                ('mask_out', c_void_p), ('pred_out', c_void_p), ('present_out', c_void_p), ('chosen_out', c_void_p),
+                ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('scale', c_void_p),
                 ('ntaps', c_int), ('cout', c_int), ('cin', c_int), ('first_block', c_int)]
@@ -295,6 +302,8 @@ PROTOTYPES = {
                             c_void_p]),
     'cms_tta_resize': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'cms_tta_vote': (c_int, [_P(TtaDesc), c_void_p]),
+    'cms_classmix_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'cms_classmix': (c_int, [_P(ClassMixDesc), c_void_p]),
 }
 
 fn = {}

@@ -13,6 +13,9 @@ is the device path.
 
 CowMaskGenerator is not in the reference, which only carries its scaffolding (the abstract `torch_masks_from_params`,
 `gaussian_kernels`): host draws of (p, sigma) per sample, the masks themselves made on the device (csrc/cowmask.hip).
+
+ClassMixGenerator is not in the reference either: host draws of one key per sample and class, the masks cut along the teacher's
+predicted class regions on the device (csrc/classmix.hip).
 """
 import numpy as np
 import torch
@@ -225,6 +228,35 @@ class CowMaskGenerator(MaskGenerator):
         for i in np.nonzero(p >= 1.0)[0]:
             masks[int(i)].fill_(1.0)
         return masks
+
+
+class ClassMixGenerator(MaskGenerator):
+    """
+    ClassMix (Olsson, Tranheden, Pinto, Svensson, "ClassMix: Segmentation-Based Data Augmentation for Semi-Supervised Learning",
+    WACV 2021): the mask of a sample is the region that the teacher predicts, on image 1, to belong to a random half of the classes
+    it predicts there. Not in the reference. 1 means "take image 1", like the default (inverted) box mask; there is no `invert`.
+
+    Host draw, one RandomState, ONE call per batch: keys = rng.random_sample((N, n_classes)), row n for sample n. Everything else
+    runs on the device (ops.classmix_mask, csrc/classmix.hip): the full-resolution argmax of the teacher's low-resolution logits,
+    the set of classes present among the sample's valid pixels, and of its m classes the k = (m + 1) // 2 with the smallest (key,
+    class index) -- a uniformly random subset of that size, since the keys are i.i.d. k = ceil(m / 2) is the rule of the authors'
+    published code as far as we recall it; it has not been tuned here.
+
+    `needs_teacher` tells train_seg_semisup_mask_mt.mask_mt_job to make the mask after the unsupervised images are staged, from the
+    teacher's logits of image 1 (`torch_masks_from_logits`); there is no `generate_ranges`, so the step takes a materialised mask.
+    """
+
+    needs_teacher = True
+
+    def generate_params(self, n_masks, n_classes, rng=None):
+        """float64 (N, n_classes) keys, uniform on [0, 1): the only host draw"""
+        if rng is None:
+            rng = np.random
+        return rng.random_sample((int(n_masks), int(n_classes)))
+
+    def torch_masks_from_logits(self, keys, logits, out_size, align_corners, valid=None):
+        """keys (N, C) from generate_params, logits (N, C, h, w) on the device, valid optional f32 (N,1,H,W) -> f32 (N,1,H,W)"""
+        return ops.classmix_mask(logits, keys, out_size, align_corners=align_corners, valid=valid)
 
 
 class AddMaskParamsToBatch(object):

@@ -155,7 +155,12 @@ def _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size):
 
 def _workspace(name, d, device):
     """uninitialised scratch of the size cms_<name>_workspace_bytes asks for"""
-    return torch.empty(max(int(fn['cms_{}_workspace_bytes'.format(name)](C.byref(d))), 16), dtype=torch.uint8, device=device)
+    return _workspace_bytes(int(fn['cms_{}_workspace_bytes'.format(name)](C.byref(d))), device)
+
+
+def _workspace_bytes(nbytes, device):
+    """uninitialised scratch of `nbytes` (at least 16) from torch's caching allocator: no allocation call once the size has been seen"""
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
 def _check_grad_out(who, grad_out, like):
@@ -1246,6 +1251,86 @@ def cowmask(noise, taps, thresh_factor, out=None, stats=None):
         ws = _COW_WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=noise.device)
     check(fn['cms_cowmask'](_ptr(noise), _ptr(taps), _ptr(thresh_factor), n, h, w, radius, _ptr(out), _ptr(stats), _ptr(ws),
                             C.c_size_t(ws.numel()), _stream()), 'cms_cowmask')
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- ClassMix
+def _classmix_keys(keys, n, c, device):
+    """host array / tensor of (n, c) keys -> contiguous float64 tensor on `device`; shape and (on the host) finiteness checked
+    before the GPU is touched"""
+    if torch.is_tensor(keys):
+        if tuple(keys.shape) != (n, c):
+            raise ValueError('classmix_mask: keys have shape {}, {} expected'.format(tuple(keys.shape), (n, c)))
+        if keys.is_cuda:
+            if keys.dtype != torch.float64:
+                raise TypeError('classmix_mask: device keys must be float64, got {}'.format(keys.dtype))
+            return keys.contiguous()
+        keys = keys.detach().numpy()
+    keys = np.ascontiguousarray(keys, dtype=np.float64)
+    if keys.shape != (n, c):
+        raise ValueError('classmix_mask: keys have shape {}, {} expected'.format(keys.shape, (n, c)))
+    if not np.all(np.isfinite(keys)):
+        raise ValueError('classmix_mask: keys must be finite')
+    return None if device is None else _f64_on(keys, device, (n, c), 'keys')
+
+
+def classmix_mask(logits, keys, out_size, align_corners=True, valid=None, out=None, pred_out=None, sets_out=None):
+    """
+    The ClassMix mask of a batch (csrc/classmix.hip): logits (N,C,h,w) CUDA (converted to fp32 as tta_vote does), keys float64 (N,C)
+    -- a host array or a device tensor --, valid optional f32 (N,1,H,W) / (N,H,W). Per sample: pred = the argmax of the logits
+    upsampled to `out_size` (bit for bit tta_vote's single-view prediction), present = the classes predicted at some pixel with
+    valid != 0, chosen = the ceil(|present| / 2) present classes with the smallest (key, class index), mask = 1 where valid != 0 and
+    pred is chosen. Returns the f32 (N,1,H,W) mask (`out` when given). `pred_out`: a contiguous uint8 (N,H,W) tensor that receives
+    pred; `sets_out`: a contiguous int64 (N,2) tensor that receives [present, chosen] as 64-bit sets (bit 63 is the sign bit). Two
+    launches on the current stream, no host synchronisation; the same inputs give the same bits.
+    """
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise TypeError('classmix_mask: logits must be an (N,C,h,w) tensor')
+    n, c, h, w = (int(s) for s in logits.shape)
+    if min(n, c, h, w) < 1:
+        raise ValueError('classmix_mask: empty logits {}'.format(tuple(logits.shape)))
+    if c > 64:
+        raise ValueError('classmix_mask: 1 <= num_classes <= 64, got {}'.format(c))
+    H, W = _size2(out_size, 'classmix_mask: out_size')
+    _classmix_keys(keys, n, c, None)                       # shape and finiteness, before the GPU is touched
+    _need_cuda(logits, valid, out, pred_out, sets_out)
+    if n > 65535 or n * H * W > 2 ** 31 - 1:
+        raise ValueError('classmix_mask: more than 65535 samples or 2^31 - 1 output pixels')
+    logits = _f32c(logits)
+    dev = logits.device
+    keys = _classmix_keys(keys, n, c, dev)
+    if valid is not None:
+        if valid.dim() == 4 and valid.shape[1] == 1:
+            valid = valid[:, 0]
+        if tuple(valid.shape) != (n, H, W):
+            raise ValueError('classmix_mask: valid has shape {}, {} expected'.format(tuple(valid.shape), (n, H, W)))
+        valid = _f32c(valid)
+    if out is None:
+        out = torch.empty((n, 1, H, W), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, 1, H, W):
+        raise TypeError('classmix_mask: out must be a contiguous float32 tensor of shape {}'.format((n, 1, H, W)))
+    if pred_out is not None and (pred_out.dtype != torch.uint8 or not pred_out.is_contiguous() or tuple(pred_out.shape) != (n, H, W)):
+        raise TypeError('classmix_mask: pred_out must be a contiguous uint8 tensor of shape {}'.format((n, H, W)))
+    if sets_out is not None and (sets_out.dtype != torch.int64 or not sets_out.is_contiguous() or tuple(sets_out.shape) != (n, 2)):
+        raise TypeError('classmix_mask: sets_out must be a contiguous int64 tensor of shape {}'.format((n, 2)))
+    d = _lib.ClassMixDesc()
+    d.logits, d.valid, d.keys = logits.data_ptr(), (valid.data_ptr() if valid is not None else None), keys.data_ptr()
+    d.n, d.c, d.h, d.w, d.H, d.W, d.align_corners = n, c, h, w, H, W, int(bool(align_corners))
+    d.mask_out = out.data_ptr()
+    d.pred_out = pred_out.data_ptr() if pred_out is not None else None
+    sets = None
+    if sets_out is not None:
+        # the kernel writes (n) words each: a (2, n) staging tensor, transposed into the caller's (n, 2)
+        sets = torch.empty((2, n), dtype=torch.int64, device=dev)
+        d.present_out, d.chosen_out = sets[0].data_ptr(), sets[1].data_ptr()
+    need = int(fn['cms_classmix_workspace_bytes'](n, H, W))
+    if need == 0:
+        raise ValueError('classmix_mask: {} x {} x {} is more than the kernel takes'.format(n, H, W))
+    ws = _workspace_bytes(need, dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(fn['cms_classmix'](C.byref(d), _stream()), 'cms_classmix')
+    if sets is not None:
+        sets_out.copy_(sets.t())
     return out
 
 

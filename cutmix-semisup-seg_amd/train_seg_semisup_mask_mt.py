@@ -20,8 +20,8 @@ Differences, all additive:
   * one process per GPU under torchrun (RANK / LOCAL_RANK / WORLD_SIZE); the reference is single-GPU (`cuda:0`, :58).
   * losses are accumulated on the device and read back once per epoch instead of three host syncs per iteration;
     the NaN bail (:469-472) fires one iteration late.
-  * the job body (`mask_mt_job`) is shared with train_seg_semisup_cowmask_mt.py, which differs in its mask generator and in the
-    options that generator reads; this command's option table, settings line and log are what they were.
+  * the job body (`mask_mt_job`) is shared with train_seg_semisup_cowmask_mt.py and train_seg_semisup_classmix_mt.py, which differ in
+    their mask generators and in the options those read; this command's option table, settings line and log are what they were.
 """
 import click
 
@@ -64,6 +64,34 @@ def train_seg_semisup_mask_mt(submit_config, dataset, model, arch, freeze_bn,
                        nan_checks_consistency=False, polls_step_nan=True, **common)
 
 
+def teacher_prepass_moves(net, freeze_bn):
+    """None when a forward pass of `net` in training mode (after freeze_batchnorm() with `freeze_bn`) changes nothing but its
+    output, else why not: a BatchNorm on batch statistics moves its running statistics, an active Dropout draws from the
+    generator. Looks at the modules only: works on a network that has never left the host."""
+    was_training = net.training
+    modes = [(m, m.training) for m in net.modules()]
+    try:
+        net.train()
+        if freeze_bn:
+            net.freeze_batchnorm()
+        # by name, as architectures/util.freeze_bn_module finds its layers
+        bn = [k for k, m in net.named_modules() if 'BatchNorm' in type(m).__name__ and m.training
+              and getattr(m, 'track_running_stats', True)]
+        drop = [k for k, m in net.named_modules() if 'Dropout' in type(m).__name__ and m.training and getattr(m, 'p', 1.0) > 0]
+    finally:
+        for m, mode in modes:
+            m.training = mode
+        assert net.training == was_training
+    if bn and not freeze_bn:
+        return ('the mask is made from a teacher pass before the step, which must not move the teacher: {} BatchNorm layers would '
+                'update their running statistics; run with --freeze_bn'.format(len(bn)))
+    if bn or drop:
+        return ('the mask is made from a teacher pass before the step, which must not move the teacher: this architecture keeps {} '
+                'BatchNorm layers on batch statistics and {} active Dropout layers even with --freeze_bn (first: {}); it is not '
+                'supported by this command'.format(len(bn), len(drop), (bn + drop)[0]))
+    return None
+
+
 def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, nan_checks_consistency, polls_step_nan,
                 dataset, model, arch, freeze_bn,
                 opt_type, sgd_momentum, sgd_nesterov, sgd_weight_decay,
@@ -85,8 +113,13 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
     train_seg_semisup_cowmask_mt (CowMix / CowOut). `settings` is what the command prints; `make_mask_generator(prop_range)` -> the
     command's mask_gen.MaskGenerator. A generator with `generate_ranges` sends an int32 box table per batch (rasterised inside the
     kernels under `invert`); any other makes its masks on the device from host parameters (`torch_masks_from_params`) and the step
-    takes the materialised mask. `mask_options`: options of the command that only its generator reads."""
-    if ':' in mask_prop_range:
+    takes the materialised mask. A generator that declares `needs_teacher` (mask_gen.ClassMixGenerator) makes its mask from the
+    teacher's prediction on image 1, AFTER the unsupervised images are staged: one extra teacher pass under no_grad per
+    unsupervised batch, outside the step (`mask_prop_range` is None for such a command: it has no share of ones to draw).
+    `mask_options`: options of the command that only its generator reads."""
+    if mask_prop_range is None:
+        pass
+    elif ':' in mask_prop_range:
         lo, hi = mask_prop_range.split(':')
         mask_prop_range = (float(lo.strip()), float(hi.strip()))
     else:
@@ -121,6 +154,9 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
 
     mask_generator = make_mask_generator(mask_prop_range)
     box_tables = hasattr(mask_generator, 'generate_ranges')
+    teacher_masks = bool(getattr(mask_generator, 'needs_teacher', False))
+    if teacher_masks and mask_mode != 'mix':
+        raise ValueError('a mask made from the teacher\'s prediction on image 1 needs --mask_mode mix')
 
     if iters_per_epoch == -1:
         iters_per_epoch = 1000 if run is None else run.iters_per_epoch(iters_per_epoch)
@@ -140,7 +176,7 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
     gen = torch.Generator(device=torch_device).manual_seed(12345 + rank)
     mask_rng = np.random.RandomState(12345 + rank)
     # masks made on the device draw their noise from a generator of their own (the data stream above stays what it is)
-    noise_gen = None if box_tables else torch.Generator(device=torch_device).manual_seed(12345 + rank)
+    noise_gen = None if (box_tables or teacher_masks) else torch.Generator(device=torch_device).manual_seed(12345 + rank)
     data = tc.SyntheticData(gen, batch_size, crop, n_classes, dtype)
 
     # `--synthetic_source_size h,w`: the synthetic samples are uint8 SOURCE images of that size resident in HBM and every
@@ -184,6 +220,20 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
         params = mask_generator.generate_params(batch_size, (H, W), rng=mask_rng)
         return dict(mask=mask_generator.torch_masks_from_params(params, (H, W), torch_device, generator=noise_gen))
 
+    def make_teacher_mask(x1_tea, um1):
+        """the mask of a `needs_teacher` generator: the teacher's low-resolution logits of image 1 under no_grad -- the pass the step
+        repeats --, then the generator's kernels at the step's own output size and corner convention. The pass must leave the
+        teacher as it found it (teacher_prepass_moves)"""
+        keys = mask_generator.generate_params(batch_size, n_classes, rng=mask_rng)
+        with torch.no_grad():
+            logits = teacher_net.forward_lowres(x1_tea)
+        return dict(mask=mask_generator.torch_masks_from_logits(keys, logits, (H, W), step.align_corners, valid=um1))
+
+    if teacher_masks:
+        moved = teacher_prepass_moves(teacher_net, freeze_bn)
+        if moved:
+            raise ValueError(moved)
+
     def make_batch():
         if run is not None:
             sb = augment.stage(run.pool, next(sup_iter), True)
@@ -196,7 +246,7 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
         unsup = []
         if cons_weight > 0.0:
             for _r in range(unsup_batch_ratio):
-                mask_arg = make_mask()
+                mask_arg = None if teacher_masks else make_mask()
                 if augment is not None:
                     if run is not None:
                         u0 = augment.stage(run.pool, next(unsup_iter_0), False)
@@ -204,6 +254,8 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
                     else:
                         u0 = staged(False)
                         u1 = staged(False) if step_cfg.mix else None
+                    if teacher_masks:
+                        mask_arg = make_teacher_mask(u1['image'], u1['mask'])
                     unsup.append(UnsupBatch(u0['image'], um0=u0['mask'],
                                             x1_tea=None if u1 is None else u1['image'],
                                             um1=None if u1 is None else u1['mask'], x0_stu=u0.get('image_stu'),
@@ -213,6 +265,8 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
                 x1 = data.images() if step_cfg.mix else None
                 x0s = data.images() if aug_strong_colour else None
                 x1s = data.images() if (aug_strong_colour and step_cfg.mix) else None
+                if teacher_masks:
+                    mask_arg = make_teacher_mask(x1, None)
                 unsup.append(UnsupBatch(x0, x1_tea=x1, x0_stu=x0s, x1_stu=x1s, **mask_arg))
         return batch_x, batch_y, unsup
 

@@ -976,6 +976,41 @@ typedef struct {
 int cms_tta_resize(const void* src, void* dst, int n, int c, int H, int W, int Hs, int Ws, int dtype, int flip, void* stream);
 int cms_tta_vote(const cms_tta_desc* d, void* stream);
 
+/* ClassMix (csrc/classmix.hip; Olsson et al., WACV 2021): a mixing mask cut along the predicted class regions of a batch. Per
+ * sample, with pred(y, x) the argmax over c of the bilinear sample (under `align_corners`) of logits[n, c] -- bit for bit the
+ * prediction cms_tta_vote writes for k == 1 without a flip: first index on a tie, NaN maximal, no interpolation when (h, w) == (H, W):
+ *   present        64-bit set, bit c set iff some pixel with valid != 0 has pred == c (every pixel when valid is NULL)
+ *   chosen         the (popcount(present) + 1) / 2 classes of `present` that come first in the order (keys[n, c], c): ascending
+ *                  key, the class index breaking equal keys; empty when present is
+ *   mask_out       1.0f where valid != 0 and pred is in chosen, else 0.0f
+ *   logits         (n, c, h, w) f32
+ *   valid          optional (n, H, W) f32
+ *   keys           (n, c) double, device memory; finite (NaN keys are outside the contract)
+ *   mask_out       (n, H, W) f32
+ *   pred_out       optional (n, H, W) uint8
+ *   present_out, chosen_out   optional (n) uint64
+ *   workspace      cms_classmix_workspace_bytes(n, H, W) bytes of device memory, 16-byte aligned, need not be initialised; that
+ *                  function returns 0 for sizes cms_classmix refuses
+ * Two stream-ordered launches, no atomics, no memset, no allocation and no host synchronisation: the same input gives the same bits
+ * whatever the workspace held, a sample's mask does not depend on the rest of its batch, and the call can be captured in a graph.
+ * A NULL descriptor, NULL logits / keys / mask_out / workspace, c outside 1..64, any of n, h, w, H, W below 1, more than 65535
+ * samples, more than 2^31 - 1 output pixels or logits, or a workspace that is misaligned or too small return CMS_EINVAL, decided
+ * before any HIP call; nothing is launched. */
+typedef struct {
+    const float* logits;
+    const float* valid;
+    const double* keys;
+    int n, c, h, w, H, W, align_corners;
+    float* mask_out;
+    uint8_t* pred_out;
+    uint64_t* present_out;
+    uint64_t* chosen_out;
+    void* workspace;
+    size_t workspace_bytes;
+} cms_classmix_desc;
+size_t cms_classmix_workspace_bytes(int n, int H, int W);
+int cms_classmix(const cms_classmix_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
