@@ -297,6 +297,8 @@ PROTOTYPES = {
     'cms_pd_neighbour_maps': (c_int, [c_void_p, _P(StageEntry), c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'cms_downsample_image_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'cms_downsample_labels_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cms_resize_area_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cms_sum_sumsq_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'cms_cowmask_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cms_cowmask': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                             c_void_p]),

@@ -4,7 +4,9 @@ Mirror of the reference's datapipe/isic2017_dataset.py: the ISIC 2017 skin lesio
 plus `rgb_mean_std.pkl`, a pickled dict with `rgb_mean` and `rgb_std`. Same sample list and hold-out rule as Cityscapes. A label
 map is binary: stored values >= 127 are the lesion (class 1), the rest background (class 0); there is no void.
 
-The archive is made by the reference's convert_isic.py, which resizes with cv2.INTER_AREA; that converter is not built here.
+The archive is made by convert_isic.py (cutmix-semisup-seg_amd/convert_isic.py) from the four official downloads: an exact integer
+area resize and the image statistics on the device (csrc/resize.hip). The reference's converter resizes with cv2.INTER_AREA; an
+archive it wrote is read just the same, and the two may differ by a grey level near a half (nothing here was compared with cv2).
 """
 import pickle
 

@@ -1202,6 +1202,46 @@ def downsample_labels_u8(src, d, out=None):
     return _downsample_u8('cms_downsample_labels_u8', src, d, out, 1)
 
 
+# ---------------------------------------------------------------------------------------------- converter area resize
+def _u8_image_batch(name, src):
+    """-> (contiguous src, channels) of a uint8 (N,H,W,3) or (N,H,W) tensor"""
+    if src.dtype != torch.uint8 or src.dim() not in (3, 4) or (src.dim() == 4 and int(src.shape[-1]) != 3):
+        raise TypeError('{}: a uint8 (N,H,W,3) or (N,H,W) tensor is expected'.format(name))
+    return src.contiguous(), 3 if src.dim() == 4 else 1
+
+
+def resize_area_u8(src, ho, wo, out=None):
+    """uint8 CUDA (N,H,W,3) or (N,H,W) -> (N,ho,wo,3) or (N,ho,wo), ho <= H and wo <= W: the exact area filter of
+    csrc/resize_math.hpp, sum wy wx p / (H W) rounded to nearest with ties to even. ho == H and wo == W copies."""
+    name = 'cms_resize_area_u8'
+    _need_cuda(src, out)
+    src, c = _u8_image_batch(name, src)
+    n, h, w, ho, wo = int(src.shape[0]), int(src.shape[1]), int(src.shape[2]), int(ho), int(wo)
+    if ho < 1 or wo < 1 or ho > h or wo > w:
+        raise ValueError('{}: {}x{} -> {}x{}: the target must be at least 1x1 and no larger than the source'.format(name, h, w, ho, wo))
+    shape = (n, ho, wo) + ((3,) if c == 3 else ())
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise TypeError('{}: out must be a contiguous uint8 tensor of shape {}'.format(name, shape))
+    check(fn[name](_ptr(src), n, h, w, c, ho, wo, _ptr(out), _stream()), name)
+    return out
+
+
+def sum_sumsq_u8(src):
+    """uint8 CUDA (N,H,W,3) or (N,H,W) -> int64 (N, 2C): per image the sum of the pixel values of each channel, then the sum of
+    their squares (the converter's rgb_mean_std.pkl is made from these)."""
+    name = 'cms_sum_sumsq_u8'
+    _need_cuda(src)
+    src, c = _u8_image_batch(name, src)
+    n, pixels = int(src.shape[0]), int(src.shape[1]) * int(src.shape[2])
+    if n < 1 or pixels < 1:
+        raise ValueError('{}: an empty tensor {}'.format(name, tuple(src.shape)))
+    out = torch.empty((n, 2 * c), dtype=torch.int64, device=src.device)
+    check(fn[name](_ptr(src), n, pixels, c, _ptr(out), _stream()), name)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- CowMask
 _COW_WORKSPACE = {}
 

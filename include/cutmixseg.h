@@ -920,6 +920,19 @@ int cms_pd_neighbour_maps(const uint8_t* pool_img, const cms_stage_entry* entry_
 int cms_downsample_image_u8(const uint8_t* src, int n, int h, int w, int d, uint8_t* dst, void* stream);
 int cms_downsample_labels_u8(const uint8_t* src, int n, int h, int w, int d, uint8_t* dst, void* stream);
 
+/* Area resize and statistics of the ISIC 2017 converter (csrc/resize.hip), dense tensors:
+ *   cms_resize_area_u8   (n, h, w, c) uint8 -> (n, ho, wo, c), c = 1 or 3, 1 <= ho <= h <= 16384, 1 <= wo <= w <= 16384. Along an
+ *                    axis of L pixels and Lo cells, in units of 1 / Lo pixel, pixel i covers [i Lo, (i + 1) Lo), cell o covers
+ *                    [o L, (o + 1) L) and wt(o, i) is the length of their overlap; out = sum wy wx p / (h w), rounded to nearest,
+ *                    an exact half to the even neighbour. ho == h and wo == w copies. This is the project's own definition of the
+ *                    area filter, not cv2's float32 one: see DESIGN section 8
+ *   cms_sum_sumsq_u8     (n, pixels, c) uint8, c = 1 or 3 -> sums (n, 2c) int64: the sum of p per channel, then the sum of p^2
+ * Integer arithmetic, no atomics: the results are the same on every run. NULL pointers, c other than 1 or 3, a size < 1, ho > h,
+ * wo > w, a side above 16384 or more than 2^31 - 1 bytes per tensor return CMS_EINVAL, decided before any HIP call; nothing is
+ * launched. src and dst must not overlap. */
+int cms_resize_area_u8(const uint8_t* src, int n, int h, int w, int c, int ho, int wo, uint8_t* dst, void* stream);
+int cms_sum_sumsq_u8(const uint8_t* src, int n, int pixels, int c, int64_t* sums, void* stream);
+
 /* CowMask (csrc/cowmask.hip): Gaussian-smoothed noise thresholded so that a chosen share of the pixels is 1.
  *   noise          (n, h, w) f32
  *   taps           (n, 2 * radius + 1) double: one row of 1-D weights per sample, applied along x and along y with ZERO padding
