@@ -82,7 +82,7 @@ class ConvDesc(C.Structure):
                 ('tap_dy', c_int * 18), ('tap_dx', c_int * 18), ('stride', c_int),
                 ('out_h', c_int), ('out_w', c_int), ('out_stride', c_int), ('relu', c_int), ('mode', c_int),
                 ('tile', c_int), ('ksplit', c_int), ('zeros', c_void_p), ('variant', c_int), ('zeros_bytes', c_int),
-                ('workspace', c_void_p), ('workspace_bytes', C.c_longlong), ('mask_bits_out', c_void_p), ('mask_bits', c_void_p),
+                ('mask_bits_out', c_void_p), ('mask_bits', c_void_p),
                 ('stats_out', c_void_p), ('stats_rows_per_group', c_int), ('mask_gates_res', c_int),
                 ('bstats_u', c_void_p), ('bstats_bits', c_void_p), ('bstats_mean', c_void_p), ('bstats_rstd', c_void_p)]
 
@@ -209,7 +209,6 @@ PROTOTYPES = {
     'cms_fill_holes': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
                                c_void_p]),
     'cms_conv_igemm': (c_int, [_P(ConvDesc), c_void_p]),
-    'cms_conv_igemm_workspace_bytes': (C.c_longlong, []),
     'cms_conv_igemm_route': (c_int, [_P(ConvDesc)]),
     'cms_conv_igemm_stats_tile_rows': (c_int, [_P(ConvDesc)]),
     'cms_frozen_bn_act_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
@@ -265,8 +264,6 @@ PROTOTYPES = {
     'cms_program_add_wgrad_group': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
     'cms_program_add_memset': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int]),
     'cms_program_add_sync': (c_int, [c_void_p, c_int, c_int, c_int]),
-    'cms_program_sync_count': (c_int, [c_void_p]),
-    'cms_program_set_sync_flags': (c_int, [c_void_p, c_void_p, c_int]),
     'cms_program_add_aspp_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, _P(c_int), _P(c_int), c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_int, c_int]),
     'cms_program_add_aspp_spread': (c_int, [c_void_p, c_void_p, c_void_p, c_int, _P(c_int), _P(c_int), c_int, c_int, c_int,

@@ -57,10 +57,9 @@ __device__ __forceinline__ void block_sum(float (&v)[K], float* smem /* >= K*16 
     }
 }
 
-// csrc/conv8.hip: the eight-phase 256 x 256 convolution (mode 0: one whole tile per workgroup, 1: persistent + stream-K)
-size_t conv8_workspace_bytes(int n_cu);
+// csrc/conv8.hip: the eight-phase 256 x 256 convolution, one whole tile per workgroup
 bool conv8_supported(const cms_conv_desc* d);
-int conv8_launch(const cms_conv_desc* d, hipStream_t s, int mode, int grid_cap, void* trace, int trace_wgs);
+int conv8_launch(const cms_conv_desc* d, hipStream_t s, void* trace, int trace_wgs);
 // csrc/wgrad8.hip: the eight-phase 256 x 256 weight gradient
 bool wgrad8_supported(const cms_wgrad_desc* d);
 int wgrad8_plan(const cms_wgrad_desc* d, int* kt_per_slice);       // -> number of pixel slices

@@ -1088,30 +1088,21 @@ extern "C" int cms_conv_set_trace(void* buf, int workgroups) {
 }
 
 // The eight-phase 256 x 256 kernel (csrc/conv8.hip) takes the wide, K-deep layers: 16 or more 64-deep K tiles per output tile
-// (the expansions on it, 4 or 8 K tiles: measured, not adopted -- profiles/r06b_*). CMS_CONV8 (read once): 0 = never,
-// 1 = one whole tile per workgroup (default: +3.5 / +5 % on the two-stream step at 321 x 321 / 512 x 1024, profiles/r04d_*),
-// 2 = persistent launch with a stream-K round where the descriptor carries a workspace (slower: the 256 KB partial tiles
-// move at the ~10 B/clk a CU gets from memory).
-static int conv8_env() {
+// (the expansions on it, 4 or 8 K tiles: measured, not adopted -- profiles/r06b_*), one whole tile per workgroup. CMS_CONV8
+// (read once): 0 = never, anything else = on (default: +3.5 / +5 % on the two-stream step at 321 x 321 / 512 x 1024,
+// profiles/r04d_*). The persistent launch with a stream-K round was slower and is gone: docs/DESIGN_HISTORY.md 4.4.
+static bool conv8_env() {
     static int mode = -1;
     if (mode < 0) {
         const char* e = getenv("CMS_CONV8");
-        mode = e ? atoi(e) : 1;
+        mode = e ? (atoi(e) != 0 ? 1 : 0) : 1;
     }
-    return mode;
-}
-
-extern "C" long long cms_conv_igemm_workspace_bytes(void) {
-    int n_cu = 0;
-    if (cms_device_info(&n_cu, nullptr, 0) != CMS_OK || n_cu <= 0) n_cu = 256;
-    return (long long)cms::conv8_workspace_bytes(n_cu);
+    return mode != 0;
 }
 
 // Would the default dispatch (variant 0, tile 0) send this launch to the eight-phase kernel?
 static bool conv_takes_conv8(const cms_conv_desc* d) {
-    return d->variant == 0 && d->tile == 0 && conv8_env() > 0 && cms::conv8_supported(d) &&
-           ((d->mask_bits == nullptr && d->mask_bits_out == nullptr) || conv8_env() == 1) &&     // (bits: whole tiles only)
-           d->ntaps * (d->cin / 64) >= 16;
+    return d->variant == 0 && d->tile == 0 && conv8_env() && cms::conv8_supported(d) && d->ntaps * (d->cin / 64) >= 16;
 }
 
 // Which kernel cms_conv_igemm runs a descriptor on (measurement tooling: per-kernel algorithmic bytes beside the PMC
@@ -1147,7 +1138,6 @@ extern "C" int cms_conv_igemm_stats_tile_rows(const cms_conv_desc* d) {
     if (d->mode == 0 ? d->bstats_u != nullptr : (d->bstats_u == nullptr || d->bstats_mean == nullptr || d->bstats_rstd == nullptr)) return 0;
     const int route = cms_conv_igemm_route(d);
     if (route < 0) return route;
-    if (route == CMS_ROUTE_CONV8 && conv8_env() != 1) return 0;        // (whole tiles per workgroup only, not the stream-K launch)
     const int rows = route == CMS_ROUTE_CONV8 ? 256 : (route == CMS_ROUTE_OTHER ? 0 : 128);
     if (rows == 0) return 0;
     const long long M = (long long)d->n * d->ho * d->wo;
@@ -1161,19 +1151,18 @@ extern "C" int cms_conv_igemm(const cms_conv_desc* d_in, void* stream) {
     if (rc) return rc;
     // an unknown code is an error: a tool that asks for a kernel that does not exist must not time the default one in its place
     CMS_REQUIRE(d_in->variant == 0 || d_in->variant == 1 || d_in->variant == 30 || d_in->variant == 43 ||
-                    (d_in->variant >= 90 && d_in->variant <= 93) || d_in->variant == 99,
+                    d_in->variant == 90 || d_in->variant == 92 || d_in->variant == 99,
                 "conv: variant %d does not exist (0 = auto, 1 = register-staged loader, 30 = cycle trace, 43 = flat direct-to-LDS "
-                "addresses, 90..93 = eight-phase kernel, 99 = never the eight-phase kernel)", d_in->variant);
-    if (d_in->variant >= 90 && d_in->variant <= 93)     // 92 / 93: 90 / 91 with cycle stamps into the cms_conv_set_trace buffer
-        return cms::conv8_launch(d_in, (hipStream_t)stream, (d_in->variant - 90) & 1, 0,
-                                 d_in->variant >= 92 ? g_conv_trace : nullptr, g_conv_trace_wgs);
+                "addresses, 90 = eight-phase kernel, 92 = with its cycle trace, 99 = never the eight-phase kernel)", d_in->variant);
+    if (d_in->variant == 90 || d_in->variant == 92)     // 92: 90 with cycle stamps into the cms_conv_set_trace buffer
+        return cms::conv8_launch(d_in, (hipStream_t)stream, d_in->variant == 92 ? g_conv_trace : nullptr, g_conv_trace_wgs);
     cms_conv_desc d_no8;
     if (d_in->variant == 99) {                 // the 128 x 128 family, whatever CMS_CONV8 says (reference of the conv8 tests)
         d_no8 = *d_in;
         d_no8.variant = 0;
         d_in = &d_no8;
     } else if (conv_takes_conv8(d_in))
-        return cms::conv8_launch(d_in, (hipStream_t)stream, conv8_env() - 1, 0, nullptr, 0);
+        return cms::conv8_launch(d_in, (hipStream_t)stream, nullptr, 0);
     const cms_conv_desc* d = d_in;
     ConvArgs a;
     a.x = (const uint16_t*)d->x; a.w = (const uint16_t*)d->w; a.y = (uint16_t*)d->y; a.y32 = d->y32;
@@ -1409,17 +1398,15 @@ __device__ __forceinline__ uint32_t wg_off(int pix, int ch) {     // byte offset
 // 3700..4100-cycle stage issuing its 8 loads (64-bit address arithmetic) and 750 waiting for them + ds_write.
 // (the body is a device function of the LOGICAL block id -- XCD-remapped by the caller -- so that a grouped launch can run the
 // weight gradients of many layers in one grid: conv_wgrad_group_kernel below)
-template <int TCO, int TCI, bool PLAIN, bool BETA, bool DMA = false, int DNS = 1>   // 32x32 MFMA tiles per wave along co / ci; waves are 2 x 2
+template <int TCO, int TCI, bool PLAIN, bool BETA, bool DMA = false>   // 32x32 MFMA tiles per wave along co / ci; waves are 2 x 2
 __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int b) {
     constexpr int BCO = 2 * TCO * 32, BCI = 2 * TCI * 32;       // <= 128 each
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int WG_STAGE = 2 * 64 * 256;        // one stage: dU tile + X tile (32 KB)
-    constexpr int WG_NS = DMA ? DNS : 1;          // DMA, DNS = 2: the loads of stage k+1 fly during the MFMAs of stage k
-    static_assert(DNS == 1 || DNS == 2, "one or two stages");
+    constexpr int WG_STAGE = 2 * 64 * 256;        // the one stage: dU tile + X tile (32 KB; a second stage lost: docs/DESIGN_HISTORY.md 4.4)
     unsigned char* lds_u = smem;                  // [64][256 B]  dU tile (only the first BCO channels are used)
     unsigned char* lds_x = smem + 64 * 256;       // [64][256 B]  X tile
-    float* lds_scale = reinterpret_cast<float*>(smem + WG_NS * WG_STAGE);   // [BCO] per-row factor of the epilogue
-    uint32_t* lds_trace = reinterpret_cast<uint32_t*>(smem + WG_NS * WG_STAGE + 128 * 4);   // [CONV_TRACE_DWORDS] when tracing
+    float* lds_scale = reinterpret_cast<float*>(smem + WG_STAGE);   // [BCO] per-row factor of the epilogue
+    uint32_t* lds_trace = reinterpret_cast<uint32_t*>(smem + WG_STAGE + 128 * 4);   // [CONV_TRACE_DWORDS] when tracing
     const bool tracing = a.trace != nullptr && (int)blockIdx.x < a.trace_wgs;
     const uint64_t t_start = tracing ? __builtin_amdgcn_s_memtime() : 0;
     const uint64_t rt_start = tracing ? __builtin_amdgcn_s_memrealtime() : 0;
@@ -1550,14 +1537,14 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int b) {
             }
         }
     };
-    auto dma_issue = [&](int buf) {
+    auto dma_issue = [&]() {
         if constexpr (DMA) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                buf_load_lds16(rsrc_u, lds_u + buf * WG_STAGE + (4 * i + wave_s) * 1024, uvoff[i], soff_u);
+                buf_load_lds16(rsrc_u, lds_u + (4 * i + wave_s) * 1024, uvoff[i], soff_u);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                buf_load_lds16(rsrc_x, lds_x + buf * WG_STAGE + (4 * i + wave_s) * 1024, xvoff[i], soff_x);
+                buf_load_lds16(rsrc_x, lds_x + (4 * i + wave_s) * 1024, xvoff[i], soff_x);
         }
     };
     if constexpr (DMA) {
@@ -1601,9 +1588,9 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int b) {
     const int ch_in_tile = 16 * (g & 1) + 4 * (li & 3);     // channel chunk this lane SUPPLIES (within a 32-wide tile)
     const int pix_in_blk = 8 * (g >> 1) + (li >> 2);        // pixel row this lane supplies (within a 16-pixel k-step)
 
-    auto mfma_phase = [&](int buf) {
-        unsigned char* su = smem + buf * WG_STAGE;                      // this stage's dU / X tiles
-        unsigned char* sx = smem + buf * WG_STAGE + 64 * 256;
+    auto mfma_phase = [&]() {
+        unsigned char* su = smem;                                       // the stage's dU / X tiles
+        unsigned char* sx = smem + 64 * 256;
         auto frag_read = [&](int kk, u32x4* fu, u32x4* fx) {
             const int pr0 = kk * 16 + pix_in_blk;           // first read: pixels +0..3 of this lane group's 8
 #pragma unroll
@@ -1655,10 +1642,9 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int b) {
         }
     };
     if constexpr (DMA) {
-        dma_issue(0);
+        dma_issue();
         stamp(4);                                           // prologue done (first stage's loads issued)
-        int buf = 0;
-        auto next_stage = [&](int p0, int nbuf) {
+        auto next_stage = [&](int p0) {
             if (p0 + 64 < p_end) {
                 soff_u += 64 * a.Cout * 2;
                 if constexpr (PLAIN) {
@@ -1673,26 +1659,21 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int b) {
                     dma_x_offsets(p0 + 64);
                 }
                 if (p0 + 128 > p_end) dma_tail_mask(p0 + 64);
-                dma_issue(nbuf);
+                dma_issue();
             }
         };
         for (int p0 = p_begin; p0 < p_end; p0 += 64) {
             const int tb = 16 + ((p0 - p_begin) >> 6) * 6;
             stamp(tb);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's pieces of stage `buf` have landed in LDS
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's pieces of the stage have landed in LDS
             stamp(tb + 1);
-            __syncthreads();                                    // ... everybody else's too (two stages: and all fragment
-            stamp(tb + 2);                                      // reads of the previous stage, the other buffer, are done)
-            if constexpr (WG_NS == 2) next_stage(p0, buf ^ 1);  // in flight during the MFMAs below
+            __syncthreads();                                    // ... everybody else's too
+            stamp(tb + 2);
             stamp(tb + 3);
-            mfma_phase(buf);
+            mfma_phase();
             stamp(tb + 4);
-            if constexpr (WG_NS == 1) {
-                __syncthreads();                                // all fragment reads done: the stage may be refilled
-                next_stage(p0, 0);
-            } else {
-                buf ^= 1;
-            }
+            __syncthreads();                                    // all fragment reads done: the stage may be refilled
+            next_stage(p0);
             stamp(tb + 5);
         }
     } else {
@@ -1710,7 +1691,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int b) {
             advance();
             load_tile();                                    // next stage (all-zero past the end of the slice)
             stamp(tb + 4);
-            mfma_phase(0);
+            mfma_phase();
             stamp(tb + 5);
         }
     }
@@ -1843,9 +1824,9 @@ __device__ __forceinline__ int xcd_logical_block() {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-template <int TCO, int TCI, bool PLAIN, bool BETA, bool DMA = false, int DNS = 1>
+template <int TCO, int TCI, bool PLAIN, bool BETA, bool DMA = false>
 __global__ __launch_bounds__(256, DMA ? ((BETA || !PLAIN) ? 3 : 4) : 1) void conv_wgrad_kernel(WgradArgs a) {
-    wgrad_body<TCO, TCI, PLAIN, BETA, DMA, DNS>(a, xcd_logical_block());
+    wgrad_body<TCO, TCI, PLAIN, BETA, DMA>(a, xcd_logical_block());
 }
 
 // GROUPED launch: the weight gradients of MANY layers (the bottlenecks of a stretch of the backward pass) in one grid. A
@@ -1870,16 +1851,16 @@ __global__ __launch_bounds__(256, PLAIN ? 4 : 3) void conv_wgrad_group_kernel(co
     }
     lo = __builtin_amdgcn_readfirstlane(lo);
     const WgradArgs a = items[lo].a;
-    wgrad_body<2, 2, PLAIN, false, true, 1>(a, b - __builtin_amdgcn_readfirstlane(items[lo].first_block));
+    wgrad_body<2, 2, PLAIN, false, true>(a, b - __builtin_amdgcn_readfirstlane(items[lo].first_block));
 }
 
 }  // namespace cms
 
-template <int TCO, int TCI, bool PLAIN, bool BETA, bool DMA, int DNS>
+template <int TCO, int TCI, bool PLAIN, bool BETA, bool DMA>
 static void wgrad_launch(dim3 grid, size_t lds, hipStream_t s, const WgradArgs& a) {
-    auto kern = conv_wgrad_kernel<TCO, TCI, PLAIN, BETA, DMA, DNS>;
+    auto kern = conv_wgrad_kernel<TCO, TCI, PLAIN, BETA, DMA>;
     static bool raised = false;
-    if (DMA && !raised) {           // two stages = 64 KB + tables: above what a kernel gets without asking
+    if (DMA && !raised) {           // (room for the trace dwords behind the stage and the tables)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         raised = true;
     }
@@ -1888,7 +1869,7 @@ static void wgrad_launch(dim3 grid, size_t lds, hipStream_t s, const WgradArgs& 
 
 // Number of pixel slices (split-K) of a weight-gradient launch and the pixels per slice -- shared by the launch and by
 // cms_conv_wgrad_workspace_bytes (a caller sizing the slab of the deterministic combine).
-static int wgrad_plan(const cms_wgrad_desc* d, int* per_out, bool* dma_out, int* stages_out) {
+static int wgrad_plan(const cms_wgrad_desc* d, int* per_out, bool* dma_out) {
     const int M = d->n * d->ho * d->wo;
     const int bco = d->cout % 128 == 0 ? 128 : 64, bci = d->cin % 128 == 0 ? 128 : 64;
     const int tiles = (d->cout / bco) * (d->cin / bci) * d->ntaps;
@@ -1896,58 +1877,40 @@ static int wgrad_plan(const cms_wgrad_desc* d, int* per_out, bool* dma_out, int*
     // per-workgroup prologue / epilogue); each slice is a multiple of 64 pixels
     // direct-to-LDS loader (buffer addressing: both tensors below 2 GB); CMS_WGRAD_DMA=0 forces the register loader and
     // CMS_WGRAD_TARGET the workgroup count the automatic split aims at (A/B switches, read once)
-    static int env_dma = -1, env_target = -1, env_stages = 1;
+    static int env_dma = -1, env_target = -1;
     if (env_dma < 0) {
         const char* e = getenv("CMS_WGRAD_DMA");
         env_dma = e ? atoi(e) : 1;
-        const char* g = getenv("CMS_WGRAD_STAGES");
-        env_stages = g ? atoi(g) : 1;
         const char* t = getenv("CMS_WGRAD_TARGET");
         env_target = t ? atoi(t) : 0;
     }
     const bool dma = env_dma != 0 && (size_t)M * d->cout * 2 < (1ull << 31) &&
                      (size_t)d->n * d->h * d->w_in * d->cin * 2 < (1ull << 31);
     const int target = env_target > 0 ? env_target : 384;
-    // one stage by default: alone on the chip two stages are ~8 % faster (5.5 vs 6.0 ms over the DeepLab v2 layer
-    // list), inside the step -- where the weight gradients share the CUs with the data-gradient convolutions of the
-    // other stream -- the 64 KB of LDS per workgroup cost 3-4 % of the step (profiles/r02u_*)
-    const int stages = env_stages == 2 ? 2 : 1;
     int ksplit = d->ksplit > 0 ? d->ksplit : (target + tiles - 1) / tiles;
     const bool plain_shape = d->ntaps == 1 && d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->stride == 1 && d->h == d->ho &&
                              d->w_in == d->wo;
     if (d->ksplit <= 0 && dma && env_target <= 0) {
-        // Number of pixel slices from a two-term model (env CMS_WGRAD_MODEL=0: the sweep-tuned rule of profiles/r02r):
+        // Number of pixel slices from a two-term model (it replaced the sweep-tuned rule of profiles/r02r):
         //   the slices' K loops run side by side (<= `cap` resident workgroups): nst / ks stages of t_stage each;
         //   their atomics are served by the memory-side units at ~0.7 TB/s IN TOTAL (tools/atomic_probe.hip): ks * |dW|.
         // The sum is smallest at ks = sqrt(nst * t_stage * 0.7e12 / |dW| bytes). It reproduces the tuned values at
         // the 321 x 321 shapes (21 / 16 / 8 / 10 slices for the 1x1 1024->256, 3x3 256->256, 3x3 512->512, 1x1 2048->512
         // layers) and follows M where the tuning did not go: DeepLab v3+ at 513 x 513 has 10 890 pixels per layer-3/4
         // launch, where 24 slices of 7 stages each spent their time in the atomics.
-        static int env_model = -1;
-        if (env_model < 0) {
-            const char* e = getenv("CMS_WGRAD_MODEL");
-            env_model = e ? atoi(e) : 1;
-        }
         const int nst = (M + 63) / 64;
-        // resident workgroups: 2 per CU with two stages (LDS), 3 where the register budget is 168 (taps / side outputs)
-        const int cap = stages == 2 ? 512 : ((plain_shape && d->dbeta == nullptr) ? 864 : 720);
-        if (env_model != 0) {
-            const double t_stage = plain_shape ? 1.25e-6 : 1.75e-6;
-            const double dw_bytes = (double)d->ntaps * d->cout * d->cin * 4.0;
-            int ks = (int)(std::sqrt((double)nst * t_stage * 0.7e12 / dw_bytes) + 0.5);
-            ks = std::max(1, std::min(ks, std::min(std::max(1, cap / tiles), nst)));
-            ksplit = ks;
-        } else {
-            const int hi = std::min(cap / tiles, nst / 32);
-            if (hi > ksplit) ksplit = hi;
-        }
+        // resident workgroups: 3 per CU where the register budget is 168 (taps / side outputs)
+        const int cap = (plain_shape && d->dbeta == nullptr) ? 864 : 720;
+        const double t_stage = plain_shape ? 1.25e-6 : 1.75e-6;
+        const double dw_bytes = (double)d->ntaps * d->cout * d->cin * 4.0;
+        const int ks = (int)(std::sqrt((double)nst * t_stage * 0.7e12 / dw_bytes) + 0.5);
+        ksplit = std::max(1, std::min(ks, std::min(std::max(1, cap / tiles), nst)));
     }
     int per = ((M + ksplit - 1) / ksplit + 63) / 64 * 64;
     if (per < 64) per = 64;
     ksplit = (M + per - 1) / per;
     if (per_out) *per_out = per;
     if (dma_out) *dma_out = dma;
-    if (stages_out) *stages_out = stages;
     return ksplit;
 }
 
@@ -1978,7 +1941,7 @@ extern "C" long long cms_conv_wgrad_workspace_bytes(const cms_wgrad_desc* d) {
     if (!d || d->cin % 64 != 0 || d->cout % 64 != 0 || d->ntaps <= 0 || d->ntaps > CMS_CONV_MAX_TAPS || d->n <= 0 || d->ho <= 0 ||
         d->wo <= 0 || d->cin % 4 != 0)
         return 0;
-    const int ks = wgrad8_selected(d) ? wgrad8_plan(d, nullptr) : wgrad_plan(d, nullptr, nullptr, nullptr);
+    const int ks = wgrad8_selected(d) ? wgrad8_plan(d, nullptr) : wgrad_plan(d, nullptr, nullptr);
     return ks > 1 ? (long long)ks * d->ntaps * d->cout * d->cin * (long long)sizeof(float) : 0;
 }
 
@@ -2019,9 +1982,9 @@ extern "C" int cms_conv_wgrad(const cms_wgrad_desc* d, void* stream) {
     if (wgrad8_selected(d)) return wgrad8_launch(d, (hipStream_t)stream, g_conv_trace, g_conv_trace_wgs);
     const int bco = d->cout % 128 == 0 ? 128 : 64, bci = d->cin % 128 == 0 ? 128 : 64;
     const int tiles = (d->cout / bco) * (d->cin / bci) * d->ntaps;
-    int per = 64, stages = 1;
+    int per = 64;
     bool dma = false;
-    int ksplit = wgrad_plan(d, &per, &dma, &stages);
+    int ksplit = wgrad_plan(d, &per, &dma);
     a.ksplit = ksplit;
     a.pix_per_split = per;
     hipStream_t s = (hipStream_t)stream;
@@ -2038,22 +2001,21 @@ extern "C" int cms_conv_wgrad(const cms_wgrad_desc* d, void* stream) {
     a.slab_stride = slice_elems;
     a.trace = g_conv_trace;                      // diagnostic (cms_conv_set_trace); NULL in production
     a.trace_wgs = g_conv_trace_wgs;
-    const size_t lds = (dma ? stages : 1) * 2 * 64 * 256 + 128 * 4 + (a.trace ? CONV_TRACE_DWORDS * 4 : 0);
+    const size_t lds = 2 * 64 * 256 + 128 * 4 + (a.trace ? CONV_TRACE_DWORDS * 4 : 0);
     const bool beta = d->dbeta != nullptr;
     const bool plain = d->ntaps == 1 && d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->stride == 1 && d->h == d->ho &&
                        d->w_in == d->wo;
-#define CMS_WGRAD_LAUNCH2(TCO, TCI, DMA, DNS)                                                         \
+#define CMS_WGRAD_LAUNCH2(TCO, TCI, DMA)                                                         \
     do {                                                                                              \
-        if (plain && beta) wgrad_launch<TCO, TCI, true, true, DMA, DNS>(grid, lds, s, a);             \
-        else if (plain) wgrad_launch<TCO, TCI, true, false, DMA, DNS>(grid, lds, s, a);               \
-        else if (beta) wgrad_launch<TCO, TCI, false, true, DMA, DNS>(grid, lds, s, a);                \
-        else wgrad_launch<TCO, TCI, false, false, DMA, DNS>(grid, lds, s, a);                         \
+        if (plain && beta) wgrad_launch<TCO, TCI, true, true, DMA>(grid, lds, s, a);             \
+        else if (plain) wgrad_launch<TCO, TCI, true, false, DMA>(grid, lds, s, a);               \
+        else if (beta) wgrad_launch<TCO, TCI, false, true, DMA>(grid, lds, s, a);                \
+        else wgrad_launch<TCO, TCI, false, false, DMA>(grid, lds, s, a);                         \
     } while (0)
 #define CMS_WGRAD_LAUNCH(TCO, TCI)                                                                    \
     do {                                                                                              \
-        if (dma && stages == 2) CMS_WGRAD_LAUNCH2(TCO, TCI, true, 2);                                 \
-        else if (dma) CMS_WGRAD_LAUNCH2(TCO, TCI, true, 1);                                           \
-        else CMS_WGRAD_LAUNCH2(TCO, TCI, false, 1);                                                   \
+        if (dma) CMS_WGRAD_LAUNCH2(TCO, TCI, true);                                                   \
+        else CMS_WGRAD_LAUNCH2(TCO, TCI, false);                                                      \
     } while (0)
     if (bco == 128 && bci == 128) CMS_WGRAD_LAUNCH(2, 2);
     else if (bco == 128) CMS_WGRAD_LAUNCH(2, 1);

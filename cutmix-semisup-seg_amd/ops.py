@@ -1890,32 +1890,9 @@ class Program(object):
             arr[i] = st.cuda_stream
         return arr
 
-    def _ensure_sync_flags(self, force=False):
-        """(round 6) the flag words of the program's cross-stream syncs (csrc/program.hip: a setter + a polling kernel per sync
-        instead of an event record + wait): one zeroed int per sync op + the timeout counter, owned by the program, given to the
-        native side before the first replay (again if ops were recorded since). OPT-IN (CMS_PROG_FLAG_SYNC=1, or `force`): the
-        flag form removes the ~12 us hole per bottleneck from the data-gradient stream and the step gets SLOWER (626.8 / 628.9
-        against 634.2 / 633.8 img/s at cfg 2, profiles/r06ae_*: the weight-gradient streams are released earlier and take CUs the
-        data-gradient chain's next launch was about to get), so the default replay keeps hipEventRecord / hipStreamWaitEvent."""
-        if not force and _os.environ.get('CMS_PROG_FLAG_SYNC', '0') != '1':
-            return
-        n = int(fn['cms_program_sync_count'](self.h))
-        if n > 0 and getattr(self, '_sync_flags_n', 0) != n:
-            if getattr(self, 'sync_flags', None) is not None:
-                self.keep.append(self.sync_flags)       # (waiters of a replay in flight may still poll the old words)
-            self.sync_flags = torch.zeros(n + 1, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
-            self._sync_flags_n = n
-            check(fn['cms_program_set_sync_flags'](self.h, self.sync_flags.data_ptr(), n + 1), 'cms_program_set_sync_flags')
-
-    def sync_timeouts(self):
-        """Waiter kernels that gave up (must stay 0; reads the device)."""
-        fl = getattr(self, 'sync_flags', None)
-        return 0 if fl is None else int(fl[-1].item())
-
     def run(self, streams, first=0, last=-1):
         if len(streams) < self.n_streams:
             raise ValueError('program recorded on {} streams, {} given'.format(self.n_streams, len(streams)))
-        self._ensure_sync_flags()
         if self.host_ops:
             # a host op recorded at index i happens after launches [0, i) and before launch i: it belongs to the range that
             # STARTS at i (segmented replays call run(first, i) and then run(i, ...)), or to the last range when i == size
@@ -1956,8 +1933,6 @@ def run_pair(prog_a, streams_a, prog_b, streams_b):
     caller can never drop the exchanges silently (`_BodyPairFn` issues such passes one after the other)."""
     if prog_a.host_ops or prog_b.host_ops:
         raise RuntimeError('run_pair: a program with host operations (SyncBN exchanges) must be replayed with Program.run')
-    prog_a._ensure_sync_flags()
-    prog_b._ensure_sync_flags()
     check(fn['cms_program_run_pair'](prog_a.h, Program._handles(streams_a), len(streams_a), prog_b.h,
                                      Program._handles(streams_b), len(streams_b)), 'cms_program_run_pair')
 
@@ -2096,29 +2071,9 @@ def _zero_page(device):
     return z
 
 
-_CONV8_WS = {}
 # cms_conv_igemm_route -> the kernel name rocprofv3 reports (prefix)
 _ROUTE_NAMES = {8: 'conv8_kernel', 2: 'conv_igemm_mixed_kernel', 1: 'conv_igemm_kernel<2, 2, 2, 2', 3: 'conv_igemm_kernel<1, 4, 2, 1',
                 4: 'conv_igemm_kernel<1, 4, 1, 1', 0: 'other'}
-
-
-def conv8_workspace(device):
-    """Scratch of the eight-phase 256 x 256 convolution (csrc/conv8.hip: arrival counters + stream-K slabs,
-    cms_conv_igemm_workspace_bytes). Launches that may overlap must not share it: a recorded program owns one per stream
-    it records on (student / teacher passes and the two streams of a backward pass replay concurrently); eager launches
-    share one per (device, stream). The counters (first 64 KB) start at zero and every launch leaves them zero."""
-    if _REC is not None:
-        prog = _REC[0]
-        store, key = prog.__dict__.setdefault('conv8_ws', {}), _rec_stream_index()
-    else:
-        store, key = _CONV8_WS, (device.index, int(torch.cuda.current_stream().cuda_stream))
-    ws = store.get(key)
-    if ws is None:
-        n = int(fn['cms_conv_igemm_workspace_bytes']())
-        ws = torch.empty(n, dtype=torch.uint8, device=device)
-        ws[:65536].zero_()
-        store[key] = ws
-    return ws
 
 
 def conv_taps(kh, kw, dilation, padding):
@@ -2204,10 +2159,6 @@ def conv_igemm(x, w_packed, taps, stride=1, out_hw=None, scale=None, bias=None, 
     zp = _zero_page(x.device)
     d.zeros, d.zeros_bytes = zp.data_ptr(), zp.numel() * 2
     d.variant = int(variant)
-    if not f32 and out_f32_nchw is None and cout % 256 == 0 and cin % 64 == 0 and ksplit <= 1 \
-            and ((int(variant) == 0 and ntaps * (cin // 64) >= 8) or int(variant) in (91, 93)):
-        ws = conv8_workspace(x.device)       # wide, K-deep layer: the library may take the eight-phase kernel (csrc/conv8.hip)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     tile_sums = None
     if stats is not None:
         stats['tile_rows'], stats['tile_sums'] = 0, None

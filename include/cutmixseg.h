@@ -379,20 +379,11 @@ typedef struct cms_conv_desc {
     int variant;           /* 0 = auto (direct-to-LDS, buffer-addressed below 2 GB per tensor, flat addresses above),
                               1 = register-staged loader, 30 = variant 0 with cycle stamps (cms_conv_set_trace), 43 = the
                               flat-address direct-to-LDS loader at any size; 90 = the eight-phase 256 x 256 kernel, one
-                              whole tile per workgroup; 91 = the same, persistent with a stream-K round (needs
-                              `workspace`); 92 / 93 = 90 / 91 with cycle stamps; 99 = never the eight-phase kernel.
-                              Any other code is an error (the stage rings, two-stage loaders, K rotation and ablation
-                              switches that once had codes were measured, none faster, and removed: DESIGN.md
-                              section 4.1)                                                                        */
+                              whole tile per workgroup; 92 = 90 with cycle stamps; 99 = never the eight-phase kernel.
+                              Any other code is an error (the stage rings, two-stage loaders, K rotation, ablation
+                              switches and the persistent stream-K launch 91 / 93 that once had codes were measured,
+                              none faster, and removed: DESIGN.md section 4.1, docs/DESIGN_HISTORY.md 4.4)        */
     int zeros_bytes;       /* length of the `zeros` run (checked against 2 * cin + 128)                          */
-    void* workspace;       /* optional scratch of the eight-phase 256 x 256 kernel (csrc/conv8.hip; variant 90 / 91 or
-                              the automatic choice for Cout % 256 == 0 layers with >= 8 K tiles), at least
-                              cms_conv_igemm_workspace_bytes() long: 64 KB of arrival counters -- ZERO before the first
-                              launch that uses the buffer, left zero by every launch -- followed by the fp32 slabs of
-                              the stream-K round (tiles whose K loop is cut across workgroups so that the launch fills
-                              every CU; the last arriver of a tile adds the pieces in a fixed order). Launches that may
-                              overlap (different streams) need different workspaces. NULL: whole tiles only.        */
-    long long workspace_bytes;
     /* ReLU masks as BITS (round 4). A forward launch with `relu` can also write, per output pixel, Cout / 8 bytes whose bit
      * c & 7 of byte c >> 3 says [y[pixel][c] > 0] (of the stored bf16 value): mask_bits_out = uint8 [N][out_h][out_w][cout / 8].
      * The data gradient that would re-read that activation only for its sign (`mask_src`) takes the bits instead
@@ -439,8 +430,6 @@ int cms_conv_igemm(const cms_conv_desc* d, void* stream);
 int cms_conv_igemm_route(const cms_conv_desc* d);
 /* pixel rows per statistics tile of a launch with stats_out (see cms_conv_desc), or 0 when the launch cannot write them */
 int cms_conv_igemm_stats_tile_rows(const cms_conv_desc* d);
-/* bytes of cms_conv_desc.workspace that every launch on this device is satisfied with */
-long long cms_conv_igemm_workspace_bytes(void);
 
 /* Diagnostic (tools/conv_trace.py): launches with variant 30 stamp s_memtime at every phase of the K loop of wave 0
  * (own loads landed / barrier / MFMAs issued / barrier / next stage issued) into `buf`: 512 dwords per workgroup for
@@ -788,15 +777,6 @@ int cms_program_add_aspp_spread(cms_program* p, const float* dlogits, void* d_nh
                                 const int* tap_dx, int n_taps, int n, int c, int zc, int h, int w, int stream_idx, int group);
 /* work enqueued so far on `from_stream` must finish before anything enqueued later on `to_stream` starts */
 int cms_program_add_sync(cms_program* p, int from_stream, int to_stream, int group);
-/* Syncs without events (round 6). With a caller-owned, ZEROED device buffer of n_flags >= cms_program_sync_count(p) + 1 ints
- * (persistent like every buffer of a program; the last word counts waiter timeouts and stays 0), a sync is replayed as a one-wave
- * setter kernel on the producing stream + a one-wave polling kernel on the waiting stream instead of hipEventRecord +
- * hipStreamWaitEvent (which costs the producing stream ~12 us per pair of waiters, tools/event_cost_probe.hip). NULL / 0 = events
- * again; CMS_PROG_FLAG_SYNC=0 in the environment keeps the events whatever is set; a replay under stream capture uses events.
- * Opt-in: in the training step the event form is FASTER (profiles/r06ae_*), so ops.Program only sets flags on request.
- * (The reference has no counterpart: its step is one stream, train_seg_semisup_mask_mt.py:287-476.) */
-int cms_program_sync_count(const cms_program* p);
-int cms_program_set_sync_flags(cms_program* p, int* flags_dev, int n_flags);
 /* Trainable BatchNorm affine over frozen statistics on the eight-phase weight-gradient kernel (csrc/wfinish.hip; the torchvision
  * backbone of architectures/deeplab3plus.py:96-98 + autograd): the weight-gradient launch writes the UNSCALED gradient G into a
  * scratch tensor of the weight's shape, cms_channel_sum takes d(beta) = sum_p dU, and one finishing launch per backward pass does,

@@ -171,6 +171,9 @@ def test_conv_rejects_retired_variant_code(ops):
     assert ops.conv_igemm(x, w, [(0, 0)]).shape == (1, 4, 4, 128)
     with pytest.raises(ValueError, match='variant 12 does not exist'):
         ops.conv_igemm(x, w, [(0, 0)], variant=12)
+    for code in (91, 93):           # the persistent stream-K launch of the eight-phase kernel and its cycle trace
+        with pytest.raises(ValueError, match='variant {} does not exist'.format(code)):
+            ops.conv_igemm(x, w, [(0, 0)], variant=code)
 
 
 WG_CASES = [('1x1_256_1024', 2, 41, 41, 256, 1024, 1, 1, 1), ('3x3d2_256', 2, 41, 41, 256, 256, 3, 1, 2),

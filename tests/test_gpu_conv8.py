@@ -1,13 +1,12 @@
 """
-GPU parity of the eight-phase 256 x 256 convolution (csrc/conv8.hip: cms_conv_igemm variants 90 = one whole tile per
-workgroup, 91 = persistent launch with a stream-K round) through the C ABI:
+GPU parity of the eight-phase 256 x 256 convolution (csrc/conv8.hip: cms_conv_igemm variant 90, one whole tile per
+workgroup) through the C ABI:
   * against the same operator in FP64 ON THE HOST on identical bf16 inputs -- one bf16 rounding of the output plus fp32
     accumulation noise, every epilogue kind the backbone uses (plain / BN affine + ReLU / + residual; data gradient with
     ReLU mask, with mask AND gradient add, with the add alone), 1 x 1 / dilated 3 x 3 / odd K-tile counts / ragged pixel
     tiles / a strided output scatter;
   * against the default 128 x 128 kernel: whole tiles accumulate in the same K order, so variant 90 is BIT-IDENTICAL to it;
-  * the stream-K round sums a tile's pieces in run order: repeated launches are bit-identical and within one bf16 rounding
-    of the default kernel.
+  * a default-route launch that takes the kernel allocates nothing but its output.
 """
 import pytest
 import torch
@@ -55,7 +54,7 @@ def _close_to_fp64(y, ref):
     assert float(err.mean()) <= 0.5 * BF16_HALF_ULP * float(ref.abs().mean()) + 1e-6
 
 
-@pytest.mark.parametrize('variant', [90, 91])
+@pytest.mark.parametrize('variant', [90])
 @pytest.mark.parametrize('epi', ['plain', 'bn_relu', 'bn_res_relu'])
 @pytest.mark.parametrize('case', CASES, ids=[c[0] for c in CASES])
 def test_conv8_forward_vs_fp64(ops, case, epi, variant):
@@ -79,14 +78,10 @@ def test_conv8_forward_vs_fp64(ops, case, epi, variant):
         ref = F.relu(ref)
     _close_to_fp64(y, ref.permute(0, 2, 3, 1))
     y0 = ops.conv_igemm(x, _pack(w), taps, scale=scale, bias=bias, res=res, relu=relu, variant=99)     # the 128 x 128 kernel
-    if variant == 90:
-        assert torch.equal(y, y0), 'whole tiles must equal the default kernel bit for bit'
-    else:
-        for _ in range(2):      # run-order sums: reproducible
-            assert torch.equal(ops.conv_igemm(x, _pack(w), taps, scale=scale, bias=bias, res=res, relu=relu, variant=variant), y)
+    assert torch.equal(y, y0), 'whole tiles must equal the default kernel bit for bit'
 
 
-@pytest.mark.parametrize('variant', [90, 91])
+@pytest.mark.parametrize('variant', [90])
 @pytest.mark.parametrize('epi', ['mask', 'mask_add', 'add'])
 @pytest.mark.parametrize('case', [CASES[0], CASES[1], CASES[3]], ids=[CASES[0][0], CASES[1][0], CASES[3][0]])
 def test_conv8_data_gradient_vs_fp64(ops, case, epi, variant):
@@ -114,8 +109,7 @@ def test_conv8_data_gradient_vs_fp64(ops, case, epi, variant):
     if mask is not None:
         ref = ref * (_d(x) > 0)
     _close_to_fp64(dx, ref.detach())
-    if variant == 90:
-        assert torch.equal(dx, ops.conv_igemm(dU, wT, ops.conv_taps(k, k, dil, pad), res=add, mode=1, mask_src=mask, variant=99))
+    assert torch.equal(dx, ops.conv_igemm(dU, wT, ops.conv_taps(k, k, dil, pad), res=add, mode=1, mask_src=mask, variant=99))
 
 
 def test_conv8_strided_scatter_equals_default(ops):
@@ -126,16 +120,15 @@ def test_conv8_strided_scatter_equals_default(ops):
     wt = _mk((4, Cout, Cin), g, 0.05)
     taps = [(0, 0), (0, 1), (1, 0), (1, 1)]
     outs = []
-    for var in (99, 90, 91):
+    for var in (99, 90):
         out = torch.zeros(N, 2 * h, 2 * w_, Cout, dtype=torch.bfloat16, device=DEV)
         ops.conv_igemm(du, wt, taps, mode=1, out=out, out_hw=(h, w_), out_stride=2, out_full_hw=(2 * h, 2 * w_), variant=var)
         outs.append(out)
     assert torch.equal(outs[0], outs[1])
-    assert float((outs[2].float() - outs[0].float()).abs().max()) <= 2.0 ** -7 * float(outs[0].float().abs().max())
 
 
-def test_conv8_two_streams_with_their_own_workspaces(ops):
-    """Student || teacher: two streams run the stream-K variant at once; eager launches get one workspace per stream."""
+def test_conv8_two_streams_at_once(ops):
+    """Student || teacher: two streams run the eight-phase kernel at once."""
     case = CASES[1]
     name, N, H, W, Cin, Cout, k, dil = case
     g = torch.Generator(device=DEV).manual_seed(17)
@@ -151,11 +144,10 @@ def test_conv8_two_streams_with_their_own_workspaces(ops):
         for _ in range(3):
             for i in range(2):
                 with torch.cuda.stream(streams[i]):
-                    ops.conv_igemm(xs[i], ws[i], taps, relu=True, out=outs[i], variant=91)
+                    ops.conv_igemm(xs[i], ws[i], taps, relu=True, out=outs[i], variant=90)
         torch.cuda.synchronize()
         for i in range(2):
-            d = (outs[i].float() - refs[i].float()).abs()
-            assert bool((d <= 2.0 ** -7 * torch.maximum(outs[i].float().abs(), refs[i].float().abs()) + 1e-5).all())
+            assert torch.equal(outs[i], refs[i])        # whole tiles: bit-identical to the 128 x 128 kernel
 
 
 # ------------------------------------------------------------------------------------------------- ReLU masks as bits (round 5)
@@ -213,5 +205,49 @@ def test_conv8_relu_mask_bits_written_forward_and_read_by_the_data_gradient(ops,
     assert torch.equal(ops.conv_igemm(du, wT, one, res=gated, mode=1, variant=99), got90)
     with pytest.raises(ValueError):
         ops.conv_igemm(du, wT, one, mode=1, mask_bits=bits, mask_gates_res=True)          # no residual to gate
-    with pytest.raises(ValueError):
-        ops.conv_igemm(du, wT, one, mode=1, mask_bits=bits, variant=91)                   # stream-K launch: no bits
+    for code in (91, 93):                                                                 # the retired stream-K launch
+        with pytest.raises(ValueError, match='variant {} does not exist'.format(code)):
+            ops.conv_igemm(du, wT, one, mode=1, mask_bits=bits, variant=code)
+
+
+def test_conv8_default_route_allocates_nothing_but_its_output(ops):
+    """The eight-phase kernel needs no scratch: the first default-route launch of a wide, K-deep layer on a fresh stream, eager and
+    while recording a program, grows the allocator by its output and nothing else (the retired stream-K launch kept a workspace of
+    64 KiB + 2 x CUs x 256 KiB, 128 MiB, per stream)."""
+    import ctypes as C
+    from cutmix_semisup_seg_amd import _lib
+    name, N, H, W, Cin, Cout, k, dil = CASES[4]                # one_ragged_tile: ntaps * Cin / 64 = 18 >= 16 K tiles
+    g = torch.Generator(device=DEV).manual_seed(23)
+    taps = ops.conv_taps(k, k, dil, dil * (k - 1) // 2)
+    x = _mk((N, H, W, Cin), g)
+    w = _pack(_mk((Cout, Cin, k, k), g, 0.03))
+    ops.conv_igemm(_mk((1, 4, 4, 64), g), _mk((1, 128, 64), g), [(0, 0)])       # a narrow layer: the zero page exists from here on
+    ref = ops.conv_igemm(x, w, taps, relu=True, variant=99)
+    d = _lib.ConvDesc()
+    d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), ref.data_ptr()
+    d.n, d.h, d.w_in, d.cin, d.ho, d.wo, d.cout, d.cout_real, d.ntaps = N, H, W, Cin, H, W, Cout, Cout, len(taps)
+    for i, (dy, dx) in enumerate(taps):
+        d.tap_dy[i], d.tap_dx[i] = dy, dx
+    d.stride, d.out_h, d.out_w, d.out_stride, d.relu = 1, H, W, 1, 1
+    zp = ops._zero_page(x.device)
+    d.zeros, d.zeros_bytes = zp.data_ptr(), zp.numel() * 2
+    assert int(ops.fn['cms_conv_igemm_route'](C.byref(d))) == 8             # CMS_ROUTE_CONV8
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    before = torch.cuda.memory_allocated()
+    with torch.cuda.stream(side):
+        y = ops.conv_igemm(x, w, taps, relu=True)
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() - before < 2 ** 20
+    assert torch.equal(y, ref)
+    rec_stream = torch.cuda.Stream()
+    prog = ops.Program()
+    out = torch.empty_like(ref)
+    before = torch.cuda.memory_allocated()
+    with ops.recording(prog, [rec_stream]):
+        with torch.cuda.stream(rec_stream):
+            ops.conv_igemm(x, w, taps, relu=True, out=out)
+    assert torch.cuda.memory_allocated() - before < 2 ** 20
+    prog.run([rec_stream])
+    torch.cuda.synchronize()
+    assert torch.equal(out, ref)
