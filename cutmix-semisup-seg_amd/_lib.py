@@ -143,6 +143,13 @@ class ClassMixDesc(C.Structure):
                 ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
+class BoundaryDesc(C.Structure):
+    _fields_ = [('truth', c_void_p), ('pred', c_void_p), ('widths', c_void_p),
+                ('n', c_int), ('h', c_int), ('w', c_int), ('num_classes', c_int), ('ignore_index', c_int), ('k', c_int),
+                ('bcm', c_void_p), ('tcm', c_void_p), ('dist_truth', c_void_p), ('dist_pred', c_void_p),
+                ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('scale', c_void_p),
                 ('ntaps', c_int), ('cout', c_int), ('cin', c_int), ('first_block', c_int)]
@@ -303,6 +310,8 @@ PROTOTYPES = {
     'cms_tta_vote': (c_int, [_P(TtaDesc), c_void_p]),
     'cms_classmix_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cms_classmix': (c_int, [_P(ClassMixDesc), c_void_p]),
+    'cms_boundary_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'cms_boundary_confusion': (c_int, [_P(BoundaryDesc), c_void_p]),
 }
 
 fn = {}

@@ -1,7 +1,7 @@
 """
 Score a trained model: `python eval_seg.py MODEL.pth --dataset pascal_aug [--subset val|test] [--scales 0.5,0.75,1,1.25,1.5,1.75]
 [--flip] [--batch_size 10] [--n_val -1] [--val_seed 131] [--split_path FILE] [--bin_fill_holes] [--save_preds DIR]
-[--compute_dtype bf16|fp32]`.
+[--compute_dtype bf16|fp32] [--boundary_width 3,5,0.02]`.
 
 The reference has no such program: it evaluates inside a training run only, at one scale without a flip. MODEL.pth is the whole-module
 pickle a trainer writes with `--save_model` (or the reference's own). The data set is opened exactly as the trainers open it
@@ -11,9 +11,15 @@ trainer_common.DatasetRun.staged_eval: whole images on a padded canvas, one forw
 kernel (csrc/tta.hip). The output is the trainers': `VAL mIoU=...` (or `TEST mIoU=...`) and the `-- ` per-class line; with the defaults
 (`--scales 1`, no `--flip`) the numbers are bit for bit those of the trainer's last evaluation of that model.
 
+`--boundary_width SPEC` (off by default) adds the contour scores of evaluation.EvaluatorBoundary for up to four band widths, an integer
+being pixels and a number in (0, 1) a ratio of each image's own diagonal: after the two lines above, per width in the order given,
+`VAL BIoU@<w>=...` (Boundary IoU, Cheng et al. 2021) with its per-class line `-- BIoU@<w> ...`, then `VAL trimap@<w>=...` (the IoU over
+the pixels within <w> of a ground-truth boundary) with `-- trimap@<w> ...`. The prediction scored is the one the mIoU line scores
+(the vote, hole-filled with `--bin_fill_holes`); the first two lines do not change.
+
 What keeps the program from starting is said before the GPU is touched: a model file that does not load, a data set that is not
 configured, `--subset test` without a held-out set, `--bin_fill_holes` on more than two classes, a model of another class count, bad
-`--scales`, more than one process.
+`--scales`, a bad `--boundary_width`, more than one process.
 """
 import os
 
@@ -36,11 +42,24 @@ def model_num_classes(net):
     return int(convs[-1].out_channels)
 
 
-def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes):
+def boundary_spec(text):
+    """--boundary_width as [(label, width)] in the order given, the label being the entry as it was typed; None without the option"""
+    if text is None:
+        return None
+    from . import evaluation
+    try:
+        widths = evaluation.parse_boundary_widths(text)
+    except ValueError as e:
+        raise EvalNotRun('--boundary_width: {}'.format(e))
+    return list(zip([p.strip() for p in text.split(',')], widths))
+
+
+def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes, boundary_width=None):
     """Everything that can refuse, on the host -> (tta, net on the CPU, ds_dict, ndx)."""
     from . import tta as tta_mod
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise EvalNotRun('eval_seg runs on one GPU: start one process (WORLD_SIZE={})'.format(os.environ['WORLD_SIZE']))
+    boundary_spec(boundary_width)
     try:
         tta = tta_mod.TTA(tta_mod.parse_scales(scales), flip)
     except ValueError as e:
@@ -77,9 +96,11 @@ def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_pa
 
 
 def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_size=10, n_val=-1, val_seed=131, split_path=None,
-             bin_fill_holes=False, save_preds=None, compute_dtype='bf16'):
-    """-> the per-class IoU (numpy); prints the trainers' lines."""
-    tta, net, ds_dict, ndx = prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes)
+             bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None):
+    """-> the per-class IoU (numpy); prints the trainers' lines, and with `boundary_width` the contour scores after them."""
+    tta, net, ds_dict, ndx = prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes,
+                                     boundary_width)
+    spec = boundary_spec(boundary_width)
 
     import types
     import torch
@@ -100,10 +121,23 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
     if save_preds is not None:
         os.makedirs(save_preds, exist_ok=True)
     iou_eval = evaluation.EvaluatorIoU(run.n_classes, bin_fill_holes)
-    run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta)
+    if spec is None:
+        run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta)
+    else:
+        try:
+            bd_eval = evaluation.EvaluatorBoundary(run.n_classes, [w for _, w in spec])
+        except ValueError as e:
+            raise EvalNotRun('--boundary_width: {}'.format(e))
+        run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta, boundary=bd_eval)
     iou = iou_eval.score()
-    print('{} mIoU={:.3%}'.format('VAL' if subset == 'val' else 'TEST', iou.mean()))
+    prefix = 'VAL' if subset == 'val' else 'TEST'
+    print('{} mIoU={:.3%}'.format(prefix, iou.mean()))
     print('-- {}'.format(', '.join(['{:.3%}'.format(x) for x in iou])))
+    if spec is not None:
+        for (label, _), b_iou, t_iou in zip(spec, bd_eval.boundary_iou(), bd_eval.trimap_iou()):
+            for name, score in (('BIoU', b_iou), ('trimap', t_iou)):
+                print('{} {}@{}={:.3%}'.format(prefix, name, label, score.mean()))
+                print('-- {}@{} {}'.format(name, label, ', '.join(['{:.3%}'.format(x) for x in score])))
     return iou
 
 
@@ -120,12 +154,14 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
 @click.option('--bin_fill_holes', is_flag=True, default=False)
 @click.option('--save_preds', type=click.Path(file_okay=False), default=None)
 @click.option('--compute_dtype', type=click.Choice(['bf16', 'fp32']), default='bf16')
+@click.option('--boundary_width', type=str, default=None)
 def experiment(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-               compute_dtype):
+               compute_dtype, boundary_width):
     if batch_size < 1:
         raise EvalNotRun('--batch_size must be at least 1')
+    boundary_spec(boundary_width)                  # a malformed one is said before the model file is even opened
     evaluate(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-             compute_dtype)
+             compute_dtype, boundary_width)
 
 
 if __name__ == '__main__':

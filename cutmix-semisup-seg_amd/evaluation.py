@@ -49,6 +49,109 @@ def per_class_i_and_u_cm(pred, tru, num_classes, ignore_value=None):
     return diag.copy(), cm.sum(axis=0) + cm.sum(axis=1) - diag, cm
 
 
+def parse_boundary_widths(text):
+    """'3,5,0.02' -> [3, 5, 0.02]: an integer in 1..254 is a band width in pixels, a number in (0, 1) a ratio of the image's own
+    diagonal (Boundary IoU's default is 0.02). One to four entries; anything else raises ValueError."""
+    if not isinstance(text, str):
+        raise ValueError('boundary widths must be given as text such as "3,5,0.02", got {!r}'.format(text))
+    parts = [p.strip() for p in text.split(',')]
+    if not 1 <= len(parts) <= 4:
+        raise ValueError('boundary widths: one to four comma-separated entries, got {!r}'.format(text))
+    out = []
+    for p in parts:
+        try:
+            v = int(p)
+        except ValueError:
+            try:
+                v = float(p)
+            except ValueError:
+                raise ValueError('boundary widths: {!r} is neither a width in pixels nor a ratio of the diagonal'.format(p))
+            if not 0.0 < v < 1.0:             # NaN included
+                raise ValueError('boundary widths: a ratio of the diagonal lies in (0, 1), got {!r}'.format(p))
+        else:
+            if not 1 <= v <= 254:
+                raise ValueError('boundary widths: a width in pixels lies in 1..254, got {!r}'.format(p))
+        out.append(v)
+    return out
+
+
+def boundary_width_px(spec, size):
+    """One entry of a widths specification in pixels for an image of `size` (h, w): the integer itself, or
+    max(1, round(ratio * diagonal)) (at most 254, the widest band the kernel tells apart)."""
+    if isinstance(spec, (int, np.integer)):
+        return int(spec)
+    h, w = size
+    return min(254, max(1, int(round(float(spec) * np.sqrt(float(h * h + w * w))))))
+
+
+class EvaluatorBoundary(object):
+    """Boundary IoU (Cheng et al., CVPR 2021) and trimap IoU over the samples it is given, for up to four band widths at once
+    (`widths_spec`: what parse_boundary_widths returns, or its text). Both follow exactly from two integer matrices per width that
+    ops.boundary_confusion accumulates on the device: `bcm` (K,C+1,C+1) and `tcm` (K,C,C)."""
+
+    def __init__(self, num_classes, widths_spec):
+        if isinstance(widths_spec, str):
+            widths_spec = parse_boundary_widths(widths_spec)
+        widths_spec = list(widths_spec)
+        if not 1 <= len(widths_spec) <= 4:
+            raise ValueError('EvaluatorBoundary: one to four widths, got {}'.format(len(widths_spec)))
+        for v in widths_spec:
+            ok = 1 <= v <= 254 if isinstance(v, (int, np.integer)) else (isinstance(v, float) and 0.0 < v < 1.0)
+            if not ok:
+                raise ValueError('EvaluatorBoundary: a width is an integer in 1..254 or a ratio in (0, 1), got {!r}'.format(v))
+        if not 1 <= int(num_classes) <= 64:
+            raise ValueError('EvaluatorBoundary: 1 <= num_classes <= 64, got {}'.format(num_classes))
+        self.num_classes = int(num_classes)
+        self.widths_spec = widths_spec
+        self._bcm_dev = self._tcm_dev = None
+
+    def _matrices(self):
+        if self._bcm_dev is None:
+            k, c, dev = len(self.widths_spec), self.num_classes, _device()
+            self._bcm_dev = torch.zeros((k, c + 1, c + 1), dtype=torch.int64, device=dev)
+            self._tcm_dev = torch.zeros((k, c, c), dtype=torch.int64, device=dev)
+        return self._bcm_dev, self._tcm_dev
+
+    def sample(self, truth, prediction, sizes=None, ignore_value=255):
+        """Accumulate one (H,W) or batched (N,H,W) pair of integer maps. `sizes`: the (h, w) of every image before padding, which
+        a width given as a ratio of the diagonal refers to; without it the map's own size. The counts of an image do not depend on
+        the padding round it (label `ignore_value`)."""
+        dev = _device()
+        truth = _to_u8_cuda(truth, dev, 'truth')
+        prediction = _to_u8_cuda(prediction, dev, 'prediction')
+        n = int(truth.shape[0]) if truth.dim() == 3 else 1
+        if sizes is None:
+            sizes = [tuple(int(v) for v in truth.shape[-2:])] * n
+        if len(sizes) != n:
+            raise ValueError('EvaluatorBoundary.sample: {} sizes for {} maps'.format(len(sizes), n))
+        widths = np.array([[boundary_width_px(v, s) for v in self.widths_spec] for s in sizes], dtype=np.int32)
+        bcm, tcm = self._matrices()
+        ops.boundary_confusion(truth, prediction, self.num_classes, widths, ignore_index=ignore_value, bcm=bcm, tcm=tcm)
+
+    @property
+    def bcm(self):
+        return self._matrices()[0].cpu().numpy()
+
+    @property
+    def tcm(self):
+        return self._matrices()[1].cpu().numpy()
+
+    def boundary_iou(self):
+        """-> (K, C): bcm[c,c] / max(row c + column c - bcm[c,c], 1), the sums over all C + 1 entries"""
+        m = self.bcm
+        c = self.num_classes
+        diag = np.diagonal(m, axis1=1, axis2=2)[:, :c]
+        union = m.sum(axis=2)[:, :c] + m.sum(axis=1)[:, :c] - diag
+        return diag.astype(float) / np.maximum(union.astype(float), 1.0)
+
+    def trimap_iou(self):
+        """-> (K, C): the IoU over the pixels within the width of a ground-truth boundary"""
+        m = self.tcm
+        diag = np.diagonal(m, axis1=1, axis2=2)
+        union = m.sum(axis=2) + m.sum(axis=1) - diag
+        return diag.astype(float) / np.maximum(union.astype(float), 1.0)
+
+
 class EvaluatorIoU(object):
     def __init__(self, num_classes, fill_holes=False):
         if fill_holes:

@@ -1374,6 +1374,90 @@ def classmix_mask(logits, keys, out_size, align_corners=True, valid=None, out=No
     return out
 
 
+# ---------------------------------------------------------------------------------------------- boundary scores
+_BOUNDARY_WIDTHS = {}       # (device, shape, bytes) -> the int32 table on the device: an evaluation asks for the same few tables
+
+
+def _boundary_widths_on(wd, device):
+    """The device copy of a validated (N,K) int32 table. Tables are small, read-only and repeat from batch to batch, so a table seen
+    before costs no upload (an upload from pageable memory makes the host wait for the stream)."""
+    key = (str(device), wd.shape, wd.tobytes())
+    t = _BOUNDARY_WIDTHS.get(key)
+    if t is None:
+        if len(_BOUNDARY_WIDTHS) >= 256:
+            _BOUNDARY_WIDTHS.clear()
+        t = _BOUNDARY_WIDTHS[key] = torch.from_numpy(wd.copy()).to(device)
+    return t
+
+
+def _boundary_widths(widths, n):
+    """-> int32 (n, K) host array; a list of K ints is broadcast over the batch"""
+    w = np.asarray(widths)
+    if w.dtype.kind not in 'iu' or w.ndim not in (1, 2) or w.size == 0:
+        raise TypeError('boundary_confusion: widths must be K integers or an (N,K) integer array, got {!r}'.format(widths))
+    if w.ndim == 1:
+        w = np.broadcast_to(w[None, :], (n, w.shape[0]))
+    if w.shape[0] != n or not 1 <= w.shape[1] <= 4:
+        raise ValueError('boundary_confusion: widths have shape {}, ({}, 1..4) expected'.format(tuple(w.shape), n))
+    if int(w.min()) < 1 or int(w.max()) > 254:
+        raise ValueError('boundary_confusion: widths must lie in 1..254, got {}..{}'.format(int(w.min()), int(w.max())))
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def boundary_confusion(truth, pred, num_classes, widths, ignore_index=255, bcm=None, tcm=None, want_dist=False):
+    """
+    The counts behind Boundary IoU and trimap IoU (csrc/boundary.hip): truth, pred uint8 CUDA (N,H,W) [or (H,W)], `widths` K <= 4
+    band widths in pixels (a list, the same for every sample, or an (N,K) array). With D the Chebyshev distance of a pixel to the
+    nearest pixel of another value, void pixel (truth == ignore_index) or array edge, in the truth map (D_T) and in the prediction
+    with the void pixels blanked (D_P): bcm[j] (C+1,C+1) += 1 at [D_T <= d ? truth : C, D_P <= d ? pred : C] per non-void pixel, tcm[j]
+    (C,C) += 1 at [truth, pred] per non-void pixel with D_T <= d. Returns (bcm (K,C+1,C+1), tcm (K,C,C), (dist_truth, dist_pred) |
+    None): int64 matrices (accumulated into when given) and, with `want_dist`, the uint8 maps min(D, 255), 0 at void pixels. The
+    number of launches depends on C and K only, and nothing waits for the device but the upload of a widths table not seen before.
+    """
+    if not torch.is_tensor(truth) or not torch.is_tensor(pred):
+        raise TypeError('boundary_confusion: truth and pred must be tensors')
+    if truth.dtype != torch.uint8 or pred.dtype != torch.uint8:
+        raise TypeError('boundary_confusion: uint8 maps required')
+    if truth.dim() not in (2, 3) or truth.shape != pred.shape:
+        raise ValueError('boundary_confusion: truth and pred must be (N,H,W) or (H,W) maps of one shape, got {} and {}'.format(
+            tuple(truth.shape), tuple(pred.shape)))
+    n = int(truth.shape[0]) if truth.dim() == 3 else 1
+    h, w = int(truth.shape[-2]), int(truth.shape[-1])
+    c = int(num_classes)
+    if not 1 <= c <= 64:
+        raise ValueError('boundary_confusion: 1 <= num_classes <= 64, got {}'.format(c))
+    if min(n, h, w) < 1 or n * h * w > 2 ** 31 - 1:
+        raise ValueError('boundary_confusion: {} x {} x {} maps: empty, or more than 2^31 - 1 pixels'.format(n, h, w))
+    wd = _boundary_widths(widths, n)
+    k = int(wd.shape[1])
+    for name, m, shape in (('bcm', bcm, (k, c + 1, c + 1)), ('tcm', tcm, (k, c, c))):
+        if m is not None and (not torch.is_tensor(m) or m.dtype != torch.int64 or tuple(m.shape) != shape or not m.is_contiguous()):
+            raise TypeError('boundary_confusion: {} must be a contiguous int64 tensor of shape {}'.format(name, shape))
+    _need_cuda(truth, pred, bcm, tcm)
+    dev = truth.device
+    truth, pred = truth.contiguous(), pred.contiguous()
+    if bcm is None:
+        bcm = torch.zeros((k, c + 1, c + 1), dtype=torch.int64, device=dev)
+    if tcm is None:
+        tcm = torch.zeros((k, c, c), dtype=torch.int64, device=dev)
+    wd_dev = _boundary_widths_on(wd, dev)
+    dist = None
+    if want_dist:
+        dist = (torch.empty_like(truth), torch.empty_like(truth))
+    d = _lib.BoundaryDesc()
+    d.truth, d.pred, d.widths = truth.data_ptr(), pred.data_ptr(), wd_dev.data_ptr()
+    d.n, d.h, d.w, d.num_classes, d.k = n, h, w, c, k
+    d.ignore_index = -1 if ignore_index is None else int(ignore_index)
+    d.bcm, d.tcm = bcm.data_ptr(), tcm.data_ptr()
+    if dist is not None:
+        d.dist_truth, d.dist_pred = dist[0].data_ptr(), dist[1].data_ptr()
+    need = int(fn['cms_boundary_workspace_bytes'](n, h, w))
+    ws = _workspace_bytes(need, dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(fn['cms_boundary_confusion'](C.byref(d), _stream()), 'cms_boundary_confusion')
+    return bcm, tcm, dist
+
+
 # ---------------------------------------------------------------------------------------------- fp64 FFT / patch distances
 _TWIDDLES = {}
 

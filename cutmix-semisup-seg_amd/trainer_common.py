@@ -367,10 +367,13 @@ class DatasetRun(object):
             print('sup_ndx={}'.format(self.sup_ndx.tolist()))
         return [iter(st) for st in self._streams]
 
-    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None):
+    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None):
         """The reference's evaluation loop over `ndx` in index order: whole images, centred on a padded canvas per batch
         (stage_eval); padding carries label 255 and is ignored. With a `tta.TTA` every batch is evaluated as the vote over its
-        views (eval_seg); `step` is read for `align_corners` only."""
+        views (eval_seg); `step` is read for `align_corners` only. With `boundary` (evaluation.EvaluatorBoundary) the batch's
+        prediction -- hole-filled first, on its canvas as `evaluator` fills it, when that fills holes -- is scored against the labels
+        with every image's own size;
+        the files in `preds_dir` stay the plain prediction."""
         import numpy as np
         import torch
         from . import ops
@@ -378,18 +381,22 @@ class DatasetRun(object):
         with torch.no_grad():
             for batch_ndx in seg_data.eval_batches(ndx, self.batch_size):
                 ev = self.augment.stage_eval(self.pool, batch_ndx, self.student_net.BLOCK_SIZE)
+                want_pred = preds_dir is not None or boundary is not None
                 if tta is not None:
                     _, pred = tta.predict(eval_net, ev['image'], ev['canvas'], step.align_corners, labels=ev['labels'],
-                                          ignore_index=255, want_pred=preds_dir is not None,
+                                          ignore_index=255, want_pred=want_pred,
                                           block_size=self.student_net.BLOCK_SIZE, evaluator=evaluator)
                 else:
                     logits = eval_net.forward_lowres(ev['image'])
                     if evaluator is not None:
                         evaluator.sample_logits(logits, ev['labels'], ev['canvas'], ignore_value=255,
                                                 align_corners=step.align_corners)
-                    if preds_dir is not None:
+                    if want_pred:
                         _, pred = ops.argmax_confusion(logits, None, self.n_classes, ev['canvas'],
                                                        align_corners=step.align_corners, want_pred=True)
+                if boundary is not None:
+                    scored = ops.fill_holes(pred)[0] if getattr(evaluator, 'fill_holes', False) else pred
+                    boundary.sample(ev['labels'][:, 0], scored, sizes=self.pool.sizes_of(batch_ndx), ignore_value=255)
                 if preds_dir is not None:
                     pred = pred.cpu().numpy()
                     for k, sample_ndx in enumerate(batch_ndx):

@@ -1004,6 +1004,44 @@ typedef struct {
 size_t cms_classmix_workspace_bytes(int n, int H, int W);
 int cms_classmix(const cms_classmix_desc* d, void* stream);
 
+/* Boundary IoU (Cheng et al., CVPR 2021) and trimap IoU (the DeepLab papers) as exact integer counts (csrc/boundary.hip). With
+ * T = truth and P = pred with every void pixel (truth == ignore_index) set to ignore_index:
+ *   D_M(p)         for a non-void pixel p of map M, the Chebyshev distance to the nearest position q that lies outside the h x w
+ *                  array or has M(q) != M(p) (a void q is different); D >= 1, 1 on the array's edge. Stored as min(D, 255), 0 at
+ *                  void pixels. D_M <= d is exactly G & ~erode^d(G) of the class mask G = (M == c): d 3 x 3 erosions, zero border
+ *   bcm[j]         (c+1, c+1): with d = widths[i][j] clamped to 1..254, every non-void pixel of sample i whose T and P are classes
+ *                  (< c) adds 1 at [D_T <= d ? T : c, D_P <= d ? P : c]; Boundary IoU of class a is
+ *                  bcm[a][a] / (row a + column a - bcm[a][a]), the sums over all c + 1 entries
+ *   tcm[j]         (c, c): every such pixel with D_T <= d adds 1 at [T, P]; trimap IoU is diag / (row + column - diag)
+ *   truth, pred    (n, h, w) uint8
+ *   widths         (n, k) int32, device memory; needed with bcm or tcm
+ *   ignore_index   < 0: no pixel is void
+ *   bcm, tcm       optional int64 (k, c+1, c+1) / (k, c, c), accumulated into
+ *   dist_truth, dist_pred   optional (n, h, w) uint8, receive the stored D_T / D_P
+ *   workspace      cms_boundary_workspace_bytes(n, h, w) bytes of device memory, 16-byte aligned, need not be initialised; that
+ *                  function returns 0 for sizes cms_boundary_confusion refuses
+ * Stream-ordered launches whose number depends on c and k only (a row pass, a column pass, ceil(k / fit) counting passes with fit
+ * the widths whose histograms fit 64 KiB of LDS), no allocation and no host synchronisation; the workspace is six bytes per pixel. Integer atomics: the same input gives
+ * the same bits. No window crosses from one sample of the batch into the next, and label 255 round an image counts as the outside
+ * of the array does, so an image's counts do not depend on its batch or on the canvas it is padded to. A NULL descriptor, NULL
+ * truth / pred / workspace, NULL widths with bcm or tcm, nothing to produce (bcm, tcm and both distance outputs NULL), k outside
+ * 1..4, num_classes outside 1..64, any of n, h, w below 1, more than 2^31 - 1 pixels, or a workspace that is misaligned or too
+ * small return CMS_EINVAL, decided before any HIP call; nothing is launched. */
+typedef struct {
+    const uint8_t* truth;
+    const uint8_t* pred;
+    const int32_t* widths;
+    int n, h, w, num_classes, ignore_index, k;
+    int64_t* bcm;
+    int64_t* tcm;
+    uint8_t* dist_truth;
+    uint8_t* dist_pred;
+    void* workspace;
+    size_t workspace_bytes;
+} cms_boundary_desc;
+size_t cms_boundary_workspace_bytes(int n, int h, int w);
+int cms_boundary_confusion(const cms_boundary_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
