@@ -143,6 +143,14 @@ class ClassMixDesc(C.Structure):
                 ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
+class CpsDesc(C.Structure):
+    _fields_ = [('l0_a', c_void_p), ('l1_a', c_void_p), ('l0_b', c_void_p), ('l1_b', c_void_p),
+                ('ranges', c_void_p), ('mask', c_void_p), ('um0', c_void_p), ('um1', c_void_p),
+                ('n', c_int), ('c', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int), ('align_corners', c_int),
+                ('n_boxes', c_int), ('invert', c_int), ('conf_thresh', c_float),
+                ('label_a', c_void_p), ('label_b', c_void_p), ('stats', c_void_p)]
+
+
 class BoundaryDesc(C.Structure):
     _fields_ = [('truth', c_void_p), ('pred', c_void_p), ('widths', c_void_p),
                 ('n', c_int), ('h', c_int), ('w', c_int), ('num_classes', c_int), ('ignore_index', c_int), ('k', c_int),
@@ -310,6 +318,7 @@ PROTOTYPES = {
     'cms_tta_vote': (c_int, [_P(TtaDesc), c_void_p]),
     'cms_classmix_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cms_classmix': (c_int, [_P(ClassMixDesc), c_void_p]),
+    'cms_cps_labels': (c_int, [_P(CpsDesc), c_void_p]),
     'cms_boundary_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cms_boundary_confusion': (c_int, [_P(BoundaryDesc), c_void_p]),
 }

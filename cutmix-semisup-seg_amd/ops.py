@@ -1374,6 +1374,79 @@ def classmix_mask(logits, keys, out_size, align_corners=True, valid=None, out=No
     return out
 
 
+# ---------------------------------------------------------------------------------------------- cross pseudo supervision
+def _cps_map(name, t, n, H, W):
+    """an optional f32 (N,1,H,W) / (N,H,W) map -> contiguous f32 (N,H,W)"""
+    if t is None:
+        return None
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if tuple(t.shape) != (n, H, W):
+        raise ValueError('cps_labels: {} has shape {}, {} expected'.format(name, tuple(t.shape), (n, H, W)))
+    return _f32c(t)
+
+
+def cps_labels(l0_a, l1_a, l0_b, l1_b, out_size, ranges=None, mask=None, invert=True, um0=None, um1=None, conf_thresh=0.0,
+               align_corners=True, labels_out=None, stats_out=None):
+    """
+    The hard pseudo-labels two networks give each other on a CutMix-ed pair (csrc/cps.hip): four (N,C,h,w) CUDA logit tensors
+    (converted to fp32 as the loss kernels do), exactly one of `ranges` (int32 (N,nb,4), read under `invert` as the consistency kernels
+    read it) and `mask` (f32 (N,1,H,W) / (N,H,W), >= 0.5 takes image 1), optional validity maps um0 / um1. Per pixel and network k:
+    u_k = the upsampled logits of image 1 where the mask says so, else of image 0; pred_k = argmax u_k; label_k = pred_k where the
+    pixel's validity map is >= 0.5 and (conf_thresh <= 0 or max softmax(u_k) >= conf_thresh), else 255. Returns (label_a, label_b,
+    stats): two uint8 (N,H,W) maps -- `labels_out`, a pair of contiguous uint8 (N,H,W) tensors, when given -- and int64[4]
+    = [valid pixels, labels kept in a, labels kept in b, valid pixels where the predictions agree] (`stats_out` when given). One
+    launch on the current stream, no host synchronisation; the same inputs give the same bits whatever the outputs held.
+    """
+    logits = (l0_a, l1_a, l0_b, l1_b)
+    if not all(torch.is_tensor(t) and t.dim() == 4 for t in logits):
+        raise TypeError('cps_labels: the logits must be four (N,C,h,w) tensors')
+    if any(tuple(t.shape) != tuple(l0_a.shape) for t in logits):
+        raise ValueError('cps_labels: the four logit tensors differ in shape')
+    n, c, h, w = (int(s) for s in l0_a.shape)
+    if min(n, c, h, w) < 1:
+        raise ValueError('cps_labels: empty logits {}'.format(tuple(l0_a.shape)))
+    if c > 64:
+        raise ValueError('cps_labels: 1 <= num_classes <= 64, got {}'.format(c))
+    H, W = _size2(out_size, 'cps_labels: out_size')
+    if h > H or w > W:
+        raise ValueError('cps_labels: logits of {} x {} are larger than the output {} x {}'.format(h, w, H, W))
+    if (ranges is None) == (mask is None):
+        raise ValueError('cps_labels: give exactly one of ranges / mask')
+    _need_cuda(l0_a, l1_a, l0_b, l1_b, ranges, mask, um0, um1, stats_out, *(labels_out or ()))
+    if n > 65535 or n * H * W > 2 ** 31 - 1:
+        raise ValueError('cps_labels: more than 65535 samples or 2^31 - 1 output pixels')
+    l0_a, l1_a, l0_b, l1_b = (_f32c(t) for t in logits)
+    dev = l0_a.device
+    if ranges is not None:
+        if ranges.dtype != torch.int32 or ranges.dim() != 3 or ranges.shape[0] != n or ranges.shape[2] != 4:
+            raise ValueError('cps_labels: ranges must be an int32 ({}, n_boxes, 4) tensor'.format(n))
+        ranges = _nonempty_ranges(ranges).contiguous()
+    mask, um0, um1 = _cps_map('mask', mask, n, H, W), _cps_map('um0', um0, n, H, W), _cps_map('um1', um1, n, H, W)
+    if labels_out is None:
+        # two allocations: each map starts aligned, whatever N * H * W is, and gets the kernel's 4-byte stores
+        labels_out = (torch.empty((n, H, W), dtype=torch.uint8, device=dev), torch.empty((n, H, W), dtype=torch.uint8, device=dev))
+    elif len(labels_out) != 2 or any(t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != (n, H, W) for t in labels_out):
+        raise TypeError('cps_labels: labels_out must be a pair of contiguous uint8 tensors of shape {}'.format((n, H, W)))
+    if stats_out is None:
+        stats_out = torch.empty(4, dtype=torch.int64, device=dev)
+    elif stats_out.dtype != torch.int64 or not stats_out.is_contiguous() or tuple(stats_out.shape) != (4,):
+        raise TypeError('cps_labels: stats_out must be a contiguous int64 tensor of shape (4,)')
+    d = _lib.CpsDesc()
+    d.l0_a, d.l1_a, d.l0_b, d.l1_b = l0_a.data_ptr(), l1_a.data_ptr(), l0_b.data_ptr(), l1_b.data_ptr()
+    d.ranges = ranges.data_ptr() if ranges is not None else None
+    d.mask = mask.data_ptr() if mask is not None else None
+    d.um0 = um0.data_ptr() if um0 is not None else None
+    d.um1 = um1.data_ptr() if um1 is not None else None
+    d.n, d.c, d.h, d.w, d.H, d.W, d.align_corners = n, c, h, w, H, W, int(bool(align_corners))
+    d.n_boxes = int(ranges.shape[1]) if ranges is not None else 0
+    d.invert = int(bool(invert))
+    d.conf_thresh = float(conf_thresh)
+    d.label_a, d.label_b, d.stats = labels_out[0].data_ptr(), labels_out[1].data_ptr(), stats_out.data_ptr()
+    check(fn['cms_cps_labels'](C.byref(d), _stream()), 'cms_cps_labels')
+    return labels_out[0], labels_out[1], stats_out
+
+
 # ---------------------------------------------------------------------------------------------- boundary scores
 _BOUNDARY_WIDTHS = {}       # (device, shape, bytes) -> the int32 table on the device: an evaluation asks for the same few tables
 

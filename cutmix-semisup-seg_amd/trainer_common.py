@@ -474,7 +474,7 @@ def epoch_line(epoch_i, seconds, sup_loss, consistency_loss, conf_rate, miou):
 
 def run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, schedulers, num_epochs, iters_per_epoch,
                freeze_bn, rampup, conf_thresh, n_classes, bin_fill_holes, torch_device, data_parallel,
-               nan_checks_consistency, polls_step_nan, rank=0, img_per_s_of=None):
+               nan_checks_consistency, polls_step_nan, rank=0, img_per_s_of=None, after_epoch=None):
     """'Training...' and the epochs: `step(*make_batch(), ramp_val=...)` per iteration with the losses summed on the device,
     then `evaluate(evaluator)` and the epoch's log lines -> False when the network died (said so; the job ends), else True.
 
@@ -483,6 +483,7 @@ def run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, s
       nan_checks_consistency  a NaN consistency loss ends the job as a NaN supervised loss does
       polls_step_nan          ask `step.nan_detected()` before every iteration as well
       img_per_s_of            (batch_size, world) to print the img/s line after each epoch, None for no such line
+      after_epoch             `after_epoch(epoch_i)` is called behind an epoch's log lines (a trainer's own line), None for nothing
     """
     import time
     import torch
@@ -541,4 +542,6 @@ def run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, s
                 batch_size, world = img_per_s_of
                 print('-- {:.2f} img/s ({} GPU{})'.format(iters_per_epoch * batch_size * world / max(t2 - t1, 1e-9), world,
                                                           's' if world > 1 else ''))
+            if after_epoch is not None:
+                after_epoch(epoch_i)
     return True

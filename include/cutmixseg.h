@@ -1004,6 +1004,43 @@ typedef struct {
 size_t cms_classmix_workspace_bytes(int n, int H, int W);
 int cms_classmix(const cms_classmix_desc* d, void* stream);
 
+/* Cross pseudo supervision (csrc/cps.hip; Chen et al., CVPR 2021): the hard pseudo-labels two networks a and b give each other on a
+ * CutMix-ed pair. Per output pixel (y, x) of sample n, for k = a, b:
+ *   m            "take image 1": the bit the consistency kernels read from `ranges` under `invert`, or mask >= 0.5
+ *   u_k(c)       the bilinear sample (under `align_corners`) of l1_k[n, c] if m, else of l0_k[n, c]; no interpolation when
+ *                (h, w) == (H, W)
+ *   pred_k       argmax over c of u_k(c): first index on a tie, NaN maximal -- with a constant mask, cms_tta_vote's single-view prediction
+ *   conf_k       the largest softmax probability of u_k
+ *   valid        um1 >= 0.5 if m, else um0 >= 0.5; a NULL map is all valid
+ *   label_k      pred_k if valid and (conf_thresh <= 0 or conf_k >= conf_thresh), else 255
+ *   stats        int64 [4]: valid pixels, labels != 255 in label_a, the same in label_b, valid pixels with pred_a == pred_b
+ *   l0_a, l1_a, l0_b, l1_b   (n, c, h, w) f32
+ *   ranges       (n, n_boxes, 4) int32 half-open [y0, y1, x0, x1], or NULL
+ *   mask         (n, H, W) f32, or NULL: exactly one of ranges / mask
+ *   um0, um1     optional (n, H, W) f32
+ *   label_a, label_b   (n, H, W) uint8, every element written; stats: 8-byte aligned, need not be initialised
+ * A 32-byte memset of stats and one launch on `stream`: no workspace, no allocation, no host synchronisation. The counts are
+ * integer atomics: the same input gives the same bits whatever the outputs held, and a sample's labels do not depend on the rest of
+ * its batch. A NULL descriptor, NULL logits / label_a / label_b / stats, c outside 1..64, any of n, h, w, H, W below 1, more than
+ * 65535 samples, h > H or w > W, more than 2^31 - 1 output pixels, logits or range entries, both or neither of ranges / mask, ranges
+ * with n_boxes < 1, or a misaligned stats return CMS_EINVAL, decided before any HIP call; nothing is launched. */
+typedef struct {
+    const float* l0_a;
+    const float* l1_a;
+    const float* l0_b;
+    const float* l1_b;
+    const int32_t* ranges;
+    const float* mask;
+    const float* um0;
+    const float* um1;
+    int n, c, h, w, H, W, align_corners, n_boxes, invert;
+    float conf_thresh;
+    uint8_t* label_a;
+    uint8_t* label_b;
+    int64_t* stats;
+} cms_cps_desc;
+int cms_cps_labels(const cms_cps_desc* d, void* stream);
+
 /* Boundary IoU (Cheng et al., CVPR 2021) and trimap IoU (the DeepLab papers) as exact integer counts (csrc/boundary.hip). With
  * T = truth and P = pred with every void pixel (truth == ignore_index) set to ignore_index:
  *   D_M(p)         for a non-void pixel p of map M, the Chebyshev distance to the nearest position q that lies outside the h x w
