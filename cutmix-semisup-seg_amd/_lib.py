@@ -158,6 +158,16 @@ class BoundaryDesc(C.Structure):
                 ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
+class CrfDesc(C.Structure):
+    _fields_ = [('logits', c_void_p * TTA_MAX_VIEWS), ('h', c_int * TTA_MAX_VIEWS), ('w', c_int * TTA_MAX_VIEWS),
+                ('flip', c_int * TTA_MAX_VIEWS),
+                ('n', c_int), ('c', c_int), ('H', c_int), ('W', c_int), ('k', c_int), ('align_corners', c_int),
+                ('rgb', c_void_p), ('rect', c_void_p), ('radius', c_int), ('dilation', c_int), ('iters', c_int),
+                ('bi_w', c_float), ('bi_xy', c_float), ('bi_rgb', c_float), ('pos_w', c_float), ('pos_xy', c_float),
+                ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int), ('cm', c_void_p), ('pred_out', c_void_p),
+                ('q_out', c_void_p), ('stats', c_void_p)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('scale', c_void_p),
                 ('ntaps', c_int), ('cout', c_int), ('cin', c_int), ('first_block', c_int)]
@@ -321,6 +331,8 @@ PROTOTYPES = {
     'cms_cps_labels': (c_int, [_P(CpsDesc), c_void_p]),
     'cms_boundary_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cms_boundary_confusion': (c_int, [_P(BoundaryDesc), c_void_p]),
+    'cms_crf_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'cms_crf_refine': (c_int, [_P(CrfDesc), c_void_p, c_size_t, c_void_p]),
 }
 
 fn = {}

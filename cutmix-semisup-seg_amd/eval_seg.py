@@ -1,7 +1,8 @@
 """
 Score a trained model: `python eval_seg.py MODEL.pth --dataset pascal_aug [--subset val|test] [--scales 0.5,0.75,1,1.25,1.5,1.75]
 [--flip] [--batch_size 10] [--n_val -1] [--val_seed 131] [--split_path FILE] [--bin_fill_holes] [--save_preds DIR]
-[--compute_dtype bf16|fp32] [--boundary_width 3,5,0.02]`.
+[--compute_dtype bf16|fp32] [--boundary_width 3,5,0.02] [--crf [--crf_iters 5] [--crf_radius 5] [--crf_dilation 3] [--crf_bi_w 4]
+[--crf_bi_xy 15] [--crf_bi_rgb 13] [--crf_pos_w 3] [--crf_pos_xy 3]]`.
 
 The reference has no such program: it evaluates inside a training run only, at one scale without a flip. MODEL.pth is the whole-module
 pickle a trainer writes with `--save_model` (or the reference's own). The data set is opened exactly as the trainers open it
@@ -17,9 +18,15 @@ being pixels and a number in (0, 1) a ratio of each image's own diagonal: after 
 the pixels within <w> of a ground-truth boundary) with `-- trimap@<w> ...`. The prediction scored is the one the mIoU line scores
 (the vote, hole-filled with `--bin_fill_holes`); the first two lines do not change.
 
+`--crf` (off by default) refines every batch's vote against its image before anything is counted: crf.py's truncated, dilated-window
+form of the fully connected CRF the DeepLab papers report their numbers after (csrc/crf.hip). The refined prediction is what the mIoU
+line, `--bin_fill_holes`, `--boundary_width` and `--save_preds` then see, and after the two lines above one more says what it did:
+`-- CRF changed x.xxx% of the pixels`. The `--crf_*` values are crf.CRFParams'; their defaults are not tuned. Without `--crf` every
+printed line and every saved file is what it was.
+
 What keeps the program from starting is said before the GPU is touched: a model file that does not load, a data set that is not
 configured, `--subset test` without a held-out set, `--bin_fill_holes` on more than two classes, a model of another class count, bad
-`--scales`, a bad `--boundary_width`, more than one process.
+`--scales`, a bad `--boundary_width`, a bad `--crf_*` value or one without `--crf`, more than one process.
 """
 import os
 
@@ -52,6 +59,18 @@ def boundary_spec(text):
     except ValueError as e:
         raise EvalNotRun('--boundary_width: {}'.format(e))
     return list(zip([p.strip() for p in text.split(',')], widths))
+
+
+CRF_OPTIONS = ('crf_iters', 'crf_radius', 'crf_dilation', 'crf_bi_w', 'crf_bi_xy', 'crf_bi_rgb', 'crf_pos_w', 'crf_pos_xy')
+
+
+def crf_spec(crf, **options):
+    """--crf and the --crf_* values as they were typed (None where not given) -> crf.CRFParams, or None without --crf"""
+    from . import crf as crf_mod
+    try:
+        return crf_mod.CRFParams.from_options(bool(crf), **options)
+    except ValueError as e:
+        raise EvalNotRun(str(e))
 
 
 def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes, boundary_width=None):
@@ -96,8 +115,11 @@ def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_pa
 
 
 def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_size=10, n_val=-1, val_seed=131, split_path=None,
-             bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None):
-    """-> the per-class IoU (numpy); prints the trainers' lines, and with `boundary_width` the contour scores after them."""
+             bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None, crf=None):
+    """-> the per-class IoU (numpy); prints the trainers' lines, with `crf` (crf.CRFParams) what the refinement changed, and with
+    `boundary_width` the contour scores after them."""
+    if crf is not None and not hasattr(crf, 'as_dict'):
+        raise EvalNotRun('crf must be a crf.CRFParams, got {!r}'.format(crf))
     tta, net, ds_dict, ndx = prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes,
                                      boundary_width)
     spec = boundary_spec(boundary_width)
@@ -121,18 +143,22 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
     if save_preds is not None:
         os.makedirs(save_preds, exist_ok=True)
     iou_eval = evaluation.EvaluatorIoU(run.n_classes, bin_fill_holes)
-    if spec is None:
-        run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta)
-    else:
+    more = {} if crf is None else dict(crf=crf)
+    bd_eval = None
+    if spec is not None:
         try:
             bd_eval = evaluation.EvaluatorBoundary(run.n_classes, [w for _, w in spec])
         except ValueError as e:
             raise EvalNotRun('--boundary_width: {}'.format(e))
-        run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta, boundary=bd_eval)
+        more['boundary'] = bd_eval
+    crf_stats = run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta, **more)
     iou = iou_eval.score()
     prefix = 'VAL' if subset == 'val' else 'TEST'
     print('{} mIoU={:.3%}'.format(prefix, iou.mean()))
     print('-- {}'.format(', '.join(['{:.3%}'.format(x) for x in iou])))
+    if crf is not None:
+        pixels, changed = (int(v) for v in crf_stats.cpu().tolist())
+        print('-- CRF changed {:.3%} of the pixels'.format(changed / max(pixels, 1)))
     if spec is not None:
         for (label, _), b_iou, t_iou in zip(spec, bd_eval.boundary_iou(), bd_eval.trimap_iou()):
             for name, score in (('BIoU', b_iou), ('trimap', t_iou)):
@@ -155,13 +181,23 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
 @click.option('--save_preds', type=click.Path(file_okay=False), default=None)
 @click.option('--compute_dtype', type=click.Choice(['bf16', 'fp32']), default='bf16')
 @click.option('--boundary_width', type=str, default=None)
+@click.option('--crf', is_flag=True, default=False)
+@click.option('--crf_iters', type=str, default=None, help='5')
+@click.option('--crf_radius', type=str, default=None, help='5')
+@click.option('--crf_dilation', type=str, default=None, help='3')
+@click.option('--crf_bi_w', type=str, default=None, help='4')
+@click.option('--crf_bi_xy', type=str, default=None, help='15')
+@click.option('--crf_bi_rgb', type=str, default=None, help='13')
+@click.option('--crf_pos_w', type=str, default=None, help='3')
+@click.option('--crf_pos_xy', type=str, default=None, help='3')
 def experiment(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-               compute_dtype, boundary_width):
+               compute_dtype, boundary_width, crf, **crf_options):
     if batch_size < 1:
         raise EvalNotRun('--batch_size must be at least 1')
     boundary_spec(boundary_width)                  # a malformed one is said before the model file is even opened
+    params = crf_spec(crf, **crf_options)          # ... and so is a malformed --crf_* value, or one without --crf
     evaluate(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-             compute_dtype, boundary_width)
+             compute_dtype, boundary_width, params)
 
 
 if __name__ == '__main__':

@@ -1171,6 +1171,136 @@ def tta_vote(logits_list, flips, num_classes, out_size, labels=None, ignore_inde
     return cm, pred
 
 
+CRF_LIMITS = dict(radius=(1, 5), dilation=(1, 16), iters=(1, 32))
+CRF_WEIGHTS, CRF_THETAS = ('bi_w', 'pos_w'), ('bi_xy', 'bi_rgb', 'pos_xy')
+
+
+def crf_checked_params(params):
+    """`params` (crf.CRFParams, or anything with its eight attributes / keys) -> dict of plain numbers inside the kernel's limits;
+    TypeError / ValueError otherwise. No torch, no GPU."""
+    import math
+    get = (lambda k: params[k]) if isinstance(params, dict) else (lambda k: getattr(params, k))
+    out = {}
+    try:
+        for k, (lo, hi) in CRF_LIMITS.items():
+            v = get(k)
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError('crf_refine: {} must be an integer, got {!r}'.format(k, v))
+            if not lo <= int(v) <= hi:
+                raise ValueError('crf_refine: {} <= {} <= {}, got {}'.format(lo, k, hi, v))
+            out[k] = int(v)
+        for k in CRF_WEIGHTS + CRF_THETAS:
+            v = float(get(k))
+            if not math.isfinite(v) or v > 3.0e38 or (v < 0.0 if k in CRF_WEIGHTS else v <= 0.0):
+                raise ValueError('crf_refine: {} must be finite and {} 0, got {}'.format(k, '>=' if k in CRF_WEIGHTS else '>', v))
+            out[k] = v
+    except (KeyError, AttributeError) as e:
+        raise TypeError('crf_refine: params lacks {}'.format(e))
+    return out
+
+
+def _crf_rects(rects, n, H, W):
+    """(n, 4) (top, left, h, w) on the HOST (numpy, list or CPU tensor) -> contiguous int32 numpy, every rectangle on the canvas"""
+    if torch.is_tensor(rects):
+        if rects.is_cuda:
+            raise TypeError('crf_refine: rects must live on the host (they are checked before anything is launched)')
+        rects = rects.numpy()
+    r = np.asarray(rects)
+    if r.dtype.kind not in 'iu' or r.shape != (n, 4):
+        raise TypeError('crf_refine: rects must be an integer array of shape {}, got {} {}'.format((n, 4), r.dtype, r.shape))
+    r = r.astype(np.int64)
+    if (r[:, :2] < 0).any() or (r[:, 2:] < 1).any() or (r[:, 0] + r[:, 2] > H).any() or (r[:, 1] + r[:, 3] > W).any():
+        raise ValueError('crf_refine: a rectangle is empty or leaves the {} x {} canvas: {}'.format(H, W, r.tolist()))
+    return np.ascontiguousarray(r, dtype=np.int32)
+
+
+def crf_refine(logits_list, flips, rgb, rects, num_classes, out_size, params, labels=None, ignore_index=255, align_corners=True,
+               cm=None, pred=None, want_q=False, stats_out=None):
+    """
+    CRF refinement of the vote over the views of a batch against its image (csrc/crf.hip; include/cutmixseg.h states the
+    definition): logits_list / flips as tta_vote's, rgb (N,3,H,W) uint8 CUDA, rects (N,4) = (top, left, h, w) of every image on the
+    canvas, on the HOST, params a crf.CRFParams. labels (N,H,W) / (N,1,H,W) uint8 / int64 or None; `cm`, `pred`, `stats_out`
+    (int64 [2]): contiguous CUDA tensors to accumulate into / fill. Returns (cm | None, pred uint8 (N,H,W), q fp32 (N,C,H,W) | None,
+    stats int64 [2] = [pixels inside rectangles, of those the refined labels that differ from the unary ones]). Everything is
+    refused before the GPU is touched; no host synchronisation.
+    """
+    prm = crf_checked_params(params)
+    logits_list = list(logits_list)
+    flips = [bool(f) for f in flips]
+    k = len(logits_list)
+    if k < 1 or k > _lib.TTA_MAX_VIEWS:
+        raise ValueError('crf_refine: {} views, 1 to {} are built'.format(k, _lib.TTA_MAX_VIEWS))
+    if len(flips) != k:
+        raise ValueError('crf_refine: {} views but {} flips'.format(k, len(flips)))
+    if any(not torch.is_tensor(t) or t.dim() != 4 for t in logits_list):
+        raise TypeError('crf_refine: every view must be an (N,C,h,w) tensor')
+    if any(t.dtype != torch.float32 for t in logits_list):
+        raise TypeError('crf_refine: the views must be float32')
+    num_classes = int(num_classes)
+    if num_classes < 1 or num_classes > 64:
+        raise ValueError('crf_refine: 1 <= num_classes <= 64, got {}'.format(num_classes))
+    H, W = _size2(out_size, 'crf_refine: out_size')
+    n = int(logits_list[0].shape[0])
+    for t in logits_list:
+        if int(t.shape[0]) != n or int(t.shape[1]) != num_classes or min(int(s) for s in t.shape) < 1:
+            raise ValueError('crf_refine: a view of shape {} among views of {} samples and {} classes'.format(
+                tuple(t.shape), n, num_classes))
+    if n * H * W > 2 ** 31 - 1:
+        raise ValueError('crf_refine: more than 2^31 - 1 output pixels')
+    if not torch.is_tensor(rgb) or rgb.dtype != torch.uint8:
+        raise TypeError('crf_refine: rgb must be a uint8 tensor')
+    if tuple(rgb.shape) != (n, 3, H, W):
+        raise ValueError('crf_refine: rgb of shape {}, {} expected'.format(tuple(rgb.shape), (n, 3, H, W)))
+    rects = _crf_rects(rects, n, H, W)
+    if labels is not None:
+        if not torch.is_tensor(labels) or labels.dtype not in (torch.uint8, torch.int64):
+            raise TypeError('crf_refine: labels must be a uint8 or int64 tensor')
+        if labels.dim() == 4:
+            labels = labels[:, 0]
+        if tuple(labels.shape) != (n, H, W):
+            raise ValueError('crf_refine: labels of shape {}, {} expected'.format(tuple(labels.shape), (n, H, W)))
+    if cm is not None:
+        if labels is None:
+            raise ValueError('crf_refine: cm given without labels')
+        if not torch.is_tensor(cm) or cm.dtype != torch.int64 or tuple(cm.shape) != (num_classes, num_classes) or not cm.is_contiguous():
+            raise TypeError('crf_refine: cm must be a contiguous int64 ({0},{0}) matrix'.format(num_classes))
+    if pred is not None:
+        if not torch.is_tensor(pred) or pred.dtype != torch.uint8 or not pred.is_contiguous() or tuple(pred.shape) != (n, H, W):
+            raise TypeError('crf_refine: pred must be a contiguous uint8 tensor of shape {}'.format((n, H, W)))
+    if stats_out is not None:
+        if (not torch.is_tensor(stats_out) or stats_out.dtype != torch.int64 or not stats_out.is_contiguous()
+                or tuple(stats_out.shape) != (2,)):
+            raise TypeError('crf_refine: stats_out must be a contiguous int64 tensor of 2 elements')
+    _need_cuda(rgb, labels, cm, pred, stats_out, *logits_list)
+    views = [t.contiguous() for t in logits_list]          # kept alive until the launches are queued
+    dev = views[0].device
+    rgb = rgb.contiguous()
+    if labels is not None:
+        labels = labels.contiguous()
+        if cm is None:
+            cm = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=dev)
+    if pred is None:
+        pred = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    q = torch.empty((n, num_classes, H, W), dtype=torch.float32, device=dev) if want_q else None
+    stats = stats_out if stats_out is not None else torch.empty(2, dtype=torch.int64, device=dev)
+    nbytes = int(fn['cms_crf_workspace_bytes'](n, num_classes, H, W))
+    work = _workspace_bytes(nbytes, dev)
+    d = _lib.CrfDesc()
+    for i, t in enumerate(views):
+        d.logits[i], d.h[i], d.w[i], d.flip[i] = t.data_ptr(), int(t.shape[2]), int(t.shape[3]), int(flips[i])
+    d.n, d.c, d.H, d.W, d.k, d.align_corners = n, num_classes, H, W, k, int(bool(align_corners))
+    d.rgb, d.rect = rgb.data_ptr(), rects.ctypes.data
+    d.radius, d.dilation, d.iters = prm['radius'], prm['dilation'], prm['iters']
+    d.bi_w, d.bi_xy, d.bi_rgb, d.pos_w, d.pos_xy = prm['bi_w'], prm['bi_xy'], prm['bi_rgb'], prm['pos_w'], prm['pos_xy']
+    d.labels = labels.data_ptr() if labels is not None else None
+    d.label_dtype = _lib.LABEL_I64 if labels is not None and labels.dtype == torch.int64 else _lib.LABEL_U8
+    d.ignore_index = -1 if ignore_index is None else int(ignore_index)
+    d.cm = cm.data_ptr() if cm is not None else None
+    d.pred_out, d.q_out, d.stats = pred.data_ptr(), (q.data_ptr() if q is not None else None), stats.data_ptr()
+    check(fn['cms_crf_refine'](C.byref(d), _ptr(work), nbytes, _stream()), 'cms_crf_refine')
+    return cm, pred, q, stats
+
+
 # ---------------------------------------------------------------------------------------------- converter downsampling
 def _downsample_u8(name, src, d, out, channels):
     _need_cuda(src, out)

@@ -367,22 +367,40 @@ class DatasetRun(object):
             print('sup_ndx={}'.format(self.sup_ndx.tolist()))
         return [iter(st) for st in self._streams]
 
-    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None):
+    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None, crf=None):
         """The reference's evaluation loop over `ndx` in index order: whole images, centred on a padded canvas per batch
         (stage_eval); padding carries label 255 and is ignored. With a `tta.TTA` every batch is evaluated as the vote over its
         views (eval_seg); `step` is read for `align_corners` only. With `boundary` (evaluation.EvaluatorBoundary) the batch's
         prediction -- hole-filled first, on its canvas as `evaluator` fills it, when that fills holes -- is scored against the labels
         with every image's own size;
-        the files in `preds_dir` stay the plain prediction."""
+        the files in `preds_dir` stay the plain prediction. With `crf` (crf.CRFParams) the batch's views -- one without `tta` -- are
+        forwarded as above and the vote is refined against the canvas' bytes inside every image's rectangle (ops.crf_refine); the
+        refined prediction is what `evaluator.sample` counts (its hole filling applies to it), what `boundary` scores and what
+        `preds_dir` receives, and the call returns the device-side int64 [pixels, labels the refinement changed] (else None)."""
         import numpy as np
         import torch
         from . import ops
         from .datapipe import seg_data
+        crf_total = None
+        if crf is not None:
+            from . import crf as crf_mod, tta as tta_mod
+            crf_views = tta if tta is not None else tta_mod.TTA((1.0,), False)
+            crf_total = torch.zeros(2, dtype=torch.int64, device=self.pool.image_buffer.device)
         with torch.no_grad():
             for batch_ndx in seg_data.eval_batches(ndx, self.batch_size):
                 ev = self.augment.stage_eval(self.pool, batch_ndx, self.student_net.BLOCK_SIZE)
                 want_pred = preds_dir is not None or boundary is not None
-                if tta is not None:
+                if crf is not None:
+                    block = self.student_net.BLOCK_SIZE
+                    logits = [l.float() for l in crf_views.forward_views(eval_net, ev['image'], block)]
+                    pred, stats = crf_mod.refine_batch(
+                        crf, logits, [f for _, f in crf_views.views()], crf_mod.canvas_rgb(self.augment, self.pool, batch_ndx, block),
+                        crf_mod.rects_of(ev['offsets'], self.pool.sizes_of(batch_ndx)), self.n_classes, ev['canvas'],
+                        step.align_corners)
+                    crf_total += stats
+                    if evaluator is not None:
+                        evaluator.sample(ev['labels'][:, 0], pred, ignore_value=255)
+                elif tta is not None:
                     _, pred = tta.predict(eval_net, ev['image'], ev['canvas'], step.align_corners, labels=ev['labels'],
                                           ignore_index=255, want_pred=want_pred,
                                           block_size=self.student_net.BLOCK_SIZE, evaluator=evaluator)
@@ -401,6 +419,7 @@ class DatasetRun(object):
                     pred = pred.cpu().numpy()
                     for k, sample_ndx in enumerate(batch_ndx):
                         self.ds_src.save_prediction_by_index(preds_dir, pred[k].astype(np.uint32), sample_ndx)
+        return crf_total
 
     def evaluate_with(self, eval_net, step):
         """-> the `evaluate(evaluator)` of run_epochs over the validation set."""

@@ -1079,6 +1079,54 @@ typedef struct {
 size_t cms_boundary_workspace_bytes(int n, int h, int w);
 int cms_boundary_confusion(const cms_boundary_desc* d, void* stream);
 
+/* CRF refinement of a prediction against its image (csrc/crf.hip). This project's own truncated form of the fully connected CRF of
+ * Kraehenbuehl & Koltun (NIPS 2011) with the two DeepLab kernels, in the spirit of Convolutional CRFs (Teichmann & Cipolla, BMVC
+ * 2018): mean-field inference with a Potts compatibility over a dilated square window, cut to each sample's rectangle. The reference
+ * has nothing of the kind. Per pixel p of sample i:
+ *   P(p, c)      cms_tta_vote's score of the k views for every k (k == 1: the softmax of the upsampled logits), divided by k;
+ *                logP = log(max(P, FLT_MIN)), Q^0 = P. The unary prediction is the first index of the largest score
+ *   W(p)         { p + dilation (dy, dx) : |dy|, |dx| <= radius, (dy, dx) != 0 } cut to the rectangle rect[i] = (top, left, h, w);
+ *                n(p) = |W(p)|, an exact integer. Padding and pixels of another sample are never neighbours
+ *   k(p, q)      [ bi_w exp(-|p-q|^2 / (2 bi_xy^2) - |I_p-I_q|^2 / (2 bi_rgb^2)) + pos_w exp(-|p-q|^2 / (2 pos_xy^2)) ] / n(p),
+ *                I the rgb bytes as grey levels 0..255; divided by the neighbour COUNT, not the sum of the kernel values
+ *   Q^{t+1}(p,.) softmax_c( logP(p, c) + sum over q in W(p) of k(p, q) Q^t(q, c) ), all pixels at once (Jacobi), t < iters;
+ *                the sum runs over the window in row-major (dy, dx) order in fp32; no neighbour, no message
+ *   pred         inside the rectangle the first index of the largest Q^iters, outside it the unary prediction
+ *   logits, h, w, flip, n, c, H, W, k, align_corners, labels, label_dtype, ignore_index, cm   as cms_tta_desc's
+ *   rgb          (n, 3, H, W) uint8, device memory
+ *   rect         (n, 4) int32 in HOST memory: it is checked before anything is launched and travels as kernel arguments
+ *   pred_out     optional uint8 (n, H, W); q_out optional f32 (n, c, H, W): Q^iters inside the rectangles, P outside
+ *   stats        int64 [2], device memory, 8-byte aligned, need not be initialised: pixels inside rectangles, of those the
+ *                pixels whose pred differs from the unary prediction
+ *   workspace    cms_crf_workspace_bytes(n, c, H, W) bytes of device memory, 16-byte aligned, need not be initialised; that
+ *                function returns 0 for sizes cms_crf_refine refuses
+ * Per group of 32 samples one unary launch and `iters` mean-field launches on `stream` (ping-pong Q in the workspace; the last
+ * one fuses argmax, histogram and counts), plus a 16-byte memset of stats; no allocation, no host synchronisation. The histogram
+ * and counts are integer atomics: the same input gives the same bits, and given the same P and rgb a sample's result does not
+ * depend on its batch, its canvas or its offset on it. A NULL descriptor, NULL logits[i] / rgb / rect / stats / workspace, k
+ * outside 1..16, c outside 1..64, any of n, H, W, h[i], w[i] below 1, radius outside 1..5, dilation outside 1..16, iters outside
+ * 1..32, a weight that is negative or not finite, a theta that is not finite and > 0, a rectangle that is empty or leaves the
+ * canvas, cm without labels, nothing to produce, an unknown label_dtype with labels, more than 2^31 - 1 output pixels, a misaligned
+ * stats, or a workspace that is misaligned or too small return CMS_EINVAL, decided before any HIP call; nothing is launched. */
+typedef struct {
+    const float* logits[CMS_TTA_MAX_VIEWS];
+    int h[CMS_TTA_MAX_VIEWS], w[CMS_TTA_MAX_VIEWS], flip[CMS_TTA_MAX_VIEWS];
+    int n, c, H, W, k, align_corners;
+    const uint8_t* rgb;
+    const int32_t* rect;
+    int radius, dilation, iters;
+    float bi_w, bi_xy, bi_rgb, pos_w, pos_xy;
+    const void* labels;
+    int label_dtype;      /* CMS_LABEL_U8 / CMS_LABEL_I64 */
+    int ignore_index;
+    int64_t* cm;
+    uint8_t* pred_out;
+    float* q_out;
+    int64_t* stats;
+} cms_crf_desc;
+size_t cms_crf_workspace_bytes(int n, int c, int H, int W);
+int cms_crf_refine(const cms_crf_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,253 @@
+"""Test helper: the fp64 restatement, in plain numpy, of the CRF refinement (csrc/crf.hip; include/cutmixseg.h and DESIGN 8 state the
+definition) -- the unary term from _tta_refs.vote, then mean-field inference with shifted arrays -- the cases the CPU and GPU tests
+share, and the driver of the host-check program (tests/hostcheck_crf). Nothing here imports the product."""
+import functools
+import os
+import struct
+import subprocess
+
+import numpy as np
+
+import _tta_refs as T
+
+FLT_MIN = float(np.finfo(np.float32).tiny)
+
+# The bound on |Q - Q_fp64|: twice the larger of (a) the host-check program's largest error over every case below, 2.29e-6
+# (`pytest tests/test_crf_hostcheck.py -s` prints it per case), and (b) the kernel's on the MI355X, 2.41e-6 (2026-10-20,
+# `pytest tests/test_gpu_crf.py -s -k restatement`), rounded up to two digits. Both are the error of the unary term -- the fp32
+# sample positions of the bilinear taps the vote kernel shares, pixel_math.hpp's bilin_tap -- carried through the iterations; given
+# the same P the mean field itself stays within 3e-7. DESIGN 8 keeps the record.
+B = 4.9e-6
+
+# the parameters of every case: the defaults of eval_seg's options but for radius / dilation / iterations
+PARAMS = dict(bi_w=4.0, bi_xy=15.0, bi_rgb=13.0, pos_w=3.0, pos_xy=3.0)
+MIN_CHANGED = 0.02
+
+
+# ------------------------------------------------------------------------------------------------------------------ the definition
+def unary(logits_list, flips, size, align_corners):
+    """-> (P (n,c,H,W) fp64, unary prediction uint8, top-two gap of the vote score): the vote's score over k, a softmax for k == 1"""
+    k = len(logits_list)
+    score, pred, gap = T.vote(logits_list, flips, size, align_corners)
+    if k == 1:
+        p = T.softmax(score, 1)
+        pred = p.argmax(axis=1).astype(np.uint8)
+        if p.shape[1] > 1:
+            top = np.sort(p, axis=1)
+            gap = top[:, -1] - top[:, -2]
+        return p, pred, gap
+    return score / k, pred, gap
+
+
+def pair_weights(img, radius, dilation, bi_w, bi_xy, bi_rgb, pos_w, pos_xy):
+    """img (3,h,w) grey levels -> [(oy, ox, weight (h,w) over the destination pixels whose neighbour p + (oy, ox) is inside)] and
+    the neighbour count n(p) (h,w)"""
+    img = np.asarray(img, dtype=np.float64)
+    h, w = img.shape[1:]
+    out, count = [], np.zeros((h, w), dtype=np.int64)
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            oy, ox = dilation * dy, dilation * dx
+            if (dy == 0 and dx == 0) or abs(oy) >= h or abs(ox) >= w:
+                continue
+            ys, xs = slice(max(0, -oy), min(h, h - oy)), slice(max(0, -ox), min(w, w - ox))
+            yq, xq = slice(ys.start + oy, ys.stop + oy), slice(xs.start + ox, xs.stop + ox)
+            d2 = float(oy * oy + ox * ox)
+            di = ((img[:, ys, xs] - img[:, yq, xq]) ** 2).sum(axis=0)
+            kq = bi_w * np.exp(-d2 / (2 * bi_xy ** 2) - di / (2 * bi_rgb ** 2)) + pos_w * np.exp(-d2 / (2 * pos_xy ** 2))
+            out.append((ys, xs, yq, xq, kq))
+            count[ys, xs] += 1
+    return out, count
+
+
+def mean_field(p, rgb, rects, radius, dilation, iters, bi_w, bi_xy, bi_rgb, pos_w, pos_xy):
+    """P (n,c,H,W) fp64, rgb (n,3,H,W) uint8, rects (n,4) -> Q^iters (n,c,H,W) fp64, P outside the rectangles"""
+    q_all = np.array(p, dtype=np.float64, copy=True)
+    for i, (top, left, h, w) in enumerate(np.asarray(rects).tolist()):
+        win = (slice(None), slice(top, top + h), slice(left, left + w))
+        pi = q_all[i][win]
+        logp = np.log(np.maximum(pi, FLT_MIN))
+        pairs, count = pair_weights(rgb[i][win], radius, dilation, bi_w, bi_xy, bi_rgb, pos_w, pos_xy)
+        q = pi.copy()
+        for _ in range(iters):
+            msg = np.zeros_like(q)
+            for ys, xs, yq, xq, kq in pairs:
+                msg[:, ys, xs] += kq * q[:, yq, xq]
+            msg = np.where(count > 0, msg / np.maximum(count, 1), 0.0)
+            q = T.softmax(logp + msg, 0)
+        q_all[i][win] = q
+    return q_all
+
+
+def inside_mask(shape, rects):
+    n, H, W = shape
+    m = np.zeros(shape, dtype=bool)
+    for i, (top, left, h, w) in enumerate(np.asarray(rects).tolist()):
+        m[i, top:top + h, left:left + w] = True
+    return m
+
+
+def refine(logits, flips, rgb, rects, size, align, radius, dilation, iters, labels=None, **prm):
+    """The whole definition -> dict(q, pred, unary_pred, gap (min top-two gap of Q^T inside the rectangles), unary_gap (min score
+    gap over every pixel), stats, cm | None, changed (the share of in-rectangle labels that differ from the unary prediction))"""
+    prm = dict(PARAMS, **prm)
+    n, c = logits[0].shape[:2]
+    p, upred, ugap = unary(logits, flips, size, align)
+    q = mean_field(p, rgb, rects, radius, dilation, iters, **prm)
+    inside = inside_mask((n,) + tuple(size), rects)
+    pred = np.where(inside, q.argmax(axis=1), upred).astype(np.uint8)
+    if c > 1:
+        top = np.sort(q, axis=1)
+        gap = float((top[:, -1] - top[:, -2])[inside].min())
+    else:
+        gap = np.inf
+    stats = np.array([inside.sum(), (pred != upred)[inside].sum()], dtype=np.int64)
+    cm = T.confusion(labels, pred, c) if labels is not None else None
+    return dict(q=q, pred=pred, unary_pred=upred, gap=gap, unary_gap=float(np.min(ugap)), stats=stats, cm=cm,
+                changed=float(stats[1]) / float(stats[0]))
+
+
+# ------------------------------------------------------------------------------------------------------------------ inputs
+def make_image(n, H, W, seed):
+    """piecewise constant: 8 x 8 blocks of random colour plus 3 % uniform noise, rounded -> uint8 (n,3,H,W)"""
+    rng = np.random.RandomState(seed + 500)
+    blocks = rng.uniform(0.0, 255.0, size=(n, 3, (H + 7) // 8, (W + 7) // 8))
+    img = np.repeat(np.repeat(blocks, 8, axis=2), 8, axis=3)[:, :, :H, :W]
+    img = img + rng.uniform(-0.03 * 255.0, 0.03 * 255.0, size=img.shape)
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+MAIN = (2, 37, 53)
+MAIN_VIEWS = [(5, 7), (9, 13), (37, 53)]                      # low-resolution, low-resolution, the canvas' own size
+# the defaults barely move a label where the classes are many or the window's steps are wider than the image's 8 x 8 blocks: there
+# both kernels are given more weight and reach, so that the 2 % condition below can hold
+STRONG = dict(bi_w=8.0, bi_rgb=30.0, pos_w=6.0, pos_xy=5.0)
+WIDE = dict(bi_w=8.0, bi_xy=40.0, bi_rgb=80.0, pos_w=6.0, pos_xy=20.0)
+MAIN_RECTS = ((1, 2, 34, 49), (3, 4, 34, 49))                 # 3 padded rows and 4 padded columns, elsewhere per sample
+SMALL_VIEWS = [(2, 3), (5, 7), (3, 4)]
+
+# name -> what the case is. `seed`: searched on the CPU (tests/test_crf_cpu.py::test_case_margins re-checks) so that the fp64 top-two
+# gap of Q^T is at least 4 B at every in-rectangle pixel, the unary score gap at least _tta_refs.gap_bound(k) everywhere, and the
+# refinement changes at least 2 % of the in-rectangle labels.
+CASES = {
+    'c2_r1s1_t1_k1': dict(shape=MAIN, rects=MAIN_RECTS, c=2, radius=1, dilation=1, iters=1, k=1, align=True, seed=14),
+    'c5_r2s3_t5_k3': dict(shape=MAIN, rects=MAIN_RECTS, c=5, radius=2, dilation=3, iters=5, k=3, align=False, seed=5),
+    'c21_r5s3_t5_k1': dict(shape=MAIN, rects=MAIN_RECTS, c=21, radius=5, dilation=3, iters=5, k=1, align=True, seed=19, prm=STRONG),
+    'c64_r5s3_t1_k3': dict(shape=MAIN, rects=MAIN_RECTS, c=64, radius=5, dilation=3, iters=1, k=3, align=False, seed=19, prm=STRONG),
+    'c21_r5s16_t5_k3': dict(shape=MAIN, rects=MAIN_RECTS, c=21, radius=5, dilation=16, iters=5, k=3, align=True, seed=14, prm=WIDE),
+    'c64_r2s3_t5_k1': dict(shape=MAIN, rects=MAIN_RECTS, c=64, radius=2, dilation=3, iters=5, k=1, align=True, seed=0, prm=STRONG),
+    'c5_r5s3_t1_k1': dict(shape=MAIN, rects=MAIN_RECTS, c=5, radius=5, dilation=3, iters=1, k=1, align=False, seed=12),
+    'c2_r1s1_t5_k3': dict(shape=MAIN, rects=MAIN_RECTS, c=2, radius=1, dilation=1, iters=5, k=3, align=False, seed=17),
+    'tiny_5x7': dict(shape=(1, 5, 7), rects=((0, 0, 5, 7),), c=5, radius=2, dilation=3, iters=5, k=1, align=True, seed=9,
+                     views=SMALL_VIEWS),
+    # a rectangle of one pixel has no neighbour (n = 0) and keeps its unary label; it rides with a second sample that has some
+    'one_pixel': dict(shape=(2, 5, 7), rects=((2, 3, 1, 1), (0, 1, 5, 6)), c=5, radius=1, dilation=1, iters=5, k=3, align=False,
+                      seed=16, views=SMALL_VIEWS),
+    'full_canvas': dict(shape=MAIN, rects=((0, 0, 37, 53), (0, 0, 37, 53)), c=5, radius=2, dilation=3, iters=5, k=1, align=True,
+                        seed=21),
+}
+
+
+def case_inputs(name, seed=None):
+    spec = CASES[name]
+    seed = spec['seed'] if seed is None else seed
+    n, H, W = spec['shape']
+    logits, flips = T.make_views(spec['k'], spec['c'], n, seed, spec.get('views', MAIN_VIEWS))
+    if spec['k'] >= 2:
+        flips[1] = True                                       # every vote has a flip
+    rgb = make_image(n, H, W, seed)
+    labels = T.make_labels((n, H, W), spec['c'], seed)
+    spec = dict(spec, prm=dict(PARAMS, **spec.get('prm', {})))
+    return dict(spec, logits=logits, flips=flips, rgb=rgb, labels=labels, rects=np.array(spec['rects'], dtype=np.int32),
+                size=(H, W), name=name)
+
+
+@functools.lru_cache(maxsize=None)
+def case(name, iters=None):
+    """-> (inputs, reference), computed once; `iters` overrides the case's"""
+    inp = case_inputs(name)
+    if iters is not None:
+        inp['iters'] = iters
+    ref = refine(inp['logits'], inp['flips'], inp['rgb'], inp['rects'], inp['size'], inp['align'], inp['radius'], inp['dilation'],
+                 inp['iters'], labels=inp['labels'], **inp['prm'])
+    return inp, ref
+
+
+def margins_ok(ref, k):
+    return ref['gap'] >= 4 * B and ref['unary_gap'] >= T.gap_bound(k) and ref['changed'] >= MIN_CHANGED
+
+
+def search_seed(name, tries=40):
+    for seed in range(tries):
+        inp = case_inputs(name, seed)
+        ref = refine(inp['logits'], inp['flips'], inp['rgb'], inp['rects'], inp['size'], inp['align'], inp['radius'],
+                     inp['dilation'], inp['iters'], **inp['prm'])
+        if margins_ok(ref, inp['k']):
+            return seed, ref
+    raise AssertionError('no seed for ' + name)
+
+
+def compare(got, ref, bound=B):
+    """Q within the bound at every element, labels and both counts equal at every pixel -> the largest |Q - Q_fp64|"""
+    err = float(np.abs(np.asarray(got['q'], dtype=np.float64) - ref['q']).max())
+    assert err <= bound, err
+    assert np.array_equal(got['pred'], ref['pred']), int((got['pred'] != ref['pred']).sum())
+    if got.get('unary_pred') is not None:
+        assert np.array_equal(got['unary_pred'], ref['unary_pred'])
+    assert np.array_equal(np.asarray(got['stats']), ref['stats']), (got['stats'], ref['stats'])
+    return err
+
+
+# ------------------------------------------------------------------------------------------------------------------ host driver
+GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
+
+
+def hostcheck_source():
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), 'hostcheck_crf', 'hostcheck_crf.cpp')
+
+
+def hostcheck_build(directory, sanitize=False):
+    """compile tests/hostcheck_crf (a stand-alone program with its own main) into `directory` -> its path"""
+    exe = os.path.join(str(directory), 'hostcheck_crf_asan' if sanitize else 'hostcheck_crf')
+    extra = ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
+    subprocess.check_call(GXX + extra + [hostcheck_source(), '-o', exe])
+    return exe
+
+
+_count = [0]
+
+
+def hostcheck_run(exe, directory, inp, expect_code=0, **over):
+    """one request through the host driver -> dict(q, pred, unary_pred, stats), or None when it ends with `expect_code` != 0.
+    `over`: header fields sent as they are."""
+    n, c = inp['logits'][0].shape[:2]
+    H, W = inp['size']
+    head = dict(n=n, c=c, H=H, W=W, k=len(inp['logits']), align=int(inp['align']), radius=inp['radius'], dilation=inp['dilation'],
+                iters=inp['iters'])
+    prm = dict(inp.get('prm', PARAMS))
+    rects = over.pop('rects', inp['rects'])
+    for key, val in over.items():
+        (head if key in head else prm)[key] = val
+    _count[0] += 1
+    req = os.path.join(str(directory), 'req{}.bin'.format(_count[0]))
+    res = os.path.join(str(directory), 'res{}.bin'.format(_count[0]))
+    with open(req, 'wb') as f:
+        f.write(struct.pack('<9i5f', head['n'], head['c'], head['H'], head['W'], head['k'], head['align'], head['radius'],
+                            head['dilation'], head['iters'], prm['bi_w'], prm['bi_xy'], prm['bi_rgb'], prm['pos_w'], prm['pos_xy']))
+        for t, fl in zip(inp['logits'], inp['flips']):
+            f.write(struct.pack('<3i', t.shape[2], t.shape[3], int(fl)))
+        for t in inp['logits']:
+            f.write(np.ascontiguousarray(t, dtype=np.float32).tobytes())
+        f.write(np.ascontiguousarray(inp['rgb'], dtype=np.uint8).tobytes())
+        f.write(np.ascontiguousarray(rects, dtype=np.int32).tobytes())
+    code = subprocess.call([exe, req, res])
+    assert code == expect_code, code
+    if code != 0:
+        return None
+    raw = open(res, 'rb').read()
+    pix = n * H * W
+    assert len(raw) == 4 * pix * c + 2 * pix + 16
+    return dict(q=np.frombuffer(raw[:4 * pix * c], dtype=np.float32).reshape(n, c, H, W),
+                pred=np.frombuffer(raw[4 * pix * c:4 * pix * c + pix], dtype=np.uint8).reshape(n, H, W),
+                unary_pred=np.frombuffer(raw[4 * pix * c + pix:4 * pix * c + 2 * pix], dtype=np.uint8).reshape(n, H, W),
+                stats=np.frombuffer(raw[4 * pix * c + 2 * pix:], dtype=np.int64))
