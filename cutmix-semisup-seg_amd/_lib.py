@@ -158,6 +158,13 @@ class BoundaryDesc(C.Structure):
                 ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
+class SurfaceDesc(C.Structure):
+    _fields_ = [('truth', c_void_p), ('pred', c_void_p),
+                ('n', c_int), ('h', c_int), ('w', c_int), ('num_classes', c_int), ('ignore_index', c_int),
+                ('stats', c_void_p), ('sums', c_void_p), ('d2_pred', c_void_p), ('d2_truth', c_void_p),
+                ('workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
 class CrfDesc(C.Structure):
     _fields_ = [('logits', c_void_p * TTA_MAX_VIEWS), ('h', c_int * TTA_MAX_VIEWS), ('w', c_int * TTA_MAX_VIEWS),
                 ('flip', c_int * TTA_MAX_VIEWS),
@@ -333,6 +340,8 @@ PROTOTYPES = {
     'cms_boundary_confusion': (c_int, [_P(BoundaryDesc), c_void_p]),
     'cms_crf_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cms_crf_refine': (c_int, [_P(CrfDesc), c_void_p, c_size_t, c_void_p]),
+    'cms_surface_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'cms_surface_distances': (c_int, [_P(SurfaceDesc), c_void_p]),
 }
 
 fn = {}

@@ -2,7 +2,7 @@
 Score a trained model: `python eval_seg.py MODEL.pth --dataset pascal_aug [--subset val|test] [--scales 0.5,0.75,1,1.25,1.5,1.75]
 [--flip] [--batch_size 10] [--n_val -1] [--val_seed 131] [--split_path FILE] [--bin_fill_holes] [--save_preds DIR]
 [--compute_dtype bf16|fp32] [--boundary_width 3,5,0.02] [--crf [--crf_iters 5] [--crf_radius 5] [--crf_dilation 3] [--crf_bi_w 4]
-[--crf_bi_xy 15] [--crf_bi_rgb 13] [--crf_pos_w 3] [--crf_pos_xy 3]]`.
+[--crf_bi_xy 15] [--crf_bi_rgb 13] [--crf_pos_w 3] [--crf_pos_xy 3]] [--surface_dist]`.
 
 The reference has no such program: it evaluates inside a training run only, at one scale without a flip. MODEL.pth is the whole-module
 pickle a trainer writes with `--save_model` (or the reference's own). The data set is opened exactly as the trainers open it
@@ -23,6 +23,14 @@ form of the fully connected CRF the DeepLab papers report their numbers after (c
 line, `--bin_fill_holes`, `--boundary_width` and `--save_preds` then see, and after the two lines above one more says what it did:
 `-- CRF changed x.xxx% of the pixels`. The `--crf_*` values are crf.CRFParams'; their defaults are not tuned. Without `--crf` every
 printed line and every saved file is what it was.
+
+`--surface_dist` (off by default) adds the surface distances of evaluation.EvaluatorSurface, in pixels of the evaluated image, after
+every line above: `VAL HD95=...` with its per-class line `-- HD95 ...`, then `VAL ASSD=...` / `-- ASSD ...` and `VAL HD=...` / `-- HD ...`
+(the Hausdorff distance, its 95th percentile and the average symmetric surface distance in MedPy's convention; csrc/surface.hip), and
+`-- surface pairs ... (one-sided ...)`. A class is scored in the images in which both the labels and the prediction hold it; its
+number is the mean over those images, `-` when there is none, and the headline the mean over the classes that have one. The images
+in which only one of the two holds the class are counted as one-sided. The prediction scored is the one `--boundary_width` scores.
+Without the option every printed line and every saved file is what it was.
 
 What keeps the program from starting is said before the GPU is touched: a model file that does not load, a data set that is not
 configured, `--subset test` without a held-out set, `--bin_fill_holes` on more than two classes, a model of another class count, bad
@@ -115,9 +123,9 @@ def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_pa
 
 
 def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_size=10, n_val=-1, val_seed=131, split_path=None,
-             bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None, crf=None):
-    """-> the per-class IoU (numpy); prints the trainers' lines, with `crf` (crf.CRFParams) what the refinement changed, and with
-    `boundary_width` the contour scores after them."""
+             bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None, crf=None, surface_dist=False):
+    """-> the per-class IoU (numpy); prints the trainers' lines, with `crf` (crf.CRFParams) what the refinement changed, with
+    `boundary_width` the contour scores after them, and with `surface_dist` the surface distances after those."""
     if crf is not None and not hasattr(crf, 'as_dict'):
         raise EvalNotRun('crf must be a crf.CRFParams, got {!r}'.format(crf))
     tta, net, ds_dict, ndx = prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes,
@@ -151,6 +159,9 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
         except ValueError as e:
             raise EvalNotRun('--boundary_width: {}'.format(e))
         more['boundary'] = bd_eval
+    sf_eval = None
+    if surface_dist:
+        sf_eval = more['surface'] = evaluation.EvaluatorSurface(run.n_classes)
     crf_stats = run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta, **more)
     iou = iou_eval.score()
     prefix = 'VAL' if subset == 'val' else 'TEST'
@@ -164,6 +175,13 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
             for name, score in (('BIoU', b_iou), ('trimap', t_iou)):
                 print('{} {}@{}={:.3%}'.format(prefix, name, label, score.mean()))
                 print('-- {}@{} {}'.format(name, label, ', '.join(['{:.3%}'.format(x) for x in score])))
+    if sf_eval is not None:
+        for name, score in (('HD95', sf_eval.hd95()), ('ASSD', sf_eval.assd()), ('HD', sf_eval.hd())):
+            print('{} {}={:.3f}'.format(prefix, name, sf_eval.headline(score)))
+            print('-- {} {}'.format(name, ', '.join(['-' if x != x else '{:.3f}'.format(x) for x in score])))
+        scored, one_sided = sf_eval.pairs()
+        print('-- surface pairs {} (one-sided {})'.format(', '.join(str(int(x)) for x in scored),
+                                                          ', '.join(str(int(x)) for x in one_sided)))
     return iou
 
 
@@ -190,14 +208,15 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
 @click.option('--crf_bi_rgb', type=str, default=None, help='13')
 @click.option('--crf_pos_w', type=str, default=None, help='3')
 @click.option('--crf_pos_xy', type=str, default=None, help='3')
+@click.option('--surface_dist', is_flag=True, default=False)
 def experiment(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-               compute_dtype, boundary_width, crf, **crf_options):
+               compute_dtype, boundary_width, crf, surface_dist, **crf_options):
     if batch_size < 1:
         raise EvalNotRun('--batch_size must be at least 1')
     boundary_spec(boundary_width)                  # a malformed one is said before the model file is even opened
     params = crf_spec(crf, **crf_options)          # ... and so is a malformed --crf_* value, or one without --crf
     evaluate(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-             compute_dtype, boundary_width, params)
+             compute_dtype, boundary_width, params, surface_dist)
 
 
 if __name__ == '__main__':

@@ -1661,6 +1661,54 @@ def boundary_confusion(truth, pred, num_classes, widths, ignore_index=255, bcm=N
     return bcm, tcm, dist
 
 
+# ---------------------------------------------------------------------------------------------- surface distances
+def surface_distances(truth, pred, num_classes, ignore_index=255, want_maps=False):
+    """
+    What HD, HD95 and ASSD follow from (csrc/surface.hip): truth, pred uint8 CUDA (N,H,W) [or (H,W)]. Per image and class, with G the
+    class mask of the truth, S that of the prediction with the void pixels (truth == ignore_index) blanked and the surface of a mask
+    its pixels with a 4-neighbour outside it: d2 is the exact squared Euclidean distance from a surface pixel of one mask to the
+    nearest surface pixel of the other. Returns (stats int64 (N,C,6) = [|dS|, |dG|, max d2 over dS, max d2 over dG, a[lo], a[hi]] with a
+    the sorted pooled d2 and lo, hi the ranks behind numpy.percentile(., 95); sums float64 (N,C,2) = the two directed sums of sqrt(d2);
+    with `want_maps` (d2_pred, d2_truth) int32 (N,H,W), -1 off the surfaces, else None). A pair with an empty G or S is not scored:
+    its counts, -1 in the other four and 0.0. A fixed number of launches; nothing waits for the device.
+    """
+    if not torch.is_tensor(truth) or not torch.is_tensor(pred):
+        raise TypeError('surface_distances: truth and pred must be tensors')
+    if truth.dtype != torch.uint8 or pred.dtype != torch.uint8:
+        raise TypeError('surface_distances: uint8 maps required')
+    if truth.dim() not in (2, 3) or truth.shape != pred.shape:
+        raise ValueError('surface_distances: truth and pred must be (N,H,W) or (H,W) maps of one shape, got {} and {}'.format(
+            tuple(truth.shape), tuple(pred.shape)))
+    n = int(truth.shape[0]) if truth.dim() == 3 else 1
+    h, w = int(truth.shape[-2]), int(truth.shape[-1])
+    c = int(num_classes)
+    if not 1 <= c <= 64:
+        raise ValueError('surface_distances: 1 <= num_classes <= 64, got {}'.format(c))
+    if min(n, h, w) < 1 or max(h, w) > 16384 or n * h * w > 2 ** 31 - 1:
+        raise ValueError('surface_distances: {} x {} x {} maps: empty, a side above 16384, or more than 2^31 - 1 pixels'.format(n, h, w))
+    _need_cuda(truth, pred)
+    dev = truth.device
+    truth, pred = truth.contiguous(), pred.contiguous()
+    stats = torch.empty((n, c, 6), dtype=torch.int64, device=dev)
+    sums = torch.empty((n, c, 2), dtype=torch.float64, device=dev)
+    maps = None
+    if want_maps:
+        maps = (torch.empty((n, h, w), dtype=torch.int32, device=dev), torch.empty((n, h, w), dtype=torch.int32, device=dev))
+    d = _lib.SurfaceDesc()
+    d.truth, d.pred = truth.data_ptr(), pred.data_ptr()
+    d.n, d.h, d.w, d.num_classes = n, h, w, c
+    d.ignore_index = -1 if ignore_index is None else int(ignore_index)
+    d.stats, d.sums = stats.data_ptr(), sums.data_ptr()
+    if maps is not None:
+        d.d2_pred, d.d2_truth = maps[0].data_ptr(), maps[1].data_ptr()
+    ws = _workspace_bytes(int(fn['cms_surface_workspace_bytes'](n, h, w, c)), dev)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(fn['cms_surface_distances'](C.byref(d), _stream()), 'cms_surface_distances')
+    if maps is not None and truth.dim() == 2:
+        maps = (maps[0][0], maps[1][0])
+    return stats, sums, maps
+
+
 # ---------------------------------------------------------------------------------------------- fp64 FFT / patch distances
 _TWIDDLES = {}
 

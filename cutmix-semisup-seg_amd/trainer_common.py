@@ -367,15 +367,15 @@ class DatasetRun(object):
             print('sup_ndx={}'.format(self.sup_ndx.tolist()))
         return [iter(st) for st in self._streams]
 
-    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None, crf=None):
+    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None, crf=None, surface=None):
         """The reference's evaluation loop over `ndx` in index order: whole images, centred on a padded canvas per batch
         (stage_eval); padding carries label 255 and is ignored. With a `tta.TTA` every batch is evaluated as the vote over its
         views (eval_seg); `step` is read for `align_corners` only. With `boundary` (evaluation.EvaluatorBoundary) the batch's
         prediction -- hole-filled first, on its canvas as `evaluator` fills it, when that fills holes -- is scored against the labels
         with every image's own size;
-        the files in `preds_dir` stay the plain prediction. With `crf` (crf.CRFParams) the batch's views -- one without `tta` -- are
+        the files in `preds_dir` stay the plain prediction. `surface` (evaluation.EvaluatorSurface) is given the map `boundary` is. With `crf` (crf.CRFParams) the batch's views -- one without `tta` -- are
         forwarded as above and the vote is refined against the canvas' bytes inside every image's rectangle (ops.crf_refine); the
-        refined prediction is what `evaluator.sample` counts (its hole filling applies to it), what `boundary` scores and what
+        refined prediction is what `evaluator.sample` counts (its hole filling applies to it), what `boundary` and `surface` score and what
         `preds_dir` receives, and the call returns the device-side int64 [pixels, labels the refinement changed] (else None)."""
         import numpy as np
         import torch
@@ -389,7 +389,7 @@ class DatasetRun(object):
         with torch.no_grad():
             for batch_ndx in seg_data.eval_batches(ndx, self.batch_size):
                 ev = self.augment.stage_eval(self.pool, batch_ndx, self.student_net.BLOCK_SIZE)
-                want_pred = preds_dir is not None or boundary is not None
+                want_pred = preds_dir is not None or boundary is not None or surface is not None
                 if crf is not None:
                     block = self.student_net.BLOCK_SIZE
                     logits = [l.float() for l in crf_views.forward_views(eval_net, ev['image'], block)]
@@ -412,9 +412,12 @@ class DatasetRun(object):
                     if want_pred:
                         _, pred = ops.argmax_confusion(logits, None, self.n_classes, ev['canvas'],
                                                        align_corners=step.align_corners, want_pred=True)
-                if boundary is not None:
+                if boundary is not None or surface is not None:
                     scored = ops.fill_holes(pred)[0] if getattr(evaluator, 'fill_holes', False) else pred
-                    boundary.sample(ev['labels'][:, 0], scored, sizes=self.pool.sizes_of(batch_ndx), ignore_value=255)
+                    if boundary is not None:
+                        boundary.sample(ev['labels'][:, 0], scored, sizes=self.pool.sizes_of(batch_ndx), ignore_value=255)
+                    if surface is not None:
+                        surface.sample(ev['labels'][:, 0], scored, ignore_value=255)
                 if preds_dir is not None:
                     pred = pred.cpu().numpy()
                     for k, sample_ndx in enumerate(batch_ndx):

@@ -1127,6 +1127,45 @@ typedef struct {
 size_t cms_crf_workspace_bytes(int n, int c, int H, int W);
 int cms_crf_refine(const cms_crf_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Surface distances between a truth and a prediction map as exact integers (csrc/surface.hip): what the Hausdorff distance (HD,
+ * Huttenlocher et al. 1993), its 95th percentile (HD95) and the average symmetric surface distance (ASSD) follow from, in MedPy's
+ * convention with connectivity 1 and unit spacing. With T = truth and P = pred with every void pixel (truth == ignore_index) set
+ * to void, per sample i and class c < num_classes, G = (T_i == c) and S = (P_i == c):
+ *   surface        dM: the pixels of a mask M with at least one of their FOUR edge neighbours outside M; a neighbour outside the
+ *                  h x w array, or a void one, is outside M (M & ~binary_erosion(M, cross, border_value=0)). Boundary IoU uses
+ *                  the 3 x 3 neighbourhood; this does not
+ *   d2(p, dG)      min over q in dG of (py - qy)^2 + (px - qx)^2, an exact integer < 2^30
+ *   scored         the pair (i, c) when G and S are both non-empty
+ *   stats          int64 (n, c, 6), written: [|dS|, |dG|, max d2(p, dG) over dS, max d2(q, dS) over dG, a[lo], a[hi]] with a the
+ *                  sorted pooled multiset of all |dS| + |dG| = m squared distances, lo = 19 (m - 1) / 20 (integer division) and
+ *                  hi = min(lo + 1, m - 1): numpy.percentile(sqrt(a), 95) is sqrt(a[lo]) + (19 (m - 1) % 20) / 20 * (sqrt(a[hi])
+ *                  - sqrt(a[lo])). An unscored pair gets its two counts and -1 in the other four
+ *   sums           double (n, c, 2), written: [sum over dS of sqrt(d2(p, dG)), sum over dG of sqrt(d2(q, dS))], 0.0 for an unscored
+ *                  pair. Summed in a fixed order without atomics: the same input gives the same bits
+ *   d2_pred, d2_truth   optional int32 (n, h, w): d2 at every surface pixel of a scored pair (dS / dG), -1 everywhere else
+ *   truth, pred    (n, h, w) uint8;  ignore_index < 0: no pixel is void
+ *   workspace      cms_surface_workspace_bytes(n, h, w, num_classes) bytes of device memory, 16-byte aligned, need not be
+ *                  initialised; that function returns 0 for sizes cms_surface_distances refuses
+ * A fixed number of stream-ordered launches (one memset, mark, rows, column walk, and with stats or sums a reduction and four
+ * radix-select passes), no allocation, no host synchronisation, no float atomics. Distances are between pixels of one sample only,
+ * and label 255 round an image counts as the outside of the array does, so a sample's numbers do not depend on its batch or on the
+ * canvas it is padded to. A NULL descriptor, NULL truth / pred / workspace, nothing to produce (stats, sums and both maps NULL),
+ * num_classes outside 1..64, any of n, h, w below 1, h or w above 16384, 2^31 pixels or more, or a workspace that is misaligned or
+ * too small return CMS_EINVAL, decided before any HIP call; nothing is launched. */
+typedef struct {
+    const uint8_t* truth;
+    const uint8_t* pred;
+    int n, h, w, num_classes, ignore_index;
+    int64_t* stats;
+    double* sums;
+    int32_t* d2_pred;
+    int32_t* d2_truth;
+    void* workspace;
+    size_t workspace_bytes;
+} cms_surface_desc;
+size_t cms_surface_workspace_bytes(int n, int h, int w, int num_classes);
+int cms_surface_distances(const cms_surface_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

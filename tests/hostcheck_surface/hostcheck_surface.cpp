@@ -1,0 +1,239 @@
+// test infrastructure: a stand-alone host driver of the product's surface-distance arithmetic (csrc/surface_math.hpp), the very
+// functions the kernels of csrc/surface.hip call, walked workgroup by workgroup, lane by lane and pixel by pixel as the launches walk
+// them. A ballot of the kernel is a loop over the 64 lanes here, a tree in LDS a loop over its steps.
+//
+//   hostcheck_surface REQUEST RESULT
+//
+// REQUEST, little-endian: int32 n, h, w, num_classes, ignore_index; then the (n, h, w) uint8 truth and the (n, h, w) uint8 prediction.
+// RESULT: n * c * 6 int64 stats, n * c * 2 double sums, n * h * w int32 d2_pred, n * h * w int32 d2_truth.
+// The workspace has exactly the bytes the product asks for and the layout the product gives it, and all of it but the part the
+// product clears with its memset is filled with 0xA5 before use, so a sanitizer build sees every byte outside it and a byte a later
+// pass reads without an earlier one having written it shows in the result. Exit code 2 for a request the product refuses (the
+// refusal is the product's own check).
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../cutmix-semisup-seg_amd/csrc/surface_math.hpp"
+
+using namespace cms;
+typedef unsigned long long u64;
+
+static void* read_block(FILE* f, size_t bytes) {
+    void* p = malloc(bytes ? bytes : 1);
+    if (!p || fread(p, 1, bytes, f) != bytes) exit(1);
+    return p;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 3) {
+        fprintf(stderr, "usage: hostcheck_surface REQUEST RESULT\n");
+        return 1;
+    }
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) return 1;
+    int32_t head[5];
+    if (fread(head, sizeof(int32_t), 5, f) != 5) return 1;
+    cms_surface_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = head[0], d.h = head[1], d.w = head[2], d.num_classes = head[3], d.ignore_index = head[4];
+    // the product's verdict on the sizes before anything is read or allocated by them
+    alignas(16) static char probe[16];
+    d.truth = d.pred = (const uint8_t*)probe, d.stats = (int64_t*)probe, d.workspace = probe;
+    d.workspace_bytes = (size_t)-1;
+    if (surface_check(&d)) return 2;
+    const int n = d.n, H = d.h, W = d.w, C = d.num_classes, ignore = d.ignore_index;
+    const size_t hw = (size_t)H * W, pix = (size_t)n * hw, pairs = (size_t)n * C;
+    uint8_t* truth = (uint8_t*)read_block(f, pix);
+    uint8_t* pred = (uint8_t*)read_block(f, pix);
+    fclose(f);
+    const SfLayout l = surface_layout(n, H, W, C);
+    const size_t ws_bytes = surface_workspace_bytes(n, H, W, C);
+    if (ws_bytes != l.total) return 3;
+    uint8_t* ws = (uint8_t*)aligned_alloc(16, ws_bytes);
+    memset(ws, 0xA5, ws_bytes);
+    memset(ws, 0, l.zeroed);                                             // the call's hipMemsetAsync
+    int64_t* stats = (int64_t*)malloc(pairs * 6 * sizeof(int64_t));
+    double* sums = (double*)malloc(pairs * 2 * sizeof(double));
+    d.truth = truth, d.pred = pred, d.stats = stats, d.sums = sums, d.workspace = ws, d.workspace_bytes = ws_bytes;
+    if (surface_check(&d)) return 2;
+    int32_t* counts = (int32_t*)(ws + l.counts);
+    uint32_t* hist = (uint32_t*)(ws + l.hist);
+    SfState* state = (SfState*)(ws + l.state);
+    SfPartial* partial = (SfPartial*)(ws + l.partial);
+    uint8_t *surf_t = ws + l.surf, *surf_p = surf_t + l.map;
+    int32_t *d2_pred = (int32_t*)(ws + l.d2), *d2_truth = (int32_t*)(ws + l.d2 + l.d2map);
+    uint16_t *rows_t = (uint16_t*)(ws + l.rows), *rows_p = (uint16_t*)(ws + l.rows + l.plane);
+
+    // ---- pass 1: a thread per pixel, the counts of a "workgroup" in a block of exactly its bins
+    for (int i = 0; i < n; ++i) {
+        unsigned int* bins = (unsigned int*)calloc(2 * C, sizeof(unsigned int));
+        const size_t base = (size_t)i * hw;
+        for (size_t k = 0; k < hw; ++k) {
+            const int y = (int)(k / W), x = (int)(k - (size_t)y * W);
+            const SfPair s = sf_surface(truth + base, pred + base, x, y, H, W, ignore, C);
+            surf_t[base + k] = (uint8_t)s.t, surf_p[base + k] = (uint8_t)s.p;
+            if (s.p != kSfNoClass) bins[2 * s.p] += 1;
+            if (s.t != kSfNoClass) bins[2 * s.t + 1] += 1;
+        }
+        for (int b = 0; b < 2 * C; ++b) counts[(size_t)i * 2 * C + b] += (int32_t)bins[b];
+        free(bins);
+    }
+
+    // ---- pass 2: a wavefront per row of a (map, sample, class) plane
+    const int chunks = (W + kSfLanes - 1) / kSfLanes;
+    for (long long item = 0; item < 2ll * n * C * H; ++item) {
+        const int y = (int)(item % H);
+        const long long pc = item / H;
+        const int c = (int)(pc % C);
+        const long long mi = pc / C;
+        const int i = (int)(mi % n), map = (int)(mi / n);
+        if (!sf_scored(counts + ((size_t)i * C + c) * 2)) continue;
+        const uint8_t* srow = (map ? surf_p : surf_t) + ((size_t)i * H + y) * W;
+        uint16_t* out = (map ? rows_p : rows_t) + (((size_t)i * C + c) * H + y) * W;
+        auto ballot = [&](int cx) {
+            u64 m = 0;
+            for (int lane = 0; lane < kSfLanes; ++lane) m |= (u64)(cx + lane < W && srow[cx + lane] == c) << lane;
+            return m;
+        };
+        int last = -1;
+        for (int k = 0; k < chunks; ++k) {
+            const int cx = k * kSfLanes;
+            const u64 m = ballot(cx);
+            for (int lane = 0; lane < kSfLanes; ++lane)
+                if (cx + lane < W) out[cx + lane] = (uint16_t)sf_row_left(m, lane, cx + lane, last);
+            last = sf_carry_last(m, cx, last);
+        }
+        if (last < 0) continue;
+        int next = -1;
+        for (int k = chunks - 1; k >= 0; --k) {
+            const int cx = k * kSfLanes;
+            const u64 m = ballot(cx);
+            for (int lane = 0; lane < kSfLanes; ++lane)
+                if (cx + lane < W) {
+                    const int x = cx + lane, left = out[x], r = sf_row_right(m, lane, x, next);
+                    if (r < left) out[x] = (uint16_t)r;
+                }
+            next = sf_carry_next(m, cx, next);
+        }
+    }
+
+    // ---- pass 3: a thread per pixel
+    for (size_t idx = 0; idx < pix; ++idx) {
+        const size_t i = idx / hw, k = idx - i * hw;
+        const int y = (int)(k / W);
+        const size_t col = k - (size_t)y * W;
+        const int sp = surf_p[idx], st = surf_t[idx];
+        int32_t dp = -1, dt = -1;
+        if (sp != kSfNoClass && sf_scored(counts + (i * C + sp) * 2)) {
+            const uint16_t* plane = rows_t + (i * C + sp) * hw + col;
+            dp = sf_column_walk(plane[(size_t)y * W], y, H, [&](int yy) { return (int)plane[(size_t)yy * W]; });
+        }
+        if (st != kSfNoClass && sf_scored(counts + (i * C + st) * 2)) {
+            const uint16_t* plane = rows_p + (i * C + st) * hw + col;
+            dt = sf_column_walk(plane[(size_t)y * W], y, H, [&](int yy) { return (int)plane[(size_t)yy * W]; });
+        }
+        d2_pred[idx] = dp, d2_truth[idx] = dt;
+    }
+
+    // ---- pass 4: a "workgroup" per (sample, class, slab), its tree in blocks of exactly kSfBlock entries; then a thread per pair
+    const int slabs = sf_slabs(H, W);
+    const size_t len = (size_t)sf_slab_len(H, W);
+    for (size_t b = 0; b < pairs * slabs; ++b) {
+        const int slab = (int)(b % slabs);
+        const size_t pair = b / slabs, i = pair / C, base = i * hw;
+        const int c = (int)(pair - i * C);
+        if (!sf_scored(counts + pair * 2)) continue;
+        const size_t lo = slab * len, hi = lo + len < hw ? lo + len : hw;
+        double* sum[2] = {(double*)calloc(kSfBlock, sizeof(double)), (double*)calloc(kSfBlock, sizeof(double))};
+        int32_t* mx[2] = {(int32_t*)malloc(kSfBlock * sizeof(int32_t)), (int32_t*)malloc(kSfBlock * sizeof(int32_t))};
+        for (int t = 0; t < kSfBlock; ++t) {
+            mx[0][t] = mx[1][t] = -1;
+            for (size_t k = lo + t; k < hi; k += kSfBlock) {
+                if (surf_p[base + k] == c) {
+                    const int32_t v = d2_pred[base + k];
+                    sum[0][t] += sqrt((double)v), mx[0][t] = v > mx[0][t] ? v : mx[0][t];
+                }
+                if (surf_t[base + k] == c) {
+                    const int32_t v = d2_truth[base + k];
+                    sum[1][t] += sqrt((double)v), mx[1][t] = v > mx[1][t] ? v : mx[1][t];
+                }
+            }
+        }
+        for (int stride = kSfBlock / 2; stride > 0; stride >>= 1)
+            for (int t = 0; t < stride; ++t) sf_tree_step(sum[0], mx[0], t, stride), sf_tree_step(sum[1], mx[1], t, stride);
+        SfPartial p;
+        p.sum[0] = sum[0][0], p.sum[1] = sum[1][0], p.max_d2[0] = mx[0][0], p.max_d2[1] = mx[1][0], p.pad[0] = p.pad[1] = 0;
+        partial[b] = p;
+        free(sum[0]), free(sum[1]), free(mx[0]), free(mx[1]);
+    }
+    for (size_t pair = 0; pair < pairs; ++pair) {
+        const int32_t* cnt = counts + pair * 2;
+        SfState st;
+        memset(&st, 0, sizeof(st));
+        st.max_d2 = -1;
+        double s0 = 0.0, s1 = 0.0;
+        int32_t m0 = -1, m1 = -1;
+        if (sf_scored(cnt)) {
+            for (int s = 0; s < slabs; ++s) {
+                const SfPartial p = partial[pair * slabs + s];
+                s0 += p.sum[0], s1 += p.sum[1];
+                m0 = p.max_d2[0] > m0 ? p.max_d2[0] : m0, m1 = p.max_d2[1] > m1 ? p.max_d2[1] : m1;
+            }
+            const u64 m = (u64)cnt[0] + (u64)cnt[1];
+            st.max_d2 = m0 > m1 ? m0 : m1;
+            st.remaining[0] = (uint32_t)sf_rank_lo(m), st.remaining[1] = (uint32_t)sf_rank_hi(m);
+        }
+        state[pair] = st;
+        int64_t* o = stats + pair * 6;
+        o[0] = cnt[0], o[1] = cnt[1], o[2] = m0, o[3] = m1, o[4] = o[5] = -1;
+        sums[pair * 2] = s0, sums[pair * 2 + 1] = s1;
+    }
+
+    // ---- pass 5: per digit a histogram "workgroup" per (sample, class, slab), then a thread per pair and rank
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (size_t b = 0; b < pairs * slabs; ++b) {
+            const int slab = (int)(b % slabs);
+            const size_t pair = b / slabs, i = pair / C, base = i * hw;
+            const int c = (int)(pair - i * C);
+            const SfState st = state[pair];
+            if (sf_pass_skipped(st.max_d2, shift)) continue;
+            unsigned int* bins = (unsigned int*)calloc(2 * 256, sizeof(unsigned int));
+            const size_t lo = slab * len, hi = lo + len < hw ? lo + len : hw;
+            for (size_t k = lo; k < hi; ++k)
+                for (int dir = 0; dir < 2; ++dir) {
+                    if ((dir ? surf_t : surf_p)[base + k] != c) continue;
+                    const uint32_t v = (uint32_t)(dir ? d2_truth : d2_pred)[base + k];
+                    if (sf_in_prefix(v, st.prefix[0], shift)) bins[v >> shift & 255u] += 1;
+                    if (sf_in_prefix(v, st.prefix[1], shift)) bins[256 + (v >> shift & 255u)] += 1;
+                }
+            for (int k = 0; k < 512; ++k) hist[pair * 512 + k] += bins[k];
+            free(bins);
+        }
+        for (size_t id = 0; id < 2 * pairs; ++id) {
+            const size_t pair = id >> 1;
+            const int r = (int)(id & 1);
+            const int32_t max_d2 = state[pair].max_d2;
+            if (max_d2 < 0) continue;
+            if (!sf_pass_skipped(max_d2, shift)) {
+                uint32_t* h = hist + (pair * 2 + r) * 256;
+                uint32_t rem = state[pair].remaining[r];
+                const int dgt = sf_pick_digit(h, &rem);
+                state[pair].prefix[r] |= (uint32_t)dgt << shift;
+                state[pair].remaining[r] = rem;
+                for (int k = 0; k < 256; ++k) h[k] = 0;
+            }
+            if (shift == 0) stats[pair * 6 + 4 + r] = state[pair].prefix[r];
+        }
+    }
+
+    FILE* g = fopen(argv[2], "wb");
+    if (!g) return 1;
+    if (fwrite(stats, 8, pairs * 6, g) != pairs * 6 || fwrite(sums, 8, pairs * 2, g) != pairs * 2 ||
+        fwrite(d2_pred, 4, pix, g) != pix || fwrite(d2_truth, 4, pix, g) != pix)
+        return 1;
+    fclose(g);
+    free(truth), free(pred), free(ws), free(stats), free(sums);
+    return 0;
+}
