@@ -136,6 +136,14 @@ class TtaDesc(C.Structure):
                 ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int), ('cm', c_void_p), ('pred_out', c_void_p)]
 
 
+CALIB_MAX_BINS, CALIB_MAX_TEMPS = 48, 8
+
+
+class CalibDesc(C.Structure):
+    _fields_ = TtaDesc._fields_ + [('nb', c_int), ('edges', c_void_p), ('nt', c_int), ('temps', c_void_p), ('hist', c_void_p),
+                                   ('scores', c_void_p)]
+
+
 class ClassMixDesc(C.Structure):
     _fields_ = [('logits', c_void_p), ('valid', c_void_p), ('keys', c_void_p),
                 ('n', c_int), ('c', c_int), ('h', c_int), ('w', c_int), ('H', c_int), ('W', c_int), ('align_corners', c_int),
@@ -333,6 +341,7 @@ PROTOTYPES = {
                             c_void_p]),
     'cms_tta_resize': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'cms_tta_vote': (c_int, [_P(TtaDesc), c_void_p]),
+    'cms_calib_accumulate': (c_int, [_P(CalibDesc), c_void_p]),
     'cms_classmix_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cms_classmix': (c_int, [_P(ClassMixDesc), c_void_p]),
     'cms_cps_labels': (c_int, [_P(CpsDesc), c_void_p]),

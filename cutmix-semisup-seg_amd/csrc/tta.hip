@@ -12,12 +12,6 @@ namespace cms {
 
 constexpr int kTtaBlock = 256;
 
-__device__ __forceinline__ int tta_label(const void* labels, int label_dtype, size_t pix) {
-    if (label_dtype == CMS_LABEL_U8) return (int)((const uint8_t*)labels)[pix];
-    const int64_t v = ((const int64_t*)labels)[pix];
-    return (v < 0 || v > 0x7fffffff) ? -1 : (int)v;
-}
-
 // MODE 0: one view of the output's size (no interpolation), 1: one view, resampled, 2: the vote over k >= 2 views
 template <int MODE>
 __global__ __launch_bounds__(kTtaBlock) void tta_vote_kernel(const TtaViews v, int k, const void* labels, int label_dtype,

@@ -77,6 +77,13 @@ CMS_HD Tap tta_tap_x(int x, float sx, int w, bool align_corners, bool flip) {
     return t;
 }
 
+// the label of pixel `pix` as an int; an int64 label outside [0, 2^31) is -1 (never a class)
+CMS_HD int tta_label(const void* labels, int label_dtype, size_t pix) {
+    if (label_dtype == CMS_LABEL_U8) return (int)((const uint8_t*)labels)[pix];
+    const int64_t v = ((const int64_t*)labels)[pix];
+    return (v < 0 || v > 0x7fffffff) ? -1 : (int)v;
+}
+
 // torch.argmax's order on two candidates: larger wins, the first index keeps a tie, NaN counts as maximal (csrc/eval.hip)
 CMS_HD bool tta_beats(float v, float best) { return v > best || (v != v && best == best); }
 
@@ -110,8 +117,10 @@ CMS_HD int tta_single_pixel(const TtaViews& v, int n, int C, int y, int x, bool 
 // One output pixel of the vote over k >= 2 views -> its prediction. `score(c)` is a float lvalue per class (a column of LDS in the
 // kernel, an array on the host); views outermost, so a view's taps and softmax statistics live in registers and
 // score_c = ((p_0c + p_1c) + p_2c) + ... comes out in view order.
-template <class S>
-CMS_HD int tta_vote_pixel(const TtaViews& v, int k, int n, int C, int y, int x, bool align_corners, S score) {
+// `xf(logit)` is applied to every gathered logit before the softmax: the identity in the vote, the temperature scaling of
+// csrc/calib_math.hpp.
+template <class S, class X>
+CMS_HD int tta_vote_pixel_x(const TtaViews& v, int k, int n, int C, int y, int x, bool align_corners, S score, X xf) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -121,7 +130,7 @@ CMS_HD int tta_vote_pixel(const TtaViews& v, int k, int n, int C, int y, int x, 
         const float* base = v.logits[i] + (size_t)n * C * plane;
         const Tap ty = bilin_tap(y, v.sy[i], h, align_corners);
         const Tap tx = tta_tap_x(x, v.sx[i], w, align_corners, v.flip[i] != 0);
-        auto logit = [&](int c) { return bilin_gather(base + (size_t)c * plane, w, ty, tx); };
+        auto logit = [&](int c) { return xf(bilin_gather(base + (size_t)c * plane, w, ty, tx)); };
         SoftmaxRegs<0> s;
         softmax_regs<0>(logit, C, s);
         if (i == 0) {
@@ -143,6 +152,11 @@ CMS_HD int tta_vote_pixel(const TtaViews& v, int k, int n, int C, int y, int x, 
         }
     }
     return best;
+}
+
+template <class S>
+CMS_HD int tta_vote_pixel(const TtaViews& v, int k, int n, int C, int y, int x, bool align_corners, S score) {
+    return tta_vote_pixel_x(v, k, n, C, y, x, align_corners, score, [](float l) { return l; });
 }
 
 // The align_corners=False tap of output index `dst` with its position worked out exactly: src = (dst + 0.5) * in / out - 0.5

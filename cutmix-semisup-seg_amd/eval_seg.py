@@ -2,7 +2,8 @@
 Score a trained model: `python eval_seg.py MODEL.pth --dataset pascal_aug [--subset val|test] [--scales 0.5,0.75,1,1.25,1.5,1.75]
 [--flip] [--batch_size 10] [--n_val -1] [--val_seed 131] [--split_path FILE] [--bin_fill_holes] [--save_preds DIR]
 [--compute_dtype bf16|fp32] [--boundary_width 3,5,0.02] [--crf [--crf_iters 5] [--crf_radius 5] [--crf_dilation 3] [--crf_bi_w 4]
-[--crf_bi_xy 15] [--crf_bi_rgb 13] [--crf_pos_w 3] [--crf_pos_xy 3]] [--surface_dist]`.
+[--crf_bi_xy 15] [--crf_bi_rgb 13] [--crf_pos_w 3] [--crf_pos_xy 3]] [--surface_dist] [--calibration [--calib_bins 15]
+[--calib_thresh 0.5,0.9,0.95,0.97,0.99] [--calib_temperature 1] [--calib_nll_temps LIST] [--calib_out FILE.json]]`.
 
 The reference has no such program: it evaluates inside a training run only, at one scale without a flip. MODEL.pth is the whole-module
 pickle a trainer writes with `--save_model` (or the reference's own). The data set is opened exactly as the trainers open it
@@ -32,7 +33,18 @@ number is the mean over those images, `-` when there is none, and the headline t
 in which only one of the two holds the class are counted as one-sided. The prediction scored is the one `--boundary_width` scores.
 Without the option every printed line and every saved file is what it was.
 
-What keeps the program from starting is said before the GPU is touched: a model file that does not load, a data set that is not
+`--calibration` (off by default) scores the confidence the trainers compare with `--conf_thresh` (evaluation.EvaluatorCalibration,
+csrc/calib.hip: one launch per batch in the place of the vote launch), after every line above: `VAL ECE=...` with its per-class line
+`-- ECE ...` (by predicted class, `-` for a class that is never predicted), `-- MCE=... NLL=... Brier=...`, one `-- bin [lo,hi) n=...
+acc=... conf=...` row per equal-width bin, then per threshold `VAL pseudo@<t> pass=...% acc=...%` with `-- pseudo@<t> acc ...` (by
+predicted class) and `-- pseudo@<t> recall ...` (by true class: the share of its pixels that receive a correct pseudo-label), and with
+`--calib_nll_temps` the line `-- NLL@T ...; lowest at T=...`. `--calib_temperature T` divides the logits by T before the softmax; with
+two or more views the vote itself is then taken at T and one line says so. The tables score the network's own distribution:
+`--bin_fill_holes` does not touch them, and `--crf` is refused beside them. With T = 1 the mIoU lines are bit for bit what they are
+without the option. `--calib_out FILE.json` writes the integer tables and every derived score.
+
+What keeps the program from starting is said before the GPU is touched: a bad `--calib_*` value or one without `--calibration`,
+`--calibration` with `--crf`, a model file that does not load, a data set that is not
 configured, `--subset test` without a held-out set, `--bin_fill_holes` on more than two classes, a model of another class count, bad
 `--scales`, a bad `--boundary_width`, a bad `--crf_*` value or one without `--crf`, more than one process.
 """
@@ -81,12 +93,65 @@ def crf_spec(crf, **options):
         raise EvalNotRun(str(e))
 
 
-def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes, boundary_width=None):
-    """Everything that can refuse, on the host -> (tta, net on the CPU, ds_dict, ndx)."""
+CALIB_OPTIONS = ('calib_bins', 'calib_thresh', 'calib_temperature', 'calib_nll_temps', 'calib_out')
+
+
+def calibration_spec(calibration, calib_bins=None, calib_thresh=None, calib_temperature=None, calib_nll_temps=None, calib_out=None,
+                     crf=None):
+    """--calibration and the --calib_* values as they were typed (None where not given) -> dict(n_bins, thresholds, labels,
+    temperature, nll_temperatures, out) for evaluation.EvaluatorCalibration, or None without --calibration. No GPU."""
+    given = dict(calib_bins=calib_bins, calib_thresh=calib_thresh, calib_temperature=calib_temperature,
+                 calib_nll_temps=calib_nll_temps, calib_out=calib_out)
+    if not calibration:
+        for k, v in given.items():
+            if v is not None:
+                raise EvalNotRun('--{} is given without --calibration'.format(k))
+        return None
+    if crf:
+        raise EvalNotRun('--calibration scores the network\'s own softmax confidence; --crf replaces it with another distribution: '
+                         'give one of the two')
+    from . import evaluation
+    try:
+        n_bins = int(str(calib_bins).strip()) if calib_bins is not None else 15
+    except ValueError:
+        raise EvalNotRun('--calib_bins {!r}: an integer in 1..48 is needed'.format(calib_bins))
+    thresh_text = '0.5,0.9,0.95,0.97,0.99' if calib_thresh is None else str(calib_thresh)
+    try:
+        thresholds = evaluation.parse_calibration_thresholds(thresh_text)
+    except ValueError as e:
+        raise EvalNotRun('--calib_thresh: {}'.format(e))
+    try:
+        temperature = evaluation.parse_calibration_temperatures('1' if calib_temperature is None else calib_temperature)
+        if len(temperature) != 1:
+            raise ValueError('one number is needed, got {!r}'.format(calib_temperature))
+    except ValueError as e:
+        raise EvalNotRun('--calib_temperature: {}'.format(e))
+    try:
+        more = evaluation.parse_calibration_temperatures('' if calib_nll_temps is None else calib_nll_temps)
+        if len(more) > evaluation.CALIB_MAX_TEMPS - 1:
+            raise ValueError('{} temperatures, at most {} are taken'.format(len(more), evaluation.CALIB_MAX_TEMPS - 1))
+    except ValueError as e:
+        raise EvalNotRun('--calib_nll_temps: {}'.format(e))
+    try:
+        evaluation.calibration_edges(n_bins, thresholds)
+    except ValueError as e:
+        raise EvalNotRun('--calib_bins / --calib_thresh: {}'.format(e))
+    labels = [p.strip() for p in thresh_text.split(',')] if thresholds else []
+    return dict(n_bins=n_bins, thresholds=thresholds, labels=labels, temperature=temperature[0], nll_temperatures=more, out=calib_out)
+
+
+def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes, boundary_width=None,
+            calibration=None, crf=None):
+    """Everything that can refuse, on the host -> (tta, net on the CPU, ds_dict, ndx). `calibration`: calibration_spec's dict, or
+    (flag, dict of the --calib_* values as typed), checked here."""
     from . import tta as tta_mod
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise EvalNotRun('eval_seg runs on one GPU: start one process (WORLD_SIZE={})'.format(os.environ['WORLD_SIZE']))
     boundary_spec(boundary_width)
+    if isinstance(calibration, tuple):
+        calibration_spec(calibration[0], crf=crf, **calibration[1])
+    elif calibration is not None and crf:
+        calibration_spec(True, crf=crf)
     try:
         tta = tta_mod.TTA(tta_mod.parse_scales(scales), flip)
     except ValueError as e:
@@ -123,13 +188,19 @@ def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_pa
 
 
 def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_size=10, n_val=-1, val_seed=131, split_path=None,
-             bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None, crf=None, surface_dist=False):
+             bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None, crf=None, surface_dist=False,
+             calibration=None):
     """-> the per-class IoU (numpy); prints the trainers' lines, with `crf` (crf.CRFParams) what the refinement changed, with
-    `boundary_width` the contour scores after them, and with `surface_dist` the surface distances after those."""
+    `boundary_width` the contour scores after them, with `surface_dist` the surface distances after those, and with `calibration`
+    (calibration_spec's dict; True for the defaults) the calibration report after everything else."""
     if crf is not None and not hasattr(crf, 'as_dict'):
         raise EvalNotRun('crf must be a crf.CRFParams, got {!r}'.format(crf))
+    if calibration is True:
+        calibration = calibration_spec(True, crf=crf)
+    elif calibration is not None and not isinstance(calibration, dict):
+        raise EvalNotRun('calibration must be True or the dict of calibration_spec, got {!r}'.format(calibration))
     tta, net, ds_dict, ndx = prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes,
-                                     boundary_width)
+                                     boundary_width, calibration, crf)
     spec = boundary_spec(boundary_width)
 
     import types
@@ -162,6 +233,10 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
     sf_eval = None
     if surface_dist:
         sf_eval = more['surface'] = evaluation.EvaluatorSurface(run.n_classes)
+    cal_eval = None
+    if calibration is not None:
+        cal_eval = more['calibration'] = evaluation.EvaluatorCalibration(
+            run.n_classes, calibration['n_bins'], calibration['thresholds'], calibration['temperature'], calibration['nll_temperatures'])
     crf_stats = run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta, **more)
     iou = iou_eval.score()
     prefix = 'VAL' if subset == 'val' else 'TEST'
@@ -182,7 +257,39 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
         scored, one_sided = sf_eval.pairs()
         print('-- surface pairs {} (one-sided {})'.format(', '.join(str(int(x)) for x in scored),
                                                           ', '.join(str(int(x)) for x in one_sided)))
+    if cal_eval is not None:
+        for line in calibration_lines(prefix, cal_eval, calibration['labels'], len(tta.views())):
+            print(line)
+        if calibration.get('out'):
+            import json
+            with open(calibration['out'], 'w') as f:
+                json.dump(cal_eval.as_dict(), f)
     return iou
+
+
+def calibration_lines(prefix, cal, labels, n_views=1):
+    """The printed calibration report of an evaluation.EvaluatorCalibration; `labels`: the thresholds as they were typed."""
+    def pct(x, digits=3):
+        return '-' if x != x else '{:.{}%}'.format(x, digits)
+    lines = []
+    if cal.temperature != 1.0:
+        lines.append('-- calibration at T={:g}{}'.format(
+            cal.temperature, ': the vote over the {} views is taken at T'.format(n_views) if n_views >= 2 else ''))
+    lines.append('{} ECE={}'.format(prefix, pct(cal.ece())))
+    lines.append('-- ECE {}'.format(', '.join(pct(x) for x in cal.ece_per_class())))
+    nll = cal.nll()
+    lines.append('-- MCE={} NLL={:.4f} Brier={:.4f}'.format(pct(cal.mce()), nll[0], cal.brier()))
+    for row in cal.reliability():
+        lines.append('-- bin [{:.3f},{:.3f}) n={} acc={} conf={}'.format(row['lo'], row['hi'], row['n'], pct(row['acc']), pct(row['conf'])))
+    for label, rep in zip(labels, cal.threshold_report()):
+        lines.append('{} pseudo@{} pass={} acc={}'.format(prefix, label, pct(rep['pass_rate']), pct(rep['acc'])))
+        lines.append('-- pseudo@{} acc {}'.format(label, ', '.join(pct(x) for x in rep['acc_per_class'])))
+        lines.append('-- pseudo@{} recall {}'.format(label, ', '.join(pct(x) for x in rep['recall_per_class'])))
+    if len(cal.temperatures) > 1:
+        best = min(range(len(nll)), key=lambda i: (nll[i] != nll[i], nll[i]))
+        lines.append('-- NLL@T {}; lowest at T={:g}'.format(
+            ', '.join('{:g}={:.4f}'.format(t, v) for t, v in zip(cal.temperatures, nll)), cal.temperatures[best]))
+    return lines
 
 
 @click.command()
@@ -209,14 +316,22 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
 @click.option('--crf_pos_w', type=str, default=None, help='3')
 @click.option('--crf_pos_xy', type=str, default=None, help='3')
 @click.option('--surface_dist', is_flag=True, default=False)
+@click.option('--calibration', is_flag=True, default=False)
+@click.option('--calib_bins', type=str, default=None, help='15')
+@click.option('--calib_thresh', type=str, default=None, help='0.5,0.9,0.95,0.97,0.99')
+@click.option('--calib_temperature', type=str, default=None, help='1')
+@click.option('--calib_nll_temps', type=str, default=None, help='up to seven more temperatures for the NLL line')
+@click.option('--calib_out', type=click.Path(dir_okay=False), default=None)
 def experiment(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-               compute_dtype, boundary_width, crf, surface_dist, **crf_options):
+               compute_dtype, boundary_width, crf, surface_dist, calibration, **options):
     if batch_size < 1:
         raise EvalNotRun('--batch_size must be at least 1')
+    calib_options = {k: options.pop(k) for k in CALIB_OPTIONS}
     boundary_spec(boundary_width)                  # a malformed one is said before the model file is even opened
-    params = crf_spec(crf, **crf_options)          # ... and so is a malformed --crf_* value, or one without --crf
+    calib = calibration_spec(calibration, crf=crf, **calib_options)      # ... and a --calib_* value, or --calibration beside --crf
+    params = crf_spec(crf, **options)              # ... and so is a malformed --crf_* value, or one without --crf
     evaluate(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-             compute_dtype, boundary_width, params, surface_dist)
+             compute_dtype, boundary_width, params, surface_dist, calib)
 
 
 if __name__ == '__main__':

@@ -275,6 +275,10 @@ class EvaluatorIoU(object):
         ops.tta_vote(logits_list, flips, self.num_classes, out_size, labels=truth, ignore_index=ignore_value,
                      align_corners=align_corners, cm=self._cm())
 
+    def add_confusion(self, cm):
+        """Add a batch's int64 (C,C) confusion matrix that is already on the device (EvaluatorCalibration.sample_views')."""
+        self._cm().add_(cm)
+
     # reference attributes (float arrays, evaluation.py:49-51)
     @property
     def cm(self):
@@ -297,3 +301,235 @@ class EvaluatorIoU(object):
 
     def score(self):
         return self.intersection.astype(float) / np.maximum(self.union.astype(float), 1.0)
+
+
+# ------------------------------------------------------------------------------------------------------------------ calibration
+CALIB_MAX_BINS, CALIB_MAX_TEMPS = 48, 8
+CALIB_CONF_SCALE, CALIB_BRIER_SCALE, CALIB_NLL_SCALE = 2.0 ** 24, 2.0 ** 24, 2.0 ** 20
+CALIB_DEFAULT_THRESHOLDS = (0.5, 0.9, 0.95, 0.97, 0.99)
+
+
+def _numbers(text, what, example):
+    parts = [p.strip() for p in str(text).split(',')]
+    if not parts or any(p == '' for p in parts):
+        raise ValueError('{} {!r}: expected a comma-separated list of numbers such as {}'.format(what, text, example))
+    try:
+        return tuple(float(p) for p in parts)
+    except ValueError:
+        raise ValueError('{} {!r}: expected a comma-separated list of numbers such as {}'.format(what, text, example))
+
+
+def parse_calibration_thresholds(text):
+    """'0.5,0.9,0.97' -> (0.5, 0.9, 0.97); '' -> (). ValueError for anything that is not a list of numbers in (0, 1)."""
+    if str(text).strip() == '':
+        return ()
+    return _checked_thresholds(_numbers(text, 'thresholds', '0.5,0.9,0.97'))
+
+
+def parse_calibration_temperatures(text):
+    """'0.5,2' -> (0.5, 2.0); '' -> (). ValueError for anything that is not a list of finite numbers > 0."""
+    if str(text).strip() == '':
+        return ()
+    return _checked_temperatures(_numbers(text, 'temperatures', '0.5,0.75,1.5,2'))
+
+
+def _checked_thresholds(thresholds):
+    out = []
+    for t in thresholds:
+        t = float(t)
+        if not 0.0 < t < 1.0 or not 0.0 < float(np.float32(t)) < 1.0:
+            raise ValueError('thresholds: every threshold must lie inside (0, 1) as an fp32 number, got {!r}'.format(t))
+        if float(np.float32(t)) in [float(np.float32(u)) for u in out]:
+            raise ValueError('thresholds: {!r} is repeated'.format(t))
+        out.append(t)
+    return tuple(out)
+
+
+def _checked_temperatures(temps):
+    out = []
+    for t in temps:
+        t = float(t)
+        with np.errstate(over='ignore'):
+            t32 = float(np.float32(t))
+        if not (t > 0.0) or math.isinf(t) or not (0.0 < t32 < float('inf')):
+            raise ValueError('temperatures: every temperature must be a finite number > 0, got {!r}'.format(t))
+        out.append(t)
+    return tuple(out)
+
+
+def calibration_edges(n_bins, thresholds):
+    """The bin partition of a calibration report -> (edges, eq_bin, thr_bin): `edges` the fp32 interior edges, the sorted union of
+    the equal-width edges i / n_bins and the thresholds (built in fp64, cast to fp32, duplicates merged) -- a confidence falls into
+    bin #{j: edges[j] <= conf}; eq_bin[b] the equal-width bin that sub-bin b is a part of; thr_bin[i] the first sub-bin of the
+    pixels with conf >= thresholds[i]. ValueError when n_bins is outside 1..48 or the union makes more than 48 bins."""
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 1 <= int(n_bins) <= CALIB_MAX_BINS:
+        raise ValueError('bins: an integer in 1..{} is needed, got {!r}'.format(CALIB_MAX_BINS, n_bins))
+    n_bins = int(n_bins)
+    thresholds = _checked_thresholds(thresholds)
+    eq = (np.arange(1, n_bins, dtype=np.float64) / n_bins).astype(np.float32)
+    thr = np.asarray(thresholds, dtype=np.float64).astype(np.float32)
+    edges = np.unique(np.concatenate([eq, thr]))
+    if edges.size + 1 > CALIB_MAX_BINS:
+        raise ValueError('{} bins and {} thresholds make {} bins; the kernel takes at most {}'.format(
+            n_bins, len(thresholds), edges.size + 1, CALIB_MAX_BINS))
+    lower = np.concatenate([np.zeros(1, dtype=np.float32), edges])           # the lower edge of every sub-bin
+    eq_bin = np.searchsorted(eq, lower, side='right').astype(np.int64)       # #{i: eq_i <= lower}
+    thr_bin = (np.searchsorted(edges, thr, side='left') + 1).astype(np.int64)
+    return edges, eq_bin, thr_bin
+
+
+class EvaluatorCalibration(object):
+    """Calibration and pseudo-label quality of a model's confidence (this project's own definition; DESIGN 8, include/cutmixseg.h).
+    `sample_views` is one launch of csrc/calib.hip per batch, which takes the place of the vote launch and ADDS exact integers into
+    device-side tables: per (predicted class, confidence bin) the pixels, the correct pixels and the fixed-point confidence sum, plus
+    the fixed-point Brier and NLL sums and a confusion matrix. They come to the host once, when a score is asked for, and every score
+    is derived from them in fp64: the expected and maximum calibration error over `n_bins` equal-width bins (Naeini et al. 2015, Guo et
+    al. 2017), NLL, Brier, the reliability table, and per threshold what a trainer's `--conf_thresh` would let through. `temperature`
+    divides the logits before the softmax; `nll_temperatures` are up to seven more for the NLL alone."""
+
+    def __init__(self, n_classes, n_bins=15, thresholds=CALIB_DEFAULT_THRESHOLDS, temperature=1.0, nll_temperatures=()):
+        if not 1 <= int(n_classes) <= 64:
+            raise ValueError('EvaluatorCalibration: 1 <= n_classes <= 64, got {}'.format(n_classes))
+        self.num_classes = int(n_classes)
+        self.edges, self.eq_bin, self.thr_bin = calibration_edges(n_bins, thresholds)
+        self.n_bins = int(n_bins)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        self.temperatures = _checked_temperatures((temperature,) + tuple(nll_temperatures))
+        if len(self.temperatures) > CALIB_MAX_TEMPS:
+            raise ValueError('temperatures: {} given, at most {} beside the histogram\'s'.format(
+                len(self.temperatures) - 1, CALIB_MAX_TEMPS - 1))
+        self.nb = int(self.edges.size) + 1
+        self._dev = None
+        self._host = None
+
+    @property
+    def temperature(self):
+        return self.temperatures[0]
+
+    # ---- the tables
+    def _tables(self):
+        if self._dev is None:
+            dev, c = _device(), self.num_classes
+            self._dev = (torch.zeros((c, self.nb, 3), dtype=torch.int64, device=dev),
+                         torch.zeros((2 + len(self.temperatures),), dtype=torch.int64, device=dev),
+                         torch.zeros((c, c), dtype=torch.int64, device=dev))
+        return self._dev
+
+    def sample_views(self, logits_list, flips, truth, out_size, ignore_value=255, align_corners=True, want_pred=False):
+        """One batch: the views' low-resolution logits as ops.tta_vote takes them -> (the batch's own int64 (C,C) confusion matrix
+        on the device, the uint8 prediction or None unless wanted), what ops.tta_vote returns."""
+        hist, scores, own = self._tables()
+        batch_cm, pred = ops.calibration_accumulate(logits_list, flips, self.num_classes, out_size, truth, self.edges,
+                                                    np.asarray(self.temperatures, dtype=np.float32), hist, scores,
+                                                    ignore_index=ignore_value, align_corners=align_corners, want_pred=want_pred)
+        own += batch_cm                           # an integer add on the device: no host synchronisation
+        self._host = None
+        return batch_cm, pred
+
+    def load_tables(self, hist, scores, cm):
+        """Set the integer tables from host arrays (a saved `as_dict()`, a test): no GPU is needed for the derived scores."""
+        c = self.num_classes
+        hist, scores, cm = (np.asarray(a, dtype=np.int64) for a in (hist, scores, cm))
+        if hist.shape != (c, self.nb, 3) or scores.shape != (2 + len(self.temperatures),) or cm.shape != (c, c):
+            raise ValueError('load_tables: shapes {} / {} / {} expected'.format((c, self.nb, 3), (2 + len(self.temperatures),), (c, c)))
+        self._host = (hist.copy(), scores.copy(), cm.copy())
+        self._dev = None
+
+    def tables(self):
+        """-> (hist (C, nb, 3), scores (2 + nt,), cm (C, C)) int64 numpy"""
+        if self._host is None:
+            if self._dev is None:
+                c = self.num_classes
+                self._host = (np.zeros((c, self.nb, 3), dtype=np.int64), np.zeros(2 + len(self.temperatures), dtype=np.int64),
+                              np.zeros((c, c), dtype=np.int64))
+            else:
+                self._host = tuple(t.cpu().numpy() for t in self._dev)
+        return self._host
+
+    # ---- derived scores, fp64 from the integers
+    def _merged(self):
+        """the sub-bins merged into the equal-width bins -> (n, correct, conf_sum), each (C, n_bins) float64"""
+        hist = self.tables()[0]
+        out = np.zeros((3, self.num_classes, self.n_bins))
+        for b in range(self.nb):
+            out[:, :, self.eq_bin[b]] += hist[:, b, :].T
+        out[2] /= CALIB_CONF_SCALE
+        return out
+
+    @staticmethod
+    def _gaps(n, correct, conf_sum):
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(n > 0, np.abs(correct / n - conf_sum / n), 0.0)
+
+    def scored_pixels(self):
+        return int(self.tables()[1][0])
+
+    def ece(self):
+        """sum over the equal-width bins of (n_b / N) |acc_b - conf_b|; NaN when no pixel was scored"""
+        n, correct, conf = self._merged().sum(axis=1)
+        total = n.sum()
+        return float((n * self._gaps(n, correct, conf)).sum() / total) if total > 0 else float('nan')
+
+    def ece_per_class(self):
+        """-> (C,) the same over the pixels PREDICTED as each class; NaN for a class with none"""
+        n, correct, conf = self._merged()
+        total = n.sum(axis=1)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(total > 0, (n * self._gaps(n, correct, conf)).sum(axis=1) / total, np.nan)
+
+    def mce(self):
+        n, correct, conf = self._merged().sum(axis=1)
+        return float(self._gaps(n, correct, conf)[n > 0].max()) if (n > 0).any() else float('nan')
+
+    def nll(self):
+        """-> (nt,) the mean negative log-likelihood per temperature, temperatures[0] first"""
+        scores = self.tables()[1]
+        total = float(scores[0])
+        return scores[2:].astype(np.float64) / CALIB_NLL_SCALE / total if total > 0 else np.full(len(self.temperatures), np.nan)
+
+    def brier(self):
+        scores = self.tables()[1]
+        return float(scores[1]) / CALIB_BRIER_SCALE / float(scores[0]) if scores[0] > 0 else float('nan')
+
+    def reliability(self):
+        """-> [dict(lo, hi, n, acc, conf)] per equal-width bin; acc / conf NaN for an empty bin"""
+        n, correct, conf = self._merged().sum(axis=1)
+        rows = []
+        for b in range(self.n_bins):
+            nb_ = int(n[b])
+            rows.append(dict(lo=b / self.n_bins, hi=(b + 1) / self.n_bins, n=nb_, acc=correct[b] / nb_ if nb_ else float('nan'),
+                             conf=conf[b] / nb_ if nb_ else float('nan')))
+        return rows
+
+    def threshold_report(self):
+        """-> per threshold dict(threshold, pass_rate, acc, acc_per_class (by predicted class), recall_per_class (by TRUE class:
+        the share of its pixels that receive a correct pseudo-label)); NaN where there is no pixel"""
+        hist, scores, cm = self.tables()
+        total, truth = float(scores[0]), cm.sum(axis=1).astype(np.float64)
+        out = []
+        for t, s in zip(self.thresholds, self.thr_bin):
+            n_c = hist[:, s:, 0].sum(axis=1).astype(np.float64)               # suffix sums over the bins at and above the threshold
+            ok_c = hist[:, s:, 1].sum(axis=1).astype(np.float64)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                out.append(dict(threshold=t, pass_rate=n_c.sum() / total if total > 0 else float('nan'),
+                                acc=ok_c.sum() / n_c.sum() if n_c.sum() > 0 else float('nan'),
+                                acc_per_class=np.where(n_c > 0, ok_c / n_c, np.nan),
+                                recall_per_class=np.where(truth > 0, ok_c / truth, np.nan)))
+        return out
+
+    def as_dict(self):
+        """Everything, JSON-serialisable: the settings, the integer tables and the derived scores (NaN as None)."""
+        hist, scores, cm = self.tables()
+
+        def clean(v):
+            if isinstance(v, np.ndarray):
+                return [clean(x) for x in v.tolist()]
+            if isinstance(v, (list, tuple)):
+                return [clean(x) for x in v]
+            if isinstance(v, dict):
+                return {k: clean(x) for k, x in v.items()}
+            return None if isinstance(v, float) and v != v else v
+        return clean(dict(n_classes=self.num_classes, n_bins=self.n_bins, thresholds=list(self.thresholds),
+                          temperatures=list(self.temperatures), edges=[float(e) for e in self.edges], hist=hist, scores=scores, cm=cm,
+                          scored_pixels=self.scored_pixels(), ece=self.ece(), ece_per_class=self.ece_per_class(), mce=self.mce(),
+                          nll=self.nll(), brier=self.brier(), reliability=self.reliability(), thresholds_report=self.threshold_report()))

@@ -1171,6 +1171,88 @@ def tta_vote(logits_list, flips, num_classes, out_size, labels=None, ignore_inde
     return cm, pred
 
 
+def calibration_accumulate(logits_list, flips, num_classes, out_size, labels, edges, temps, hist, scores, ignore_index=255,
+                           align_corners=True, cm=None, want_pred=False, pred=None):
+    """
+    tta_vote with the confidence kept (csrc/calib.hip): one launch that ADDS, for every pixel with a valid label, into
+      hist    int64 (C, nb, 3) CUDA, keyed by predicted class and confidence bin: pixels, correct pixels, sum of rint(conf * 2^24)
+      scores  int64 (2 + nt,) CUDA: scored pixels, sum of rint(2^24 * squared error) at temps[0], per temperature sum of
+              rint(2^20 * nll)
+    `edges`: the nb - 1 strictly ascending interior bin edges in (0, 1) (a pixel is in bin #{j: edges[j] <= conf}, compared in fp32);
+    `temps`: 1 to 8 temperatures, temps[0] the histogram's (and, with two or more views, the vote's). Views, labels, cm and pred as
+    tta_vote's; labels are required. Returns (cm int64 (C,C) CUDA [accumulated into `cm` when given], pred | None). include/cutmixseg.h
+    states the definition.
+    """
+    logits_list = list(logits_list)
+    flips = [bool(f) for f in flips]
+    k = len(logits_list)
+    if k < 1 or k > _lib.TTA_MAX_VIEWS:
+        raise ValueError('calibration_accumulate: {} views, 1 to {} are built'.format(k, _lib.TTA_MAX_VIEWS))
+    if len(flips) != k:
+        raise ValueError('calibration_accumulate: {} views but {} flips'.format(k, len(flips)))
+    if any(not torch.is_tensor(t) or t.dim() != 4 for t in logits_list):
+        raise TypeError('calibration_accumulate: every view must be an (N,C,h,w) tensor')
+    num_classes = int(num_classes)
+    if num_classes < 1 or num_classes > 64:
+        raise ValueError('calibration_accumulate: 1 <= num_classes <= 64, got {}'.format(num_classes))
+    H, W = _size2(out_size, 'calibration_accumulate: out_size')
+    n = int(logits_list[0].shape[0])
+    for t in logits_list:
+        if int(t.shape[0]) != n or int(t.shape[1]) != num_classes or min(int(s) for s in t.shape) < 1:
+            raise ValueError('calibration_accumulate: a view of shape {} among views of {} samples and {} classes'.format(
+                tuple(t.shape), n, num_classes))
+    if n * H * W > 2 ** 31 - 1:
+        raise ValueError('calibration_accumulate: more than 2^31 - 1 output pixels')
+    if not torch.is_tensor(labels) or labels.dtype not in (torch.uint8, torch.int64):
+        raise TypeError('calibration_accumulate: labels must be a uint8 or int64 tensor')
+    if labels.dim() == 4:
+        labels = labels[:, 0]
+    if tuple(labels.shape) != (n, H, W):
+        raise ValueError('calibration_accumulate: labels of shape {}, {} expected'.format(tuple(labels.shape), (n, H, W)))
+    edges = np.ascontiguousarray(np.asarray(edges, dtype=np.float32).reshape(-1))
+    temps = np.ascontiguousarray(np.asarray(temps, dtype=np.float32).reshape(-1))
+    nb, nt = int(edges.size) + 1, int(temps.size)
+    if nb > _lib.CALIB_MAX_BINS:
+        raise ValueError('calibration_accumulate: {} bins, at most {} are built'.format(nb, _lib.CALIB_MAX_BINS))
+    if nb > 1 and not (np.all(edges > 0) and np.all(edges < 1) and np.all(np.diff(edges) > 0)):
+        raise ValueError('calibration_accumulate: edges must be strictly ascending inside (0, 1)')
+    if nt < 1 or nt > _lib.CALIB_MAX_TEMPS:
+        raise ValueError('calibration_accumulate: {} temperatures, 1 to {} are built'.format(nt, _lib.CALIB_MAX_TEMPS))
+    if not (np.all(np.isfinite(temps)) and np.all(temps > 0)):
+        raise ValueError('calibration_accumulate: every temperature must be finite and > 0, got {}'.format(temps.tolist()))
+    for name, t, shape in (('hist', hist, (num_classes, nb, 3)), ('scores', scores, (2 + nt,))):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError('calibration_accumulate: {} must be a contiguous int64 tensor of shape {}'.format(name, shape))
+    if cm is not None and (cm.dtype != torch.int64 or tuple(cm.shape) != (num_classes, num_classes) or not cm.is_contiguous()):
+        raise TypeError('calibration_accumulate: cm must be a contiguous int64 ({0},{0}) matrix'.format(num_classes))
+    if pred is not None:
+        if not torch.is_tensor(pred) or pred.dtype != torch.uint8 or not pred.is_contiguous() or tuple(pred.shape) != (n, H, W):
+            raise TypeError('calibration_accumulate: pred must be a contiguous uint8 tensor of shape {}'.format((n, H, W)))
+        want_pred = True
+    _need_cuda(labels, cm, pred, hist, scores, *logits_list)
+    views = [_f32c(t) for t in logits_list]         # kept alive until the launch is queued
+    dev = views[0].device
+    labels = labels.contiguous()
+    if cm is None:
+        cm = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=dev)
+    if want_pred and pred is None:
+        pred = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    d = _lib.CalibDesc()
+    for i, t in enumerate(views):
+        d.logits[i], d.h[i], d.w[i], d.flip[i] = t.data_ptr(), int(t.shape[2]), int(t.shape[3]), int(flips[i])
+    d.n, d.c, d.H, d.W, d.k, d.align_corners = n, num_classes, H, W, k, int(bool(align_corners))
+    d.labels = labels.data_ptr()
+    d.label_dtype = _lib.LABEL_I64 if labels.dtype == torch.int64 else _lib.LABEL_U8
+    d.ignore_index = -1 if ignore_index is None else int(ignore_index)
+    d.cm = cm.data_ptr()
+    d.pred_out = pred.data_ptr() if pred is not None else None
+    d.nb, d.edges = nb, (edges.ctypes.data if nb > 1 else None)      # host memory: read before the call returns
+    d.nt, d.temps = nt, temps.ctypes.data
+    d.hist, d.scores = hist.data_ptr(), scores.data_ptr()
+    check(fn['cms_calib_accumulate'](C.byref(d), _stream()), 'cms_calib_accumulate')
+    return cm, pred
+
+
 CRF_LIMITS = dict(radius=(1, 5), dilation=(1, 16), iters=(1, 32))
 CRF_WEIGHTS, CRF_THETAS = ('bi_w', 'pos_w'), ('bi_xy', 'bi_rgb', 'pos_xy')
 

@@ -367,7 +367,8 @@ class DatasetRun(object):
             print('sup_ndx={}'.format(self.sup_ndx.tolist()))
         return [iter(st) for st in self._streams]
 
-    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None, crf=None, surface=None):
+    def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None, crf=None, surface=None,
+                    calibration=None):
         """The reference's evaluation loop over `ndx` in index order: whole images, centred on a padded canvas per batch
         (stage_eval); padding carries label 255 and is ignored. With a `tta.TTA` every batch is evaluated as the vote over its
         views (eval_seg); `step` is read for `align_corners` only. With `boundary` (evaluation.EvaluatorBoundary) the batch's
@@ -376,12 +377,20 @@ class DatasetRun(object):
         the files in `preds_dir` stay the plain prediction. `surface` (evaluation.EvaluatorSurface) is given the map `boundary` is. With `crf` (crf.CRFParams) the batch's views -- one without `tta` -- are
         forwarded as above and the vote is refined against the canvas' bytes inside every image's rectangle (ops.crf_refine); the
         refined prediction is what `evaluator.sample` counts (its hole filling applies to it), what `boundary` and `surface` score and what
-        `preds_dir` receives, and the call returns the device-side int64 [pixels, labels the refinement changed] (else None)."""
+        `preds_dir` receives, and the call returns the device-side int64 [pixels, labels the refinement changed] (else None). With
+        `calibration` (evaluation.EvaluatorCalibration; not together with `crf`) the batch's views -- one without `tta` -- are forwarded
+        as above and the calibration launch takes the place of the vote launch: it scores the confidence of every labelled pixel and
+        gives the prediction and the confusion matrix that `evaluator`, `boundary`, `surface` and `preds_dir` then see."""
         import numpy as np
         import torch
         from . import ops
         from .datapipe import seg_data
         crf_total = None
+        if calibration is not None:
+            if crf is not None:
+                raise ValueError('staged_eval: calibration scores the network\'s own distribution, crf refines it into another one')
+            from . import tta as tta_mod
+            tta = tta if tta is not None else tta_mod.TTA((1.0,), False)
         if crf is not None:
             from . import crf as crf_mod, tta as tta_mod
             crf_views = tta if tta is not None else tta_mod.TTA((1.0,), False)
@@ -403,7 +412,8 @@ class DatasetRun(object):
                 elif tta is not None:
                     _, pred = tta.predict(eval_net, ev['image'], ev['canvas'], step.align_corners, labels=ev['labels'],
                                           ignore_index=255, want_pred=want_pred,
-                                          block_size=self.student_net.BLOCK_SIZE, evaluator=evaluator)
+                                          block_size=self.student_net.BLOCK_SIZE, evaluator=evaluator,
+                                          **({} if calibration is None else dict(calibration=calibration)))
                 else:
                     logits = eval_net.forward_lowres(ev['image'])
                     if evaluator is not None:

@@ -81,14 +81,29 @@ class TTA(object):
         return out
 
     def predict(self, net, image, canvas, align_corners, labels=None, ignore_index=255, cm=None, want_pred=False,
-                block_size=None, evaluator=None):
+                block_size=None, evaluator=None, calibration=None):
         """`net.forward_lowres` on every view of `image`, then one vote at `canvas` -> (cm | None, pred | None) as ops.tta_vote.
         With an `evaluator` (evaluation.EvaluatorIoU) the batch is counted into it (`sample_logits_tta`: its hole filling applies)
-        instead of into `cm`, and the prediction, when wanted, is the plain vote, as the trainers save the plain argmax."""
+        instead of into `cm`, and the prediction, when wanted, is the plain vote, as the trainers save the plain argmax. With a
+        `calibration` (evaluation.EvaluatorCalibration; labels are needed) its launch takes the place of the vote launch: it scores
+        the confidence and gives the plain prediction and the confusion matrix that `evaluator` (or `cm`) then receives."""
         from . import ops
         logits = self.forward_views(net, image, block_size)
         flips = [f for _, f in self.views()]
         n_classes = int(logits[0].shape[1])
+        if calibration is not None:
+            fill = getattr(evaluator, 'fill_holes', False)
+            batch_cm, pred = calibration.sample_views(logits, flips, labels, canvas, ignore_value=ignore_index,
+                                                      align_corners=align_corners, want_pred=want_pred or fill)
+            if evaluator is None:
+                if cm is not None:
+                    cm += batch_cm
+                return (batch_cm if cm is None else cm), (pred if want_pred else None)
+            if fill:
+                evaluator.sample(labels[:, 0] if labels.dim() == 4 else labels, pred, ignore_value=ignore_index)
+            else:
+                evaluator.add_confusion(batch_cm)
+            return None, (pred if want_pred else None)
         if evaluator is None:
             return ops.tta_vote(logits, flips, n_classes, canvas, labels=labels, ignore_index=ignore_index,
                                 align_corners=align_corners, cm=cm, want_pred=want_pred)

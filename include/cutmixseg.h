@@ -969,6 +969,48 @@ typedef struct {
 int cms_tta_resize(const void* src, void* dst, int n, int c, int H, int W, int Hs, int Ws, int dtype, int flip, void* stream);
 int cms_tta_vote(const cms_tta_desc* d, void* stream);
 
+/* Calibration and pseudo-label quality (csrc/calib.hip): the vote of cms_tta_vote with the confidence kept. One launch per batch
+ * takes the place of the vote launch and ADDS exact integers into device-side tables; the reference has nothing of the kind.
+ * A pixel is scored when its label is valid (label != ignore_index, 0 <= label < c), cms_tta_vote's rule. With inv_t = 1.0f / temps[t]
+ * (one fp32 division on the host) and u_ic = v_ic * inv_t (v_ic as in cms_tta_vote; the multiply is skipped when temps[t] == 1):
+ *   k >= 2   score_c = ((p_0c + p_1c) + ...), p_i = softmax(u_i) as in cms_tta_vote; pred the first index of the largest score;
+ *            pbar_c = score_c / k; conf = min(pbar_pred, 1); nll = -logf(max(pbar_label, FLT_MIN)). At temps[0] == 1 pred is
+ *            cms_tta_vote's bit for bit
+ *   k == 1   pred the argmax of the logits v_0 exactly as cms_tta_vote takes it (any temperature); z = sum_c expf(u_c - max u),
+ *            conf = 1 / z, pbar_c = expf(u_c - max u) * conf, nll = -((u_label - max u) - logf(z)). At temps[0] == 1 conf is the
+ *            float the consistency kernels compare with conf_thresh and nll the cross-entropy kernels' per-pixel loss
+ *   bin      #{ j : edges[j] <= conf }, an fp32 compare: nb bins from nb - 1 strictly ascending interior edges in (0, 1)
+ *   hist     int64 (c, nb, 3), keyed by pred: += pixels, pixels with pred == label, sum of rint(conf * 2^24); temps[0]
+ *   scores   int64 (2 + nt): += scored pixels, sum of rint(2^24 * sum_c (pbar_c - [c == label])^2) at temps[0], then per
+ *            temperature t sum of rint(2^20 * min(nll_t, 88))
+ *   cm, pred_out   as cms_tta_desc's, cm over the same scored pixels
+ *   edges, temps   HOST memory (they travel as kernel arguments); every other pointer is device memory
+ * Every sum is of integers, so it does not depend on the order of the atomics: the same input gives the same bits. Ranges: conf
+ * <= 1, the squared error <= 2 and nll <= 88 give at most 2^31 * 88 * 2^20 < 2^58 per launch. The workgroup's tables live in LDS
+ * (at most 64 KiB of scores, 48 KiB of histogram, 16 KiB of matrix) and leave with one 64-bit atomic per non-empty cell. Everything
+ * cms_tta_vote refuses is refused, and: nb outside 1..48, edges NULL with nb > 1, an edge that is not in (0, 1) or not above
+ * its predecessor, nt outside 1..8, temps NULL, a temperature that is not finite and > 0, hist / scores / labels NULL: CMS_EINVAL,
+ * decided before any HIP call; nothing is launched. */
+#define CMS_CALIB_MAX_BINS 48
+#define CMS_CALIB_MAX_TEMPS 8
+typedef struct {
+    const float* logits[CMS_TTA_MAX_VIEWS];
+    int h[CMS_TTA_MAX_VIEWS], w[CMS_TTA_MAX_VIEWS], flip[CMS_TTA_MAX_VIEWS];
+    int n, c, H, W, k, align_corners;
+    const void* labels;
+    int label_dtype;      /* CMS_LABEL_U8 / CMS_LABEL_I64 */
+    int ignore_index;
+    int64_t* cm;
+    uint8_t* pred_out;
+    int nb;
+    const float* edges;   /* nb - 1, host memory */
+    int nt;
+    const float* temps;   /* nt, host memory; temps[0] is the histogram's */
+    int64_t* hist;
+    int64_t* scores;
+} cms_calib_desc;
+int cms_calib_accumulate(const cms_calib_desc* d, void* stream);
+
 /* ClassMix (csrc/classmix.hip; Olsson et al., WACV 2021): a mixing mask cut along the predicted class regions of a batch. Per
  * sample, with pred(y, x) the argmax over c of the bilinear sample (under `align_corners`) of logits[n, c] -- bit for bit the
  * prediction cms_tta_vote writes for k == 1 without a flip: first index on a tie, NaN maximal, no interpolation when (h, w) == (H, W):
