@@ -136,6 +136,14 @@ class TtaDesc(C.Structure):
                 ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int), ('cm', c_void_p), ('pred_out', c_void_p)]
 
 
+class WindowDesc(C.Structure):
+    _fields_ = ([('logits', c_void_p * TTA_MAX_VIEWS)] +
+                [(name, c_int * TTA_MAX_VIEWS) for name in ('hl', 'wl', 'Hv', 'Wv', 'gy', 'gx', 'eh', 'ew', 'sh', 'sw', 'flip')] +
+                [('wh', c_int), ('ww', c_int),
+                 ('n', c_int), ('c', c_int), ('H', c_int), ('W', c_int), ('k', c_int), ('align_corners', c_int),
+                 ('labels', c_void_p), ('label_dtype', c_int), ('ignore_index', c_int), ('cm', c_void_p), ('pred_out', c_void_p)])
+
+
 CALIB_MAX_BINS, CALIB_MAX_TEMPS = 48, 8
 
 
@@ -351,6 +359,8 @@ PROTOTYPES = {
     'cms_crf_refine': (c_int, [_P(CrfDesc), c_void_p, c_size_t, c_void_p]),
     'cms_surface_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cms_surface_distances': (c_int, [_P(SurfaceDesc), c_void_p]),
+    'cms_window_crop': (c_int, [c_void_p, c_void_p] + [c_int] * 12 + [c_void_p]),
+    'cms_window_vote': (c_int, [_P(WindowDesc), c_void_p]),
 }
 
 fn = {}

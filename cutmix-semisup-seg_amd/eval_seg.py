@@ -3,7 +3,8 @@ Score a trained model: `python eval_seg.py MODEL.pth --dataset pascal_aug [--sub
 [--flip] [--batch_size 10] [--n_val -1] [--val_seed 131] [--split_path FILE] [--bin_fill_holes] [--save_preds DIR]
 [--compute_dtype bf16|fp32] [--boundary_width 3,5,0.02] [--crf [--crf_iters 5] [--crf_radius 5] [--crf_dilation 3] [--crf_bi_w 4]
 [--crf_bi_xy 15] [--crf_bi_rgb 13] [--crf_pos_w 3] [--crf_pos_xy 3]] [--surface_dist] [--calibration [--calib_bins 15]
-[--calib_thresh 0.5,0.9,0.95,0.97,0.99] [--calib_temperature 1] [--calib_nll_temps LIST] [--calib_out FILE.json]]`.
+[--calib_thresh 0.5,0.9,0.95,0.97,0.99] [--calib_temperature 1] [--calib_nll_temps LIST] [--calib_out FILE.json]]
+[--window H,W [--window_stride H,W] [--window_batch N]]`.
 
 The reference has no such program: it evaluates inside a training run only, at one scale without a flip. MODEL.pth is the whole-module
 pickle a trainer writes with `--save_model` (or the reference's own). The data set is opened exactly as the trainers open it
@@ -43,7 +44,19 @@ two or more views the vote itself is then taken at T and one line says so. The t
 `--bin_fill_holes` does not touch them, and `--crf` is refused beside them. With T = 1 the mIoU lines are bit for bit what they are
 without the option. `--calib_out FILE.json` writes the integer tables and every derived score.
 
-What keeps the program from starting is said before the GPU is touched: a bad `--calib_*` value or one without `--calibration`,
+`--window H,W` (or one integer; off by default) evaluates by sliding window, as the semi-supervised segmentation papers report
+Cityscapes: every view of a batch is covered by overlapping windows of that size (tta.Windows, include/cutmixseg.h states the grid), the
+network sees the windows -- `--window_batch N` at a time, by default `--batch_size` -- and one launch stitches them: a pixel's score is
+the mean softmax probability of the windows that cover it, summed over the views (csrc/window.hip). `--window_stride H,W` (or one
+integer) defaults to ceil(2 * window / 3) and lies in [ceil(window / 4), window]; the window is a multiple of the network's block size.
+After the two lines above one more says what was done: `-- sliding window 512x1024 stride 342x683: 4500 windows over 500 images`.
+`--bin_fill_holes`, `--boundary_width`, `--surface_dist` and `--save_preds` see the stitched prediction; `--crf` and `--calibration`
+read whole views and are refused beside it. The windows tile the batch's padded canvas: with images of one size, or `--batch_size 1`,
+an image's prediction does not depend on its batch; with images of several sizes and a larger batch it can. Without `--window` every
+printed line and every saved file is what it was.
+
+What keeps the program from starting is said before the GPU is touched: a bad `--window*` value or one without `--window`, `--window`
+with `--crf` or `--calibration`, a window that is not a multiple of the network's block size, a bad `--calib_*` value or one without `--calibration`,
 `--calibration` with `--crf`, a model file that does not load, a data set that is not
 configured, `--subset test` without a held-out set, `--bin_fill_holes` on more than two classes, a model of another class count, bad
 `--scales`, a bad `--boundary_width`, a bad `--crf_*` value or one without `--crf`, more than one process.
@@ -140,10 +153,48 @@ def calibration_spec(calibration, calib_bins=None, calib_thresh=None, calib_temp
     return dict(n_bins=n_bins, thresholds=thresholds, labels=labels, temperature=temperature[0], nll_temperatures=more, out=calib_out)
 
 
+def window_spec(window, window_stride=None, window_batch=None, crf=None, calibration=None):
+    """--window, --window_stride and --window_batch as they were typed (None where not given; pairs and integers are taken too) ->
+    (tta.Windows, window_batch or None), or None without --window. No GPU, no torch."""
+    from . import tta as tta_mod
+    if window is None:
+        for name, v in (('window_stride', window_stride), ('window_batch', window_batch)):
+            if v is not None:
+                raise EvalNotRun('--{} is given without --window'.format(name))
+        return None
+    if crf is not None and crf is not False:
+        raise EvalNotRun('--window with --crf: the CRF launch reads whole views, not windows; give one of the two')
+    if calibration is not None and calibration is not False:
+        raise EvalNotRun('--window with --calibration: the calibration launch reads whole views, not windows; give one of the two')
+
+    def pair(v, what):
+        return tta_mod.parse_window(v, what) if isinstance(v, str) else v
+    try:
+        windows = tta_mod.Windows(pair(window, '--window'), None if window_stride is None else pair(window_stride, '--window_stride'))
+    except ValueError as e:
+        raise EvalNotRun(str(e) if str(e).startswith('--window') else '--window / --window_stride: {}'.format(e))
+    if window_batch is not None:
+        try:
+            window_batch = int(str(window_batch).strip())
+        except ValueError:
+            raise EvalNotRun('--window_batch {!r}: an integer of at least 1 is needed'.format(window_batch))
+        if window_batch < 1:
+            raise EvalNotRun('--window_batch must be at least 1, got {}'.format(window_batch))
+    return windows, window_batch
+
+
+def check_window_block(windows, block_size):
+    """a window that is not a multiple of the network's block size does not start"""
+    try:
+        windows.check_block(block_size)
+    except ValueError as e:
+        raise EvalNotRun('--window: {}'.format(e))
+
+
 def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes, boundary_width=None,
-            calibration=None, crf=None):
+            calibration=None, crf=None, windows=None):
     """Everything that can refuse, on the host -> (tta, net on the CPU, ds_dict, ndx). `calibration`: calibration_spec's dict, or
-    (flag, dict of the --calib_* values as typed), checked here."""
+    (flag, dict of the --calib_* values as typed), checked here. `windows`: a tta.Windows, held to the loaded network's block size."""
     from . import tta as tta_mod
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise EvalNotRun('eval_seg runs on one GPU: start one process (WORLD_SIZE={})'.format(os.environ['WORLD_SIZE']))
@@ -166,6 +217,8 @@ def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_pa
     if not isinstance(net, torch.nn.Module) or not hasattr(net, 'forward_lowres'):
         raise EvalNotRun('the model file {} holds a {}, not a whole network of this project (a trainer writes one with '
                          '--save_model)'.format(model_path, type(net).__name__))
+    if windows is not None:
+        check_window_block(windows, getattr(net, 'BLOCK_SIZE', (1, 1)))
 
     from .datapipe import datasets
     try:
@@ -189,18 +242,20 @@ def prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_pa
 
 def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_size=10, n_val=-1, val_seed=131, split_path=None,
              bin_fill_holes=False, save_preds=None, compute_dtype='bf16', boundary_width=None, crf=None, surface_dist=False,
-             calibration=None):
+             calibration=None, window=None, window_stride=None, window_batch=None):
     """-> the per-class IoU (numpy); prints the trainers' lines, with `crf` (crf.CRFParams) what the refinement changed, with
     `boundary_width` the contour scores after them, with `surface_dist` the surface distances after those, and with `calibration`
-    (calibration_spec's dict; True for the defaults) the calibration report after everything else."""
+    (calibration_spec's dict; True for the defaults) the calibration report after everything else. `window` / `window_stride`
+    (text as typed, or pairs) and `window_batch`: sliding-window evaluation (window_spec), its line after the two mIoU lines."""
     if crf is not None and not hasattr(crf, 'as_dict'):
         raise EvalNotRun('crf must be a crf.CRFParams, got {!r}'.format(crf))
     if calibration is True:
         calibration = calibration_spec(True, crf=crf)
     elif calibration is not None and not isinstance(calibration, dict):
         raise EvalNotRun('calibration must be True or the dict of calibration_spec, got {!r}'.format(calibration))
+    win = window_spec(window, window_stride, window_batch, crf=crf, calibration=calibration)
     tta, net, ds_dict, ndx = prepare(model_path, dataset, subset, scales, flip, n_val, val_seed, split_path, bin_fill_holes,
-                                     boundary_width, calibration, crf)
+                                     boundary_width, calibration, crf, None if win is None else win[0])
     spec = boundary_spec(boundary_width)
 
     import types
@@ -237,11 +292,16 @@ def evaluate(model_path, dataset, subset='val', scales='1', flip=False, batch_si
     if calibration is not None:
         cal_eval = more['calibration'] = evaluation.EvaluatorCalibration(
             run.n_classes, calibration['n_bins'], calibration['thresholds'], calibration['temperature'], calibration['nll_temperatures'])
+    if win is not None:
+        more.update(windows=win[0], window_batch=win[1] if win[1] is not None else batch_size)
     crf_stats = run.staged_eval(net, step, ndx, iou_eval, save_preds, tta=tta, **more)
     iou = iou_eval.score()
     prefix = 'VAL' if subset == 'val' else 'TEST'
     print('{} mIoU={:.3%}'.format(prefix, iou.mean()))
     print('-- {}'.format(', '.join(['{:.3%}'.format(x) for x in iou])))
+    if win is not None:
+        print('-- sliding window {}x{} stride {}x{}: {} windows over {} images'.format(
+            win[0].window[0], win[0].window[1], win[0].stride[0], win[0].stride[1], int(crf_stats), len(ndx)))
     if crf is not None:
         pixels, changed = (int(v) for v in crf_stats.cpu().tolist())
         print('-- CRF changed {:.3%} of the pixels'.format(changed / max(pixels, 1)))
@@ -322,16 +382,21 @@ def calibration_lines(prefix, cal, labels, n_views=1):
 @click.option('--calib_temperature', type=str, default=None, help='1')
 @click.option('--calib_nll_temps', type=str, default=None, help='up to seven more temperatures for the NLL line')
 @click.option('--calib_out', type=click.Path(dir_okay=False), default=None)
+@click.option('--window', type=str, default=None, help='H,W or one integer: sliding-window evaluation')
+@click.option('--window_stride', type=str, default=None, help='ceil(2 * window / 3)')
+@click.option('--window_batch', type=str, default=None, help='windows per forward pass; --batch_size')
 def experiment(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
                compute_dtype, boundary_width, crf, surface_dist, calibration, **options):
     if batch_size < 1:
         raise EvalNotRun('--batch_size must be at least 1')
     calib_options = {k: options.pop(k) for k in CALIB_OPTIONS}
+    window_options = {k: options.pop(k) for k in ('window', 'window_stride', 'window_batch')}
+    window_spec(crf=crf, calibration=calibration, **window_options)      # a malformed --window* value, or --window beside --crf
     boundary_spec(boundary_width)                  # a malformed one is said before the model file is even opened
     calib = calibration_spec(calibration, crf=crf, **calib_options)      # ... and a --calib_* value, or --calibration beside --crf
     params = crf_spec(crf, **options)              # ... and so is a malformed --crf_* value, or one without --crf
     evaluate(model_path, dataset, subset, scales, flip, batch_size, n_val, val_seed, split_path, bin_fill_holes, save_preds,
-             compute_dtype, boundary_width, params, surface_dist, calib)
+             compute_dtype, boundary_width, params, surface_dist, calib, **window_options)
 
 
 if __name__ == '__main__':

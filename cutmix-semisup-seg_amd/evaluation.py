@@ -275,6 +275,18 @@ class EvaluatorIoU(object):
         ops.tta_vote(logits_list, flips, self.num_classes, out_size, labels=truth, ignore_index=ignore_value,
                      align_corners=align_corners, cm=self._cm())
 
+    def sample_windows(self, logits_list, flips, view_sizes, windows, truth, out_size, ignore_value=255, align_corners=True):
+        """sample_logits_tta over the window logits of a batch's views (tta.Windows): the stitch and vote of ops.window_vote in the
+        place of the vote."""
+        args = (logits_list, flips, view_sizes, windows.window, windows.stride, self.num_classes, out_size)
+        if self.fill_holes:
+            _, pred = ops.window_vote(*args, align_corners=align_corners, want_pred=True)
+            t = truth[:, 0] if truth.dim() == 4 else truth
+            ops.fill_holes(pred, out=pred, truth=_to_u8_cuda(t, pred.device, 'truth'), ignore_index=ignore_value,
+                           cm=self._cm())
+            return
+        ops.window_vote(*args, labels=truth, ignore_index=ignore_value, align_corners=align_corners, cm=self._cm())
+
     def add_confusion(self, cm):
         """Add a batch's int64 (C,C) confusion matrix that is already on the device (EvaluatorCalibration.sample_views')."""
         self._cm().add_(cm)

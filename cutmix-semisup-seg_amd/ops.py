@@ -1171,6 +1171,132 @@ def tta_vote(logits_list, flips, num_classes, out_size, labels=None, ignore_inde
     return cm, pred
 
 
+# ---------------------------------------------------------------------------------------------- sliding-window evaluation
+def _window_grid(view, window, stride):
+    """one axis of include/cutmixseg.h's window grid -> (windows, effective window)"""
+    return (1 if view <= window else -(-(view - window) // stride) + 1), min(window, view)
+
+
+def _window_pair(window, stride, what):
+    (wh, ww), (sh, sw) = _size2(window, what + ': window'), _size2(stride, what + ': stride')
+    for w, s in ((wh, sh), (ww, sw)):
+        if s > w or s < -(-w // 4):
+            raise ValueError('{}: stride {} x {} outside [ceil(window / 4), window] of the window {} x {}'.format(what, sh, sw, wh, ww))
+    return wh, ww, sh, sw
+
+
+def window_crop(image, view_size, flip, window, stride, out=None):
+    """All windows of one view in one launch (csrc/window.hip): image (N,C,H,W) fp32 / bf16 CUDA -> (N*gy*gx, C, eh, ew) of the same
+    dtype, window (j, i) of sample n being item (n*gy + j)*gx + i and bit for bit tta_resize(image, view_size, flip)[n, :, y1_j:y1_j+eh,
+    x1_i:x1_i+ew]; the view is never materialised. `out`: a contiguous tensor of that shape and dtype to fill."""
+    if not torch.is_tensor(image) or image.dim() != 4:
+        raise TypeError('window_crop: image must be an (N,C,H,W) tensor')
+    dtype = _dtype_code(image)
+    hv, wv = _size2(view_size, 'window_crop: view_size')
+    wh, ww, sh, sw = _window_pair(window, stride, 'window_crop')
+    _need_cuda(image, out)
+    image = image.contiguous()
+    n, c, h, w = (int(s) for s in image.shape)
+    if min(n, c, h, w) < 1:
+        raise ValueError('window_crop: empty image {}'.format(tuple(image.shape)))
+    (gy, eh), (gx, ew) = _window_grid(hv, wh, sh), _window_grid(wv, ww, sw)
+    shape = (n * gy * gx, c, eh, ew)
+    if max(n * c * h * w, shape[0] * c * eh * ew) > 2 ** 31 - 1:
+        raise ValueError('window_crop: more than 2^31 - 1 elements')
+    if out is None:
+        out = torch.empty(shape, dtype=image.dtype, device=image.device)
+    elif out.dtype != image.dtype or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise TypeError('window_crop: out must be a contiguous {} tensor of shape {}'.format(image.dtype, shape))
+    check(fn['cms_window_crop'](_ptr(image), _ptr(out), n, c, h, w, hv, wv, int(bool(flip)), wh, ww, sh, sw, dtype, _stream()),
+          'cms_window_crop')
+    return out
+
+
+def window_vote(logits, flips, view_sizes, window, stride, n_classes, size, labels=None, ignore_index=255, align_corners=True,
+                cm=None, pred=None, want_pred=False):
+    """
+    The stitch and vote over the windows of the views of a batch (csrc/window.hip; include/cutmixseg.h states the definition):
+    logits[i] (N*G_i, C, hl_i, wl_i) fp32 CUDA, the window batch of view i of size view_sizes[i], flips[i] true where the view was
+    computed on the mirrored input; `window` / `stride` pairs of integers; `size` the canvas (H, W). A pixel's score is the sum over
+    the views of the mean softmax probability of the windows that cover it; where no view has more than one window this is
+    tta_vote, bit for bit. labels, cm, pred and the return value are tta_vote's.
+    """
+    logits = list(logits)
+    flips = [bool(f) for f in flips]
+    view_sizes = [_size2(v, 'window_vote: view size') for v in view_sizes]
+    k = len(logits)
+    if k < 1 or k > _lib.TTA_MAX_VIEWS:
+        raise ValueError('window_vote: {} views, 1 to {} are built'.format(k, _lib.TTA_MAX_VIEWS))
+    if len(flips) != k or len(view_sizes) != k:
+        raise ValueError('window_vote: {} views but {} flips and {} view sizes'.format(k, len(flips), len(view_sizes)))
+    if any(not torch.is_tensor(t) or t.dim() != 4 for t in logits):
+        raise TypeError('window_vote: every view must be an (N*G,C,h,w) tensor')
+    n_classes = int(n_classes)
+    if n_classes < 1 or n_classes > 64:
+        raise ValueError('window_vote: 1 <= n_classes <= 64, got {}'.format(n_classes))
+    H, W = _size2(size, 'window_vote: size')
+    wh, ww, sh, sw = _window_pair(window, stride, 'window_vote')
+    grids = [(_window_grid(hv, wh, sh), _window_grid(wv, ww, sw)) for hv, wv in view_sizes]
+    g0 = grids[0][0][0] * grids[0][1][0]
+    if int(logits[0].shape[0]) % g0:
+        raise ValueError('window_vote: {} window logits for a view of {} windows per sample'.format(int(logits[0].shape[0]), g0))
+    n = int(logits[0].shape[0]) // g0
+    for t, ((gy, eh), (gx, ew)) in zip(logits, grids):
+        if int(t.shape[0]) != n * gy * gx or int(t.shape[1]) != n_classes or min(int(s) for s in t.shape) < 1:
+            raise ValueError('window_vote: logits of shape {} for {} samples, {} x {} windows and {} classes'.format(
+                tuple(t.shape), n, gy, gx, n_classes))
+        if int(t.shape[2]) > eh or int(t.shape[3]) > ew:
+            raise ValueError('window_vote: logits of {} x {} are larger than their window of {} x {}'.format(
+                int(t.shape[2]), int(t.shape[3]), eh, ew))
+        if t.numel() > 2 ** 31 - 1:
+            raise ValueError('window_vote: more than 2^31 - 1 logits in a view')
+    if n < 1:
+        raise ValueError('window_vote: no samples')
+    if n * H * W > 2 ** 31 - 1:
+        raise ValueError('window_vote: more than 2^31 - 1 output pixels')
+    if labels is not None:
+        if not torch.is_tensor(labels) or labels.dtype not in (torch.uint8, torch.int64):
+            raise TypeError('window_vote: labels must be a uint8 or int64 tensor')
+        if labels.dim() == 4:
+            labels = labels[:, 0]
+        if tuple(labels.shape) != (n, H, W):
+            raise ValueError('window_vote: labels of shape {}, {} expected'.format(tuple(labels.shape), (n, H, W)))
+    if cm is not None:
+        if labels is None:
+            raise ValueError('window_vote: cm given without labels')
+        if cm.dtype != torch.int64 or tuple(cm.shape) != (n_classes, n_classes) or not cm.is_contiguous():
+            raise TypeError('window_vote: cm must be a contiguous int64 ({0},{0}) matrix'.format(n_classes))
+    if pred is not None:
+        if not torch.is_tensor(pred) or pred.dtype != torch.uint8 or not pred.is_contiguous() or tuple(pred.shape) != (n, H, W):
+            raise TypeError('window_vote: pred must be a contiguous uint8 tensor of shape {}'.format((n, H, W)))
+        want_pred = True
+    if labels is None and not want_pred:
+        raise ValueError('window_vote: nothing to produce (no labels and want_pred is False)')
+    _need_cuda(labels, cm, pred, *logits)
+    views = [_f32c(t) for t in logits]         # kept alive until the launch is queued
+    dev = views[0].device
+    if labels is not None:
+        labels = labels.contiguous()
+        if cm is None:
+            cm = torch.zeros((n_classes, n_classes), dtype=torch.int64, device=dev)
+    if want_pred and pred is None:
+        pred = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    d = _lib.WindowDesc()
+    for i, (t, ((gy, eh), (gx, ew))) in enumerate(zip(views, grids)):
+        d.logits[i], d.hl[i], d.wl[i], d.flip[i] = t.data_ptr(), int(t.shape[2]), int(t.shape[3]), int(flips[i])
+        d.Hv[i], d.Wv[i] = view_sizes[i]
+        d.gy[i], d.gx[i], d.eh[i], d.ew[i], d.sh[i], d.sw[i] = gy, gx, eh, ew, sh, sw
+    d.wh, d.ww = wh, ww
+    d.n, d.c, d.H, d.W, d.k, d.align_corners = n, n_classes, H, W, k, int(bool(align_corners))
+    d.labels = labels.data_ptr() if labels is not None else None
+    d.label_dtype = _lib.LABEL_I64 if labels is not None and labels.dtype == torch.int64 else _lib.LABEL_U8
+    d.ignore_index = -1 if ignore_index is None else int(ignore_index)
+    d.cm = cm.data_ptr() if cm is not None else None
+    d.pred_out = pred.data_ptr() if pred is not None else None
+    check(fn['cms_window_vote'](C.byref(d), _stream()), 'cms_window_vote')
+    return cm, pred
+
+
 def calibration_accumulate(logits_list, flips, num_classes, out_size, labels, edges, temps, hist, scores, ignore_index=255,
                            align_corners=True, cm=None, want_pred=False, pred=None):
     """

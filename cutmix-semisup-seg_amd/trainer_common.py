@@ -368,7 +368,7 @@ class DatasetRun(object):
         return [iter(st) for st in self._streams]
 
     def staged_eval(self, eval_net, step, ndx, evaluator=None, preds_dir=None, tta=None, boundary=None, crf=None, surface=None,
-                    calibration=None):
+                    calibration=None, windows=None, window_batch=None):
         """The reference's evaluation loop over `ndx` in index order: whole images, centred on a padded canvas per batch
         (stage_eval); padding carries label 255 and is ignored. With a `tta.TTA` every batch is evaluated as the vote over its
         views (eval_seg); `step` is read for `align_corners` only. With `boundary` (evaluation.EvaluatorBoundary) the batch's
@@ -380,12 +380,22 @@ class DatasetRun(object):
         `preds_dir` receives, and the call returns the device-side int64 [pixels, labels the refinement changed] (else None). With
         `calibration` (evaluation.EvaluatorCalibration; not together with `crf`) the batch's views -- one without `tta` -- are forwarded
         as above and the calibration launch takes the place of the vote launch: it scores the confidence of every labelled pixel and
-        gives the prediction and the confusion matrix that `evaluator`, `boundary`, `surface` and `preds_dir` then see."""
+        gives the prediction and the confusion matrix that `evaluator`, `boundary`, `surface` and `preds_dir` then see. With
+        `windows` (tta.Windows; not together with `crf` or `calibration`, which read whole views) every view of the batch -- one
+        without `tta` -- is covered by overlapping windows on the batch's padded canvas, forwarded in chunks of at most
+        `window_batch` windows and stitched by one ops.window_vote launch; `evaluator`, `boundary`, `surface` and `preds_dir` see the
+        stitched prediction, and the call returns the number of windows forwarded."""
         import numpy as np
         import torch
         from . import ops
         from .datapipe import seg_data
         crf_total = None
+        n_windows = 0
+        if windows is not None:
+            if crf is not None or calibration is not None:
+                raise ValueError('staged_eval: crf and calibration read whole views, not windows')
+            from . import tta as tta_mod
+            tta = tta if tta is not None else tta_mod.TTA((1.0,), False)
         if calibration is not None:
             if crf is not None:
                 raise ValueError('staged_eval: calibration scores the network\'s own distribution, crf refines it into another one')
@@ -410,10 +420,13 @@ class DatasetRun(object):
                     if evaluator is not None:
                         evaluator.sample(ev['labels'][:, 0], pred, ignore_value=255)
                 elif tta is not None:
+                    more = {} if calibration is None else dict(calibration=calibration)
+                    if windows is not None:
+                        more = dict(windows=windows, window_batch=window_batch)
+                        n_windows += len(batch_ndx) * tta.window_count(ev['canvas'], self.student_net.BLOCK_SIZE, windows)
                     _, pred = tta.predict(eval_net, ev['image'], ev['canvas'], step.align_corners, labels=ev['labels'],
                                           ignore_index=255, want_pred=want_pred,
-                                          block_size=self.student_net.BLOCK_SIZE, evaluator=evaluator,
-                                          **({} if calibration is None else dict(calibration=calibration)))
+                                          block_size=self.student_net.BLOCK_SIZE, evaluator=evaluator, **more)
                 else:
                     logits = eval_net.forward_lowres(ev['image'])
                     if evaluator is not None:
@@ -432,7 +445,7 @@ class DatasetRun(object):
                     pred = pred.cpu().numpy()
                     for k, sample_ndx in enumerate(batch_ndx):
                         self.ds_src.save_prediction_by_index(preds_dir, pred[k].astype(np.uint32), sample_ndx)
-        return crf_total
+        return crf_total if windows is None else n_windows
 
     def evaluate_with(self, eval_net, step):
         """-> the `evaluate(evaluator)` of run_epochs over the validation set."""

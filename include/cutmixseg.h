@@ -1208,6 +1208,59 @@ typedef struct {
 size_t cms_surface_workspace_bytes(int n, int h, int w, int num_classes);
 int cms_surface_distances(const cms_surface_desc* d, void* stream);
 
+/* Sliding-window evaluation (csrc/window.hip): every view of an evaluation batch is covered by overlapping windows of one size, the
+ * network sees the windows, and one launch stitches the windows' low-resolution logits into the prediction of the canvas. The
+ * reference evaluates whole images; the definition below is this project's own.
+ *
+ * The canvas is H x W; view v has size (Hv, Wv) and may be mirrored. The window is (wh, ww), a view's stride (sh, sw). Per view and
+ * axis (y shown, x alike):
+ *   eh      min(wh, Hv), the effective window height
+ *   gy      1 if Hv <= wh, else ceil((Hv - wh) / sh) + 1 windows
+ *   y1_j    min(j * sh, Hv - eh), j < gy: the last window is flush with the edge
+ *   G       gy * gx windows, all (eh, ew); window (j, i) of sample n is item (n * gy + j) * gx + i of the view's window batch, whose
+ *           logits are (n * G, c, hl, wl) f32
+ *
+ * cms_window_crop: all windows of one view in one launch, straight from the canvas image.
+ *   src     (n, c, H, W), dst (n * G, c, eh, ew), both of `dtype` (CMS_F32 / CMS_BF16), dense; must not overlap
+ *   dst[(n * gy + j) * gx + i, ch, y, x] is bit for bit element (n, ch, y1_j + y, x1_i + x) of what cms_tta_resize makes of src at
+ *           (Hv, Wv) with `flip`; the view is never materialised. With (Hv, Wv) == (H, W) and no flip it is a strided copy. Every
+ *           element of dst is written.
+ * NULL pointers, a size below 1, an unknown dtype, a stride above its window or below ceil(window / 4), or more than 2^31 - 1
+ * elements in src or dst return CMS_EINVAL, decided before any HIP call.
+ *
+ * cms_window_vote: per canvas pixel (y, x) of sample n, for view v in order:
+ *   G == 1  the view is read exactly as cms_tta_vote reads a view of (hl, wl): same taps, same un-mirroring, same softmax;
+ *           score_c += p_c
+ *   G > 1   the pixel's view row is ry = min(Hv - 1, ((2 y + 1) Hv) / (2 H)) in integers (ry = y when Hv == H), its column rx
+ *           alike and then, for a mirrored view, rx = Wv - 1 - rx. The covering windows are those with y1_j <= ry < y1_j + eh and
+ *           x1_i <= rx < x1_i + ew, cnt their number (>= 1). For each covering window in row-major (j, i) order the taps are
+ *           bilin_tap(ry - y1_j, bilin_scale(hl, eh, align_corners), hl, align_corners), x alike and never mirrored (the
+ *           coordinate already is); the window's logits are gathered at them, p = softmax as in cms_tta_vote, and
+ *           score_c += p_c / (float)cnt (one fp32 division per class and window)
+ *   pred    the first index of the largest score, NaN counting as maximal
+ * If every view has G == 1 the call IS cms_tta_vote on (hl, wl, flip) -- its single-view argmax of the logits included. labels,
+ * label_dtype, ignore_index, cm and pred_out are cms_tta_desc's. One launch, no workspace, no host synchronisation; integer
+ * histogram: the same input gives the same bits, and a sample's prediction does not depend on the rest of its batch. Whatever
+ * cms_tta_vote refuses (with h = hl, w = wl), Hv or Wv below 1, a window or stride below 1, a stride above its window or below
+ * ceil(window / 4), eh / ew / gy / gx that do not follow from (Hv, Wv, window, stride), hl > eh or wl > ew, or more than 2^31 - 1
+ * logits in a view return CMS_EINVAL, decided before any HIP call; nothing is launched. */
+typedef struct {
+    const float* logits[CMS_TTA_MAX_VIEWS];
+    int hl[CMS_TTA_MAX_VIEWS], wl[CMS_TTA_MAX_VIEWS], Hv[CMS_TTA_MAX_VIEWS], Wv[CMS_TTA_MAX_VIEWS];
+    int gy[CMS_TTA_MAX_VIEWS], gx[CMS_TTA_MAX_VIEWS], eh[CMS_TTA_MAX_VIEWS], ew[CMS_TTA_MAX_VIEWS];
+    int sh[CMS_TTA_MAX_VIEWS], sw[CMS_TTA_MAX_VIEWS], flip[CMS_TTA_MAX_VIEWS];
+    int wh, ww;           /* the window */
+    int n, c, H, W, k, align_corners;
+    const void* labels;
+    int label_dtype;      /* CMS_LABEL_U8 / CMS_LABEL_I64 */
+    int ignore_index;
+    int64_t* cm;
+    uint8_t* pred_out;
+} cms_window_desc;
+int cms_window_crop(const void* src, void* dst, int n, int c, int H, int W, int Hv, int Wv, int flip, int wh, int ww, int sh, int sw,
+                    int dtype, void* stream);
+int cms_window_vote(const cms_window_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
