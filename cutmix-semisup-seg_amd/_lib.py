@@ -40,6 +40,13 @@ class ConsistencyDesc(C.Structure):
                 ('loss_fn', c_int), ('conf_thresh', c_float), ('conf_per_pixel', c_int)]
 
 
+CTHRESH_REPLICAS = 32         # CMS_CTHRESH_REPLICAS
+
+
+class CthreshDesc(C.Structure):
+    _fields_ = [('cons', ConsistencyDesc), ('thr', c_void_p), ('table', c_void_p)]
+
+
 class IctDesc(C.Structure):
     _fields_ = [('l_stu', c_void_p), ('l_tea0', c_void_p), ('l_tea1', c_void_p), ('lam', c_void_p),
                 ('um0', c_void_p), ('um1', c_void_p),
@@ -228,6 +235,13 @@ PROTOTYPES = {
     'cms_consistency_fused_supported': (c_int, [_P(ConsistencyDesc)]),
     'cms_consistency_fwd_bwd': (c_int, [_P(ConsistencyDesc), c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'cms_scale_by_scalar': (c_int, [c_void_p, C.c_longlong, c_void_p, c_int, c_float, c_void_p]),
+    'cms_cthresh_workspace_bytes': (c_size_t, [_P(CthreshDesc)]),
+    'cms_cthresh_fused_supported': (c_int, [_P(CthreshDesc)]),
+    'cms_cthresh_fwd': (c_int, [_P(CthreshDesc), c_void_p, c_void_p, c_void_p]),
+    'cms_cthresh_bwd': (c_int, [_P(CthreshDesc), c_void_p, c_void_p, c_void_p]),
+    'cms_cthresh_fwd_bwd': (c_int, [_P(CthreshDesc), c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'cms_cthresh_update': (c_int, [c_int, c_int, C.c_double, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     'cms_ict_blend': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, C.c_longlong, c_void_p]),
     'cms_ict_workspace_bytes': (c_size_t, [_P(IctDesc)]),
     'cms_ict_fwd': (c_int, [_P(IctDesc), c_void_p, c_void_p, c_void_p]),

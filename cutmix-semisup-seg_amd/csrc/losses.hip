@@ -17,58 +17,11 @@
 //
 // The tile walks, the tiled adjoint and the launch paths are csrc/loss_tiles.hpp, shared with the ICT loss (ict.hip) and the
 // augmentation consistency (aug_loss.hip); this file also holds the one definition of the switch state they read.
-#include "loss_tiles.hpp"
+#include "cons_args.hpp"
 
 namespace cms {
 
 // ------------------------------------------------------------------------------------------------ consistency
-struct ConsArgs {
-    cms_consistency_desc d;
-    Geo g;
-    float tau, inv_root_c;
-};
-
-struct ConsPixel {
-    bool m;
-    float um;
-    const float* tea;
-    int which;          // 0: l_tea0, 1: l_tea1 -- for callers that read the teacher logits from an LDS copy
-};
-
-__device__ __forceinline__ ConsPixel cons_pixel_inputs(const ConsArgs& a, int n, int y, int x) {
-    const cms_consistency_desc& d = a.d;
-    const size_t pix = ((size_t)n * d.H + y) * d.W + x;
-    ConsPixel p;
-    if (d.mask) {
-        p.m = d.mask[pix] >= 0.5f;
-    } else {
-        p.m = box_mask_bit(d.ranges + (size_t)n * d.n_boxes * 4, d.n_boxes, y, x, d.invert != 0);
-    }
-    const size_t sample = (size_t)n * d.c * d.h * d.w;
-    if (d.mode == MODE_MIX) {
-        // paste of teacher logits and of the validity masks with the same box mask (:351, :363)
-        p.tea = (p.m ? d.l_tea1 : d.l_tea0) + sample;
-        p.which = p.m ? 1 : 0;
-        const float* um = p.m ? d.um1 : d.um0;
-        p.um = um ? um[pix] : 1.0f;
-    } else {
-        // cut mode: loss_mask = cut_mask * um (:401)
-        p.tea = d.l_tea0 + sample;
-        p.which = 0;
-        p.um = p.m ? (d.um0 ? d.um0[pix] : 1.0f) : 0.0f;
-    }
-    return p;
-}
-
-// student | teacher 0 | teacher 1 rectangles of a tile, `pstride` floats apart
-__device__ __forceinline__ void cons_stage(const ConsArgs& a, int n, const Patch& p, float* P, int pstride) {
-    const Geo& g = a.g;
-    const size_t plane = (size_t)g.h * g.w, sample = (size_t)n * g.c * plane;
-    stage_patch(P, a.d.l_stu + sample, g.c, plane, g.w, p);
-    stage_patch(P + pstride, a.d.l_tea0 + sample, g.c, plane, g.w, p);
-    if (a.d.mode == MODE_MIX) stage_patch(P + 2 * pstride, a.d.l_tea1 + sample, g.c, plane, g.w, p);
-}
-
 // one pixel of a forward kernel from its two gathers: the three loss sums
 template <int CT, bool IDENT>
 __device__ __forceinline__ void cons_fwd_pixel(const ConsArgs& a, const ConsPixel& px, const Gather<IDENT>& gs, const Gather<IDENT>& gt,
@@ -488,7 +441,7 @@ int fused_tiles(const Geo& g, int n_patches) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int check_cons(const cms_consistency_desc* d) {
+int check_cons(const cms_consistency_desc* d) {
     CMS_REQUIRE(d != nullptr, "consistency: null descriptor");
     CMS_REQUIRE(d->l_stu && d->l_tea0, "consistency: l_stu / l_tea0 must not be NULL");
     CMS_REQUIRE(d->mode == CMS_MODE_MIX || d->mode == CMS_MODE_CUT, "consistency: unknown mode %d", d->mode);
@@ -499,7 +452,7 @@ static int check_cons(const cms_consistency_desc* d) {
     return rc ? rc : check_loss_fn(d);
 }
 
-static ConsArgs make_cons_args(const cms_consistency_desc* d) {
+ConsArgs make_cons_args(const cms_consistency_desc* d) {
     ConsArgs a;
     a.d = *d;
     a.g = geo_of(d);

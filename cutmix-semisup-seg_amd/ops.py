@@ -97,12 +97,100 @@ def cutmix_paste(x0, x1, ranges=None, invert=True, mask=None, out=None):
 
 
 # ---------------------------------------------------------------------------------------------- consistency loss
+def parse_class_thresh(text, n_classes=None):
+    """--class_thresh: 'freematch', or comma-separated numbers in (0, 1] (one per class, checked once `n_classes` is known).
+    -> 'freematch' or a list of floats; ValueError names what is wrong."""
+    if isinstance(text, str) and text.strip().lower() == 'freematch':
+        return 'freematch'
+    if isinstance(text, str):
+        try:
+            vals = [float(v) for v in text.split(',')]
+        except ValueError:
+            raise ValueError("class_thresh must be 'freematch' or comma-separated numbers, got {!r}".format(text))
+    else:
+        vals = [float(v) for v in text]
+    if len(vals) == 0 or not all(0.0 < v <= 1.0 for v in vals):      # (a NaN fails the comparison)
+        raise ValueError('class_thresh: every threshold must be in (0, 1], got {}'.format(vals))
+    if n_classes is not None and len(vals) != int(n_classes):
+        raise ValueError('class_thresh lists {} thresholds for {} classes'.format(len(vals), int(n_classes)))
+    return vals
+
+
+class ClassThresholds(object):
+    """Per-class confidence thresholds of the consistency loss and the device state behind them (csrc/cthresh.hip; definition in
+    include/cutmixseg.h). mode='freematch': self-adaptive (FreeMatch without its fairness loss) -- tau, an EMA of the teacher's mean
+    confidence, scaled per class by an EMA p~ of its mean class distribution, clamped to [floor, ceil]; both start at 1 / C. A list
+    of C numbers: static thresholds. Every buffer is allocated once, so a captured graph replays against the same addresses:
+        thr f32[C] | state f64[1 + C] = (tau, p~) | table u64[R][2 + 3C] of the iteration (R copies, summed) | epoch u64[1 + 2C].
+    The consistency launches of an iteration add into `table`; `update()` (one launch, no host sync) folds the table of the
+    PREVIOUS iteration ahead of the next one's launches; `pop_epoch_report()` is the one host synchronisation per epoch."""
+    MAX_CLASSES = 128
+
+    def __init__(self, n_classes, device, mode='freematch', ema=0.999, floor=0.0, ceil=0.97):
+        C_ = int(n_classes)
+        if not 1 <= C_ <= self.MAX_CLASSES:
+            raise ValueError('ClassThresholds: 1..{} classes, got {}'.format(self.MAX_CLASSES, n_classes))
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('cutmix-semisup-seg_amd ops run on the GPU only (got device {}); there is no CPU fallback'.format(device))
+        self.n_classes = C_
+        self.adaptive = isinstance(mode, str)
+        self.ema, self.floor, self.ceil = float(ema), float(floor), float(ceil)
+        if not (0.0 <= self.ema < 1.0):
+            raise ValueError('ClassThresholds: ema must be in [0, 1), got {}'.format(ema))
+        if not (0.0 <= self.floor <= self.ceil <= 1.0 and self.ceil > 0.0):
+            raise ValueError('ClassThresholds: need 0 <= floor <= ceil <= 1 and ceil > 0, got floor {} ceil {}'.format(floor, ceil))
+        if self.adaptive:
+            if parse_class_thresh(mode) != 'freematch':
+                raise ValueError("ClassThresholds: mode must be 'freematch' or a list of thresholds")
+            t0 = p0 = 1.0 / C_
+            thr0 = np.full(C_, np.float32(min(self.ceil, max(self.floor, t0 * p0 / p0))), dtype=np.float32)
+        else:
+            thr0 = np.asarray(parse_class_thresh(mode, C_), dtype=np.float32)
+        state0 = np.full(1 + C_, 1.0 / C_, dtype=np.float64)
+        self.thr = torch.from_numpy(thr0).to(device)
+        self.state = torch.from_numpy(state0).to(device)
+        # (torch has no unsigned 64-bit arithmetic: int64 storage, the kernels see unsigned long long; counts stay far below 2^63)
+        # (CTHRESH_REPLICAS copies: a workgroup adds into one of them, `iteration_table()` and the update launch sum them)
+        self.table = torch.zeros((_lib.CTHRESH_REPLICAS, 2 + 3 * C_), dtype=torch.int64, device=device)
+        self.epoch = torch.zeros(1 + 2 * C_, dtype=torch.int64, device=device)
+
+    def iteration_table(self):
+        """the iteration's table so far, int64[2 + 3C] on the device: the sum of the copies the launches add into"""
+        return self.table.sum(dim=0)
+
+    def update(self):
+        """Fold the previous iteration's table (cms_cthresh_update) on the current stream. No host sync."""
+        check(fn['cms_cthresh_update'](self.n_classes, int(self.adaptive), self.ema, self.floor, self.ceil, _ptr(self.state),
+                                       _ptr(self.thr), _ptr(self.table), _ptr(self.epoch), _stream()), 'cms_cthresh_update')
+
+    def pop_epoch_report(self):
+        """The epoch's report, and the epoch counters cleared: dict(thr, tau, pixels, pass_rate) -- per class the valid pixels the
+        teacher predicted as that class and the share of them that passed (None where there were none). ONE host synchronisation: the
+        three buffers cross as one byte string. The counters are those `update()` has folded: a caller that wants the iteration just
+        run in the report calls `update()` first (the trainer's hook does; the update at the head of the next step then finds an empty
+        table and leaves everything as it is)."""
+        C_ = self.n_classes
+        raw = torch.cat([t.view(torch.uint8) for t in (self.state, self.epoch, self.thr)]).cpu().numpy()
+        self.epoch.zero_()
+        state = raw[:8 * (1 + C_)].view(np.float64)
+        ep = raw[8 * (1 + C_):8 * (1 + C_) + 8 * (1 + 2 * C_)].view(np.uint64)
+        thr = raw[8 * (2 + 3 * C_):].view(np.float32).copy()
+        pred, passed = ep[1:1 + C_], ep[1 + C_:1 + 2 * C_]
+        rate = [float(passed[c]) / float(pred[c]) if pred[c] > 0 else None for c in range(C_)]
+        return dict(thr=thr, tau=float(state[0]), p=state[1:].copy(), n_valid=int(ep[0]), pixels=[int(v) for v in pred], pass_rate=rate)
+
+
 class _LossConfig(object):
     """What the three consistency losses share: the per-pixel loss function, the confidence threshold and its mode, the upsample."""
 
-    def __init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners):
+    def __init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners, class_thresh=None):
         if loss_fn not in _lib.LOSS_IDS:
             raise ValueError('Unknown consistency loss function {}'.format(loss_fn))
+        if class_thresh is not None and not isinstance(class_thresh, ClassThresholds):
+            raise TypeError('class_thresh must be an ops.ClassThresholds or None')
+        # per-class confidence thresholds (ClassThresholds) in the place of conf_thresh; None: the scalar threshold
+        self.class_thresh = class_thresh
         self.loss_fn = loss_fn
         self.conf_thresh = float(conf_thresh)
         self.conf_per_pixel = bool(conf_per_pixel)
@@ -120,10 +208,10 @@ class ConsistencyConfig(_LossConfig):
     """Static configuration of the unsupervised loss (train_seg_semisup_mask_mt.py CLI flags)."""
 
     def __init__(self, mode='mix', loss_fn='var', conf_thresh=0.97, conf_per_pixel=False, align_corners=True,
-                 invert=True):
+                 invert=True, class_thresh=None):
         if mode not in ('mix', 'cut'):
             raise ValueError('Unknown mask_mode {}'.format(mode))
-        _LossConfig.__init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners)
+        _LossConfig.__init__(self, loss_fn, conf_thresh, conf_per_pixel, align_corners, class_thresh)
         self.mode = mode
         self.invert = bool(invert)
 
@@ -153,6 +241,17 @@ def _cons_desc(cfg, l_stu, l_tea0, l_tea1, ranges, mask, um0, um1, out_size):
     return d
 
 
+def _ct_desc(cfg, d):
+    """the class-threshold descriptor around a consistency descriptor"""
+    ct = cfg.class_thresh
+    if int(d.c) != ct.n_classes:
+        raise ValueError('consistency: logits have {} classes, the class thresholds {}'.format(int(d.c), ct.n_classes))
+    cd = _lib.CthreshDesc()
+    cd.cons = d
+    cd.thr, cd.table = ct.thr.data_ptr(), ct.table.data_ptr()
+    return cd
+
+
 def _workspace(name, d, device):
     """uninitialised scratch of the size cms_<name>_workspace_bytes asks for"""
     return _workspace_bytes(int(fn['cms_{}_workspace_bytes'.format(name)](C.byref(d))), device)
@@ -171,7 +270,9 @@ def _check_grad_out(who, grad_out, like):
 def _finalized_scalars(stats, stats_g, cfg, ramp_val, cons_weight):
     """f32[4] [consistency_loss, conf_rate, grad_scale, unsup_loss] from the loss sums (`stats_g`: those of the global batch)"""
     scalars = torch.empty(4, dtype=torch.float32, device=stats.device)
-    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats_g), cfg.conf_thresh, int(cfg.conf_per_pixel),
+    # (class thresholds are always on: the finalising launch only asks whether its threshold is positive)
+    tau = 1.0 if getattr(cfg, 'class_thresh', None) is not None else cfg.conf_thresh
+    check(fn['cms_consistency_finalize'](_ptr(stats), _ptr(stats_g), tau, int(cfg.conf_per_pixel),
                                          float(ramp_val), float(cons_weight), _ptr(scalars), _stream()),
           'cms_consistency_finalize')
     return scalars
@@ -202,7 +303,7 @@ def _cons_prepare(who, cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, 
 def _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate):
     """the finalised scalars, with the confidence count of the global batch under torch.distributed"""
     stats_g = stats
-    if sync_conf_rate and cfg.conf_thresh > 0.0:
+    if sync_conf_rate and (cfg.conf_thresh > 0.0 or getattr(cfg, 'class_thresh', None) is not None):
         g = stats.clone()
         if _allreduce_sum(g, group):
             stats_g = g
@@ -220,7 +321,11 @@ def consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges=None, mask=
     dev = keep[0].device
     ws = _workspace('consistency', d, dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
-    check(fn['cms_consistency_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_consistency_fwd')
+    if cfg.class_thresh is not None:
+        cd = _ct_desc(cfg, d)
+        check(fn['cms_cthresh_fwd'](C.byref(cd), _ptr(ws), _ptr(stats), _stream()), 'cms_cthresh_fwd')
+    else:
+        check(fn['cms_consistency_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_consistency_fwd')
     return _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate), (d, keep, stats)
 
 
@@ -232,6 +337,11 @@ def consistency_backward(ctx, scalars, grad_out=None, samples=None):
     l_stu = keep[0]
     if grad_out is None:
         grad_out = torch.zeros_like(l_stu)
+    cfg_ = keep[7]
+    if cfg_.class_thresh is not None:
+        bwd = lambda dd, g: check(fn['cms_cthresh_bwd'](C.byref(_ct_desc(cfg_, dd)), _ptr(scalars), _ptr(g), _stream()), 'cms_cthresh_bwd')
+    else:
+        bwd = lambda dd, g: check(fn['cms_consistency_bwd'](C.byref(dd), _ptr(scalars), _ptr(g), _stream()), 'cms_consistency_bwd')
     if samples is not None:
         s0, s1 = int(samples[0]), int(samples[1])
         if not (0 <= s0 < s1 <= int(l_stu.shape[0])):
@@ -239,9 +349,9 @@ def consistency_backward(ctx, scalars, grad_out=None, samples=None):
         sl = lambda t: None if t is None else t[s0:s1]
         l_s, l_t0, l_t1, ranges, mask, um0, um1, cfg, out_size = keep
         d = _cons_desc(cfg, sl(l_s), sl(l_t0), sl(l_t1), sl(ranges), sl(mask), sl(um0), sl(um1), out_size)
-        check(fn['cms_consistency_bwd'](C.byref(d), _ptr(scalars), _ptr(grad_out[s0:s1]), _stream()), 'cms_consistency_bwd')
+        bwd(d, grad_out[s0:s1])
         return grad_out
-    check(fn['cms_consistency_bwd'](C.byref(d), _ptr(scalars), _ptr(grad_out), _stream()), 'cms_consistency_bwd')
+    bwd(d, grad_out)
     return grad_out
 
 
@@ -253,7 +363,9 @@ def consistency_fused(cfg, l_stu, l_tea0, l_tea1, out_size, grad_out, ranges=Non
     the two launches where the fused one does not exist (identity geometry, deterministic mode, CMS_LOSS_FUSED=0)."""
     d, keep = _cons_prepare('consistency_fused', cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1, grad_out)
     l_stu, l_tea0, l_tea1, ranges, mask, um0, um1 = keep[:7]
-    if not fn['cms_consistency_fused_supported'](C.byref(d)):
+    ct = cfg.class_thresh is not None
+    cd = _ct_desc(cfg, d) if ct else None
+    if not (fn['cms_cthresh_fused_supported'](C.byref(cd)) if ct else fn['cms_consistency_fused_supported'](C.byref(d))):
         sc, cctx = consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1, ramp_val, cons_weight, group,
                                        sync_conf_rate)
         consistency_backward(cctx, sc, grad_out)
@@ -263,10 +375,13 @@ def consistency_fused(cfg, l_stu, l_tea0, l_tea1, out_size, grad_out, ranges=Non
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     P = float(d.n) * float(d.H) * float(d.W)
     grad_unit = float(ramp_val) * float(cons_weight) / P
-    check(fn['cms_consistency_fwd_bwd'](C.byref(d), grad_unit, _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()),
-          'cms_consistency_fwd_bwd')
+    if ct:
+        check(fn['cms_cthresh_fwd_bwd'](C.byref(cd), grad_unit, _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()), 'cms_cthresh_fwd_bwd')
+    else:
+        check(fn['cms_consistency_fwd_bwd'](C.byref(d), grad_unit, _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()),
+              'cms_consistency_fwd_bwd')
     scalars = _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate)
-    if cfg.conf_thresh > 0.0 and not cfg.conf_per_pixel:
+    if (ct or cfg.conf_thresh > 0.0) and not cfg.conf_per_pixel:
         # default confidence mode (:415-418): the loss mask is the scalar RATE -- the factor the launch above left out
         check(fn['cms_scale_by_scalar'](_ptr(grad_out), grad_out.numel(), _ptr(scalars), 1, 1.0, _stream()), 'cms_scale_by_scalar')
     return scalars

@@ -37,7 +37,7 @@ class StepConfig(object):
     def __init__(self, mask_mode='mix', cons_loss_fn='var', cons_weight=1.0, conf_thresh=0.97, conf_per_pixel=False,
                  rampup=-1, unsup_batch_ratio=1, invert=True, fuse_batches=True, compute_dtype=torch.bfloat16,
                  overlap_teacher=True, bucketed_allreduce=True, allreduce_dtype='fp32', deterministic=False,
-                 early_optimizer=False):
+                 early_optimizer=False, class_thresh=None):
         if mask_mode not in ('mix', 'zero', 'cut'):
             raise ValueError('Unknown mask_mode {}'.format(mask_mode))
         self.mix = mask_mode == 'mix'
@@ -60,8 +60,12 @@ class StepConfig(object):
         # with the convolutions it overlaps -- so it is off by default
         self.early_optimizer = bool(early_optimizer)
         self.compute_dtype = compute_dtype
+        # per-class confidence thresholds (ops.ClassThresholds) in the place of conf_thresh: the step folds the previous
+        # iteration's statistics at its head, every consistency launch of the iteration adds into them
+        self.class_thresh = class_thresh
         self.cons = ops.ConsistencyConfig(mode='mix' if self.mix else 'cut', loss_fn=cons_loss_fn,
-                                          conf_thresh=conf_thresh, conf_per_pixel=conf_per_pixel, invert=invert)
+                                          conf_thresh=conf_thresh, conf_per_pixel=conf_per_pixel, invert=invert,
+                                          class_thresh=class_thresh)
 
 
 class UnsupBatch(object):
@@ -199,6 +203,9 @@ class CutMixMeanTeacherStep(object):
         self.align_corners = getattr(student_net, 'upsample_align_corners', True)
         cfg.cons.align_corners = self.align_corners
         self.world = world_size(group)
+        if cfg.class_thresh is not None and (self.world > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1):
+            raise RuntimeError('CutMixMeanTeacherStep with class thresholds runs on one GPU: the data-parallel exchange of the '
+                               'threshold statistics is not implemented')
         self._nan_probe = None
         self._nan_event = None
         self._side = None
@@ -578,6 +585,10 @@ class CutMixMeanTeacherStep(object):
         out_size = sup_x.shape[2:4]
         use_unsup = cfg.cons_weight > 0.0 and len(unsup_batches) > 0
         ramp = ramp_val if cfg.rampup > 0 else 1.0
+        if cfg.class_thresh is not None:
+            # one launch on the main stream ahead of every pass (and outside a captured graph, which replays against the same
+            # buffers): the thresholds this iteration applies are made from the iterations before it
+            cfg.class_thresh.update()
 
         independent = self._samples_independent()
         groups = None if (independent or not cfg.fuse_batches) else self._sample_groups(sup_x.shape[0], unsup_batches, use_unsup)

@@ -108,7 +108,7 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
                 num_workers,
                 synthetic=False, synthetic_n_classes=21, synthetic_val_batches=2, compute_dtype='bf16',
                 no_fuse_batches=False, synthetic_source_size='', deterministic=False,
-                allreduce_dtype='fp32', **mask_options):
+                allreduce_dtype='fp32', step_options=None, **mask_options):
     """The body of the mask-driven mean-teacher commands: this one (box masks: CutMix / Cutout) and
     train_seg_semisup_cowmask_mt (CowMix / CowOut). `settings` is what the command prints; `make_mask_generator(prop_range)` -> the
     command's mask_gen.MaskGenerator. A generator with `generate_ranges` sends an int32 box table per batch (rasterised inside the
@@ -116,7 +116,9 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
     takes the materialised mask. A generator that declares `needs_teacher` (mask_gen.ClassMixGenerator) makes its mask from the
     teacher's prediction on image 1, AFTER the unsupervised images are staged: one extra teacher pass under no_grad per
     unsupervised batch, outside the step (`mask_prop_range` is None for such a command: it has no share of ones to draw).
-    `mask_options`: options of the command that only its generator reads."""
+    `mask_options`: options of the command that only its generator reads. `step_options(n_classes, torch_device, world)`, when a
+    command gives one, is called once the class count and the device are known -> (further StepConfig keywords, the command's
+    `after_epoch(epoch_i)` hook or None) (train_seg_semisup_classthresh_mt)."""
     if mask_prop_range is None:
         pass
     elif ':' in mask_prop_range:
@@ -164,11 +166,12 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
         optimizer=student_optim, total_iters=iters_per_epoch * num_epochs, schedule_type=lr_sched, step_epochs=lr_step_epochs,
         step_gamma=lr_step_gamma, poly_power=lr_poly_power)
 
+    step_extra, after_epoch = step_options(n_classes, torch_device, world) if step_options is not None else ({}, None)
     step_cfg = StepConfig(mask_mode=mask_mode, cons_loss_fn=cons_loss_fn, cons_weight=cons_weight,
                           conf_thresh=conf_thresh, conf_per_pixel=conf_per_pixel, rampup=rampup,
                           unsup_batch_ratio=unsup_batch_ratio, invert=invert,
                           fuse_batches=not no_fuse_batches, compute_dtype=dtype,
-                          deterministic=deterministic, allreduce_dtype=allreduce_dtype)
+                          deterministic=deterministic, allreduce_dtype=allreduce_dtype, **step_extra)
     step = CutMixMeanTeacherStep(student_net, teacher_net, student_optim, teacher_optim, step_cfg)
 
     # synthetic data: N(0,1) images, uniform labels with 5 % ignore, all-ones validity masks
@@ -275,7 +278,7 @@ def mask_mt_job(job_name, submit_config, settings, make_mask_generator, invert, 
     if not tc.run_epochs(step, make_batch, evaluate, student_net, teacher_net, eval_net, schedulers, num_epochs,
                          iters_per_epoch, freeze_bn, rampup, conf_thresh, n_classes, bin_fill_holes, torch_device,
                          data_parallel=True, rank=rank, nan_checks_consistency=nan_checks_consistency, polls_step_nan=polls_step_nan,
-                         img_per_s_of=(batch_size, world)):
+                         img_per_s_of=(batch_size, world), after_epoch=after_epoch):
         return
 
     # inherited, not chosen: the whole module through checkpoint.save_model (the VAT trainer writes a state_dict)

@@ -132,6 +132,50 @@ int cms_consistency_fwd_bwd(const cms_consistency_desc* d, float grad_unit, void
 int cms_scale_by_scalar(float* x, long long n, const float* scalars, int index, float factor, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Class-threshold consistency: the masked consistency loss above with a per-class confidence threshold, and the
+ * statistics a self-adaptive threshold (FreeMatch, Wang et al., ICLR 2023) is made from riding in the loss launch.
+ * The project's own definition. For a pixel of a call, with t its pasted, bilinearly upsampled teacher logit row:
+ *   m = max t, z = sum_k exp(t_k - m), conf = 1 / z   (the very float compared with conf_thresh above)
+ *   k*  = the smallest index with t_k == m;   q_c = exp(t_c - m) / z
+ *   pass bit = conf >= thr[k*] in fp32 (a NaN fails). It takes the place of `conf >= conf_thresh` everywhere: in the
+ *   count behind the rate of the default mode (sum of bits / P over all pixels) and as the factor of conf_per_pixel.
+ *   cons.conf_thresh is not read: the threshold is always on. Loss sums, cms_consistency_finalize (call it with any
+ *   conf_thresh > 0), cms_scale_by_scalar and the deferred-rate contract of cms_consistency_fwd_bwd are unchanged.
+ *   valid pixel (statistics only): mix -- the validity map of the image the mask selects is >= 0.5; cut -- um0 >= 0.5
+ *   whatever the mask bit (the prediction is image 0's everywhere); a missing map is all valid.
+ * cms_cthresh_fwd and cms_cthresh_fwd_bwd ADD into `table`, unsigned 64-bit integers (no sum depends on the order of
+ * additions, or on how a batch is split into calls). The buffer holds CMS_CTHRESH_REPLICAS copies of the layout below, one
+ * after the other; a workgroup adds into copy (its index mod CMS_CTHRESH_REPLICAS), so that the workgroups of a launch do not
+ * all queue at the same 2 + 3C addresses, and THE table is the sum of the copies (cms_cthresh_update reads it so):
+ *   table[0] = n_valid, table[1] = S_conf = sum_valid rint(conf * 2^24), table[2 + c] = S_c = sum_valid rint(q_c * 2^24),
+ *   table[2 + C + c] = N_pred[c] = valid pixels with k* == c, table[2 + 2C + c] = N_pass[c] = those of them that pass.
+ *   (A NaN contributes 0 to S_conf / S_c.) cms_cthresh_bwd reads thr only. At most 128 classes.
+ * Geometry routes, workspace, stats_out, scalars, grad_unit and error codes are those of the cms_consistency_* twins.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define CMS_CTHRESH_REPLICAS 32
+typedef struct cms_cthresh_desc {
+    cms_consistency_desc cons;      /* as above; conf_thresh is not read                                      */
+    const float* thr;               /* f32[C] per-class thresholds (device)                                   */
+    unsigned long long* table;      /* u64[CMS_CTHRESH_REPLICAS][2 + 3C] statistics of the iteration (device), added into */
+} cms_cthresh_desc;
+size_t cms_cthresh_workspace_bytes(const cms_cthresh_desc* d);
+int cms_cthresh_fused_supported(const cms_cthresh_desc* d);
+int cms_cthresh_fwd(const cms_cthresh_desc* d, void* workspace, double* stats_out, void* stream);
+int cms_cthresh_bwd(const cms_cthresh_desc* d, const float* scalars, float* grad_l_stu, void* stream);
+int cms_cthresh_fwd_bwd(const cms_cthresh_desc* d, float grad_unit, void* workspace, double* stats_out, float* grad_l_stu,
+                        void* stream);
+/* One launch, one thread, fp64: folds the iteration's table. state = f64[1 + C] = { tau, p~_c }; epoch = u64[1 + 2C] =
+ * { n_valid, N_pred[c], N_pass[c] }. adaptive != 0 and n_valid > 0:
+ *   mu = S_conf / (2^24 n_valid), pi_c = S_c / (2^24 n_valid); tau <- ema tau + (1 - ema) mu; p~_c <- ema p~_c + (1 - ema) pi_c;
+ *   thr_c = fp32(min(ceil, max(floor, tau * p~_c / max_j p~_j))).
+ * Always: n_valid, N_pred and N_pass are added into `epoch` and the table (every copy) is zeroed. The caller starts from
+ * tau = p~_c = 1 / C and thr_c = clamp(1 / C), and runs this ahead of an iteration's loss launches: the thresholds an
+ * iteration applies are made from the iterations before it (one iteration behind the paper's update-then-mask, so that
+ * the sums ride in the loss launch and thr is constant within a step). The paper's fairness loss is not built. */
+int cms_cthresh_update(int n_classes, int adaptive, double ema, double floor_v, double ceil_v, double* state, float* thr,
+                       unsigned long long* table, unsigned long long* epoch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Supervised cross entropy, fused: bilinear upsample + log-softmax + NLL(ignore_index)
  *                               (nn.CrossEntropyLoss(ignore_index=255), train_seg_semisup_mask_mt.py:126, 299-301)
  * ------------------------------------------------------------------------------------------------------------ */
