@@ -1,6 +1,6 @@
-// What the kernels of the masked consistency loss share between losses.hip (one scalar threshold) and cthresh.hip (per-class
-// thresholds): the kernel argument block, the per-pixel inputs (mask bit, validity, which teacher) and the staging of a tile's
-// logit rectangles. Moved here from losses.hip unchanged.
+// What the kernels of the masked consistency loss (cons_kernels.hpp: one body for the scalar threshold of losses.hip and the
+// per-class thresholds of cthresh.hip) are built on: the kernel argument block, the per-pixel inputs (mask bit, validity, which
+// teacher) and the staging of a tile's logit rectangles.
 #pragma once
 #include "loss_tiles.hpp"
 

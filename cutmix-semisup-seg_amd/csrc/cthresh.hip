@@ -2,17 +2,16 @@
 // by a per-class one, thr[argmax of the teacher row], and -- in the forward and the fused launch -- the statistics a self-adaptive
 // threshold is made from, summed over the launch's valid pixels as exact integers (definition: include/cutmixseg.h).
 //
-// The per-pixel loss, confidence and gradient are those of losses.hip: the same functions of pixel_math.hpp on the same values in
-// the same order, on the same tile walks, launch paths and reductions of loss_tiles.hpp; with thr == tau in every entry the loss
-// sums are bit for bit those of cms_consistency_*. What this file adds per pixel is an argmax over the teacher row (registers),
-// one LDS read of thr[k*] and the statistics:
+// The kernels and their launches are those of losses.hip -- ONE body, the templates of cons_kernels.hpp, instantiated here with the
+// policy `ClassThresh` below; with thr == tau in every entry the loss sums are bit for bit those of cms_consistency_*. What the
+// policy adds per pixel is an argmax over the teacher row (registers), one LDS read of thr[k*] and the statistics:
 //   * S_c / S_conf / n_valid: per-thread 32-bit partials (compile-time class counts) -> one integer wave reduction at the end of
 //     the kernel -> one 64-bit LDS add per wave -> one 64-bit global atomic add per slot per workgroup, into one of
 //     CMS_CTHRESH_REPLICAS copies of the table. Integer sums do not depend on the order of additions, so neither does the table.
 //   * N_pred[k*] / N_pass[k*]: LDS integer atomics per pixel, as csrc/calib.hip counts its bins.
 //   * the run-time class count has no register array: its S_c go to the LDS table per pixel (LDS atomics, never global ones).
 // No float atomics and no per-pixel global atomics anywhere.
-#include "cons_args.hpp"
+#include "cons_kernels.hpp"
 #include "cthresh_math.hpp"
 
 namespace cms {
@@ -149,206 +148,68 @@ __device__ __forceinline__ void ct_finish(const CtArgs& a, CtShared<CT>& sh, CtA
     }
 }
 
-// one pixel of a forward kernel from its two gathers: the three loss sums (cons_fwd_pixel of losses.hip) and the statistics
-template <int CT, bool IDENT>
-__device__ __forceinline__ void ct_fwd_pixel(const CtArgs& a, CtShared<CT>& sh, CtAcc<CT>& sacc, const ConsPixel& px, bool valid,
-                                             const Gather<IDENT>& gs, const Gather<IDENT>& gt, float (&acc)[3]) {
-    const Geo& g = a.g;
-    PixelFwd r;
+// ------------------------------------------------------------------------------------------------ the threshold policy
+// What cons_kernels.hpp asks of a policy. The threshold of a pixel is thr[k*], read from LDS.
+struct CtPick {
     int k;
-    bool pass;
-    if (CT > 0) {
-        RegVec<CT> rs, rt;
-        fill<CT, IDENT>(rs, gs);
-        fill<CT, IDENT>(rt, gt);
-        r = consistency_pixel_fwd<CT>(rs, rt, g.c, a.d.loss_fn, a.inv_root_c);
-        k = ct_kstar<CT>(rt, g.c);
-        pass = ct_pass(r.conf, sh.thr[k]);
-        ct_count<CT>(a, sh, sacc, rt, k, pass, valid);
-    } else {
-        r = consistency_pixel_fwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c);
-        k = ct_kstar<0>(gt, g.c);
-        pass = ct_pass(r.conf, sh.thr[k]);
-        ct_count<CT>(a, sh, sacc, gt, k, pass, valid);
-    }
-    const float lm = r.loss * px.um;
-    const float cf = pass ? 1.0f : 0.0f;
-    acc[0] += lm;
-    acc[1] += lm * cf;
-    acc[2] += cf;
-}
+    float thr;
+    __device__ __forceinline__ bool passes(float conf) const { return ct_pass(conf, thr); }
+};
 
-template <int CT>
-__global__ __launch_bounds__(256) void ct_fwd_tiled_kernel(CtArgs a, float* __restrict__ partials, int patch_stride) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ CtShared<CT> sh;
-    static_assert(FWD_TILE_H / 4 <= 2, "ct_finish: 32-bit wave sums hold two pixels per thread");
-    ct_begin<CT>(a, sh);
-    CtAcc<CT> sacc;
-    ct_acc_zero(sacc);
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    fwd_tile_walk<false>(
-        a.g, smem, [&](int n, const Patch& p, float* P) { cons_stage(a, n, p, P, patch_stride); },
-        [&](int n, int y, int x, const Tap& ty, const Tap& tx, const Patch& p) {
-            const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-            const Gather<false> gs = gather_staged(smem, p, ty, tx);
-            const Gather<false> gt = gather_staged(smem + (px.which ? 2 : 1) * patch_stride, p, ty, tx);
-            ct_fwd_pixel<CT, false>(a, sh, sacc, px, ct_valid(a, px, n, y, x), gs, gt, acc);
-        });
-    __shared__ float red[3 * 16];
-    store_partials<3>(acc, red, partials);
-    ct_finish<CT, true>(a, sh, sacc);
-}
+struct ClassThresh {
+    using Args = CtArgs;
+    static __device__ __forceinline__ bool on(const CtArgs&) { return true; }      // class thresholds are always on
 
-template <int CT, bool IDENT>
-__global__ __launch_bounds__(256) void ct_fwd_kernel(CtArgs a, float* __restrict__ partials) {
-    const Geo& g = a.g;
-    __shared__ CtShared<CT> sh;
-    ct_begin<CT>(a, sh);
-    CtAcc<CT> sacc;
-    ct_acc_zero(sacc);
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    pixel_walk(g, [&](size_t, int n, int y, int x) {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const Gather<IDENT> gs = gather_at<IDENT>(a.d.l_stu + (size_t)n * g.c * ((size_t)g.h * g.w), g, y, x);
-        Gather<IDENT> gt = gs;
-        gt.base = px.tea;
-        ct_fwd_pixel<CT, IDENT>(a, sh, sacc, px, ct_valid(a, px, n, y, x), gs, gt, acc);
-        if (sacc.nvalid >= CT_FLUSH) ct_flush<CT>(a, sh, sacc);
-    });
-    __shared__ float red[3 * 16];
-    store_partials<3>(acc, red, partials);
-    ct_finish<CT, false>(a, sh, sacc);
-}
-
-// ---- backward, identity geometry (cons_bwd_ident_kernel with thr[k*] in the place of tau)
-template <int CT>
-__global__ __launch_bounds__(256) void ct_bwd_ident_kernel(CtArgs a, const float* __restrict__ scalars, float* __restrict__ grad) {
-    const Geo& g = a.g;
-    __shared__ CtThr<CT> sh;
-    ct_begin_thr<CT>(a, sh);
-    const size_t plane = (size_t)g.h * g.w;
-    const float gscale = scalars[2];
-    const bool pp = a.d.conf_per_pixel != 0;
-    pixel_walk(g, [&](size_t, int n, int y, int x) {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const Gather<true> gs = gather_at<true>(a.d.l_stu + (size_t)n * g.c * plane, g, y, x);
-        Gather<true> gt = gs;
-        gt.base = px.tea;
-        float* gp = grad + (size_t)n * g.c * plane + gs.off;
-        const float base_f = gscale * px.um;
-        if (CT > 0) {
-            RegVec<CT> rs, rt;
-            fill<CT, true>(rs, gs);
-            fill<CT, true>(rt, gt);
-            float gv[CT > 0 ? CT : 1];
-            const float conf = consistency_pixel_bwd<CT>(rs, rt, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { gv[k] = v; });
-            const float f = (pp && !ct_pass(conf, sh.thr[ct_kstar<CT>(rt, g.c)])) ? 0.0f : base_f;
-#pragma unroll
-            for (int k = 0; k < CT; ++k) gp[k * plane] += f * gv[k];
-        } else {
-            float mt, zt;
-            softmax_stats<0>(gt, g.c, mt, zt);
-            const float conf = 1.0f / zt;
-            const float f = (pp && !ct_pass(conf, sh.thr[ct_argmax<0>(gt, g.c, mt)])) ? 0.0f : base_f;
-            consistency_pixel_bwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { gp[k * plane] += f * v; });
+    // forward and fused kernels: thr[] and the table in the static LDS of this state, the partials in registers
+    template <int CT, bool PPT2>
+    struct Fwd {
+        static_assert(!PPT2 || (FWD_TILE_H / 4 <= 2 && TILE_H / 4 <= 2), "ct_finish: 32-bit wave sums hold two pixels per thread");
+        CtAcc<CT> acc;
+        static __device__ __forceinline__ CtShared<CT>& sh() {
+            __shared__ CtShared<CT> s;
+            return s;
         }
-    });
-}
-
-// ---- backward with upsampling (cons_bwd_tiled_kernel)
-template <int CT>
-__global__ __launch_bounds__(256) void ct_bwd_tiled_kernel(CtArgs a, const float* __restrict__ scalars, float* __restrict__ grad,
-                                                           int patch_stride) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ CtThr<CT> sh;
-    ct_begin_thr<CT>(a, sh);
-    const Geo& g = a.g;
-    const float gscale = scalars[2];
-    const bool pp = a.d.conf_per_pixel != 0;
-    const int pstride = patch_stride;
-    auto stage = [&](int n, const Patch& p, float* P) { cons_stage(a, n, p, P, pstride); };
-    auto pixel_grad = [&](int n, int y, int x, const Tap& ty, const Tap& tx, const Patch& p, const float* P, auto emit) -> bool {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const float base_f = gscale * px.um;
-        const Gather<false> gs = gather_staged(P, p, ty, tx);
-        const Gather<false> gt = gather_staged(P + (px.which ? 2 * pstride : pstride), p, ty, tx);
-        if (CT > 0) {
-            RegVec<CT> rs, rt;
-            fill<CT, false>(rs, gs);
-            fill<CT, false>(rt, gt);
-            float gv[CT > 0 ? CT : 1];
-            const float conf = consistency_pixel_bwd<CT>(rs, rt, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { gv[k] = v; });
-            const float f = (pp && !ct_pass(conf, sh.thr[ct_kstar<CT>(rt, g.c)])) ? 0.0f : base_f;
-#pragma unroll
-            for (int k = 0; k < CT; ++k) emit(k, f * gv[k]);
-        } else {
-            float mt, zt;
-            softmax_stats<0>(gt, g.c, mt, zt);
-            const float conf = 1.0f / zt;
-            const float f = (pp && !ct_pass(conf, sh.thr[ct_argmax<0>(gt, g.c, mt)])) ? 0.0f : base_f;
-            consistency_pixel_bwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { emit(k, f * v); });
+        __device__ __forceinline__ explicit Fwd(const CtArgs& a) {
+            ct_begin<CT>(a, sh());
+            ct_acc_zero(acc);
         }
-        return true;
+        __device__ __forceinline__ bool valid(const CtArgs& a, const ConsPixel& px, int n, int y, int x) const { return ct_valid(a, px, n, y, x); }
+        template <class LT>
+        __device__ __forceinline__ CtPick pick(const CtArgs& a, const LT& lt) const {
+            const int k = ct_kstar<CT>(lt, a.g.c);
+            return CtPick{k, sh().thr[k]};
+        }
+        template <class LT>
+        __device__ __forceinline__ void count(const CtArgs& a, const LT& lt, const CtPick& t, bool pass, bool valid) {
+            ct_count<CT>(a, sh(), acc, lt, t.k, pass, valid);
+        }
+        // (the flat walk, whose threads see any number of pixels)
+        __device__ __forceinline__ void pixel_done(const CtArgs& a) {
+            if (acc.nvalid >= CT_FLUSH) ct_flush<CT>(a, sh(), acc);
+        }
+        __device__ __forceinline__ void finish(const CtArgs& a) { ct_finish<CT, PPT2>(a, sh(), acc); }
     };
-    tiled_scatter(g, stage, pixel_grad, grad, smem);
-}
 
-// ---- forward + backward in ONE launch (cons_fused_tiled_kernel) with the statistics riding in it
-template <int CT, int LF>
-__global__ __launch_bounds__(256, (LF >= 0 && CT > 0) ? 4 : 1) void ct_fused_tiled_kernel(CtArgs a, float grad_unit, float* __restrict__ grad,
-                                                                                          int patch_stride, float* __restrict__ partials) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ CtShared<CT> sh;
-    static_assert(TILE_H / 4 <= 2, "ct_finish: 32-bit wave sums hold two pixels per thread");
-    ct_begin<CT>(a, sh);
-    CtAcc<CT> sacc;
-    ct_acc_zero(sacc);
-    const Geo& g = a.g;
-    const bool pp = a.d.conf_per_pixel != 0;
-    const int pstride = patch_stride;
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    auto stage = [&](int n, const Patch& p, float* P) { cons_stage(a, n, p, P, pstride); };
-    auto pixel_grad = [&](int n, int y, int x, const Tap& ty, const Tap& tx, const Patch& p, const float* P, auto emit) -> bool {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const bool valid = ct_valid(a, px, n, y, x);
-        const float base_f = grad_unit * px.um;
-        const Gather<false> gs = gather_staged(P, p, ty, tx);
-        const Gather<false> gt = gather_staged(P + (px.which ? 2 * pstride : pstride), p, ty, tx);
-        PixelFwd r;
-        bool pass;
-        if (CT > 0) {
-            RegVec<CT> rs, rt;
-            fill<CT, false>(rs, gs);
-            fill<CT, false>(rt, gt);
-            const int k = ct_kstar<CT>(rt, g.c);
-            const float thr_k = sh.thr[k];
-            r = consistency_pixel_fwd_bwd<(CT > 0 ? CT : 1), LF>(
-                rs, rt, a.d.loss_fn, a.inv_root_c,
-                [&](float conf) -> float { return (pp && !ct_pass(conf, thr_k)) ? 0.0f : base_f; },
-                [&](int c, float v) { emit(c, v); });
-            pass = ct_pass(r.conf, thr_k);
-            ct_count<CT>(a, sh, sacc, rt, k, pass, valid);
-        } else {
-            r = consistency_pixel_fwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c);
-            const int k = ct_kstar<0>(gt, g.c);
-            pass = ct_pass(r.conf, sh.thr[k]);
-            const float f = (pp && !pass) ? 0.0f : base_f;
-            consistency_pixel_bwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c, [&](int c, float v) { emit(c, f * v); });
-            ct_count<CT>(a, sh, sacc, gt, k, pass, valid);
+    // backward kernels: thr[] alone; k* of the run-time class count by ct_argmax from the maximum the kernel has computed
+    template <int CT>
+    struct Bwd {
+        static __device__ __forceinline__ CtThr<CT>& sh() {
+            __shared__ CtThr<CT> s;
+            return s;
         }
-        const float lm = r.loss * px.um;
-        const float cf = pass ? 1.0f : 0.0f;
-        acc[0] += lm;
-        acc[1] += lm * cf;
-        acc[2] += cf;
-        return true;
+        __device__ __forceinline__ explicit Bwd(const CtArgs& a) { ct_begin_thr<CT>(a, sh()); }
+        template <class LT>
+        __device__ __forceinline__ CtPick pick(const CtArgs& a, const LT& lt) const {
+            const int k = ct_kstar<CT>(lt, a.g.c);
+            return CtPick{k, sh().thr[k]};
+        }
+        template <class LT>
+        __device__ __forceinline__ CtPick pick_max(const CtArgs& a, const LT& lt, float mx) const {
+            const int k = ct_argmax<CT>(lt, a.g.c, mx);
+            return CtPick{k, sh().thr[k]};
+        }
     };
-    tiled_scatter(g, stage, pixel_grad, grad, smem);
-    __shared__ float red[3 * 16];
-    store_partials<3>(acc, red, partials);
-    ct_finish<CT, true>(a, sh, sacc);
-}
+};
 
 __global__ void ct_update_kernel(int C, int adaptive, double lam, double floor_v, double ceil_v, double* __restrict__ state,
                                  float* __restrict__ thr, unsigned long long* __restrict__ table, unsigned long long* __restrict__ epoch) {
@@ -402,7 +263,7 @@ static size_t ct_fused_static_lds() {
     static size_t known = 0;
     if (known == 0) {
         hipFuncAttributes attr;
-        if (hipFuncGetAttributes(&attr, (const void*)ct_fused_tiled_kernel<CT, LF>) != hipSuccess) {
+        if (hipFuncGetAttributes(&attr, (const void*)cons_fused_tiled_kernel<ClassThresh, CT, LF>) != hipSuccess) {
             (void)hipGetLastError();
             return 0;
         }
@@ -432,10 +293,7 @@ extern "C" int cms_cthresh_fwd(const cms_cthresh_desc* d, void* workspace, doubl
     int rc = check_ct(d);
     if (rc) return rc;
     CMS_REQUIRE(workspace && stats_out, "cthresh_fwd: workspace / stats_out NULL");
-    const CtArgs a = make_ct_args(d);
-    const FwdPlan p = fwd_plan(a.g, 3);
-    CMS_DISPATCH_C(a.g.c, launch_fwd<3>(ct_fwd_tiled_kernel<CT>, ct_fwd_kernel<CT, true>, ct_fwd_kernel<CT, false>, a, p, (float*)workspace,
-                                        stats_out, (double)((size_t)a.g.n * a.g.H * a.g.W), 3, (hipStream_t)stream, p.pstride));
+    cons_launch_fwd<ClassThresh>(make_ct_args(d), (float*)workspace, stats_out, (hipStream_t)stream);
     return launch_status("cms_cthresh_fwd");
 }
 
@@ -443,10 +301,7 @@ extern "C" int cms_cthresh_bwd(const cms_cthresh_desc* d, const float* scalars, 
     int rc = check_ct(d);
     if (rc) return rc;
     CMS_REQUIRE(scalars && grad_l_stu, "cthresh_bwd: scalars / grad NULL");
-    const CtArgs a = make_ct_args(d);
-    const int pstride = (int)patch_floats(a.g.c, a.g.sy, a.g.sx, TILE_H);
-    CMS_DISPATCH_C(a.g.c, rc = launch_bwd("cthresh_bwd", ct_bwd_ident_kernel<CT>, ct_bwd_tiled_kernel<CT>, a, 3, 0, scalars, grad_l_stu,
-                                          (hipStream_t)stream, pstride));
+    rc = cons_launch_bwd<ClassThresh>("cthresh_bwd", make_ct_args(d), scalars, grad_l_stu, (hipStream_t)stream);
     return rc ? rc : launch_status("cms_cthresh_bwd");
 }
 
@@ -458,16 +313,7 @@ extern "C" int cms_cthresh_fwd_bwd(const cms_cthresh_desc* d, float grad_unit, v
     const CtArgs a = make_ct_args(d);
     const int tiles = ct_fused_tiles(a);
     CMS_REQUIRE(tiles > 0, "cthresh_fwd_bwd: not available for this geometry / mode (ask cms_cthresh_fused_supported)");
-    hipStream_t s = (hipStream_t)stream;
-    const int pstride = (int)patch_floats(a.g.c, a.g.sy, a.g.sx, TILE_H);
-    const size_t lds = tile_lds_bytes(a.g.c, a.g.sy, a.g.sx, 3);
-    const double P = (double)((size_t)a.g.n * a.g.H * a.g.W);
-    CMS_DISPATCH_C(a.g.c, {
-        auto kern = a.d.loss_fn == CMS_LOSS_VAR ? ct_fused_tiled_kernel<CT, LOSS_VAR> : ct_fused_tiled_kernel<CT, -1>;
-        allow_lds(kern, lds);
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), lds, s, a, grad_unit, grad_l_stu, pstride, (float*)workspace);
-        hipLaunchKernelGGL((reduce_partials_kernel<3>), dim3(1), dim3(256), 0, s, (const float*)workspace, tiles, stats_out, P, 3);
-    });
+    cons_launch_fused<ClassThresh>(a, tiles, grad_unit, (float*)workspace, stats_out, grad_l_stu, (hipStream_t)stream);
     return launch_status("cms_cthresh_fwd_bwd");
 }
 

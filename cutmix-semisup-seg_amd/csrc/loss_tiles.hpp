@@ -1,7 +1,7 @@
 // The skeleton every loss family of the library shares (gfx950): consistency and cross entropy (losses.hip), ICT (ict.hip) and the
 // augmentation consistency (aug_loss.hip). Device side: the accessors of a pixel's class vector, the LDS-staged low-resolution
 // rectangles, the forward tile walk, the flat pixel walk, the tiled adjoint of the bilinear upsample and the two-stage reduction
-// of the loss sums. Host side: the geometry, its checks, and ONE launch path each for the forward and the backward kernels. A
+// of the loss sums. Host side: the geometry, its checks, and ONE launch path each for the forward, the backward and the fused kernels. A
 // family supplies its per-pixel arithmetic (the *_math.hpp headers) as lambdas and its kernels as thin shells.
 #pragma once
 #include <algorithm>
@@ -572,6 +572,16 @@ inline int launch_bwd(const char* what, Ident ident, Tiled tiled, const Args& a,
         hipLaunchKernelGGL(tiled, dim3(tiles), dim3(256), lds, s, ac, scalars, grad, tiled_extra...);
     });
     return CMS_OK;
+}
+
+// The one-launch forward + backward of a family over `tiles` tiles (`args`: what its kernel takes in front of the partials), and the
+// reduction of its K partial sums.
+template <int K, class Kern, class... Args>
+inline void launch_fused(Kern kern, int tiles, size_t lds, hipStream_t s, float* partials, double* stats_out, double extra, int extra_slot,
+                         Args... args) {
+    allow_lds(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), lds, s, args..., partials);
+    hipLaunchKernelGGL((reduce_partials_kernel<K>), dim3(1), dim3(256), 0, s, partials, tiles, stats_out, extra, extra_slot);
 }
 
 }  // namespace cms

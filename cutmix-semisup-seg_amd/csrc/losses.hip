@@ -16,64 +16,15 @@
 // issued per low-res cell per tile instead of per pixel per tap.
 //
 // The tile walks, the tiled adjoint and the launch paths are csrc/loss_tiles.hpp, shared with the ICT loss (ict.hip) and the
-// augmentation consistency (aug_loss.hip); this file also holds the one definition of the switch state they read.
-#include "cons_args.hpp"
+// augmentation consistency (aug_loss.hip); this file also holds the one definition of the switch state they read. The
+// consistency kernels and their launches are the templates of csrc/cons_kernels.hpp, instantiated here with the scalar threshold
+// (TauThresh) and in cthresh.hip with per-class thresholds: one body for both.
+#include "cons_kernels.hpp"
 
 namespace cms {
 
 // ------------------------------------------------------------------------------------------------ consistency
-// one pixel of a forward kernel from its two gathers: the three loss sums
-template <int CT, bool IDENT>
-__device__ __forceinline__ void cons_fwd_pixel(const ConsArgs& a, const ConsPixel& px, const Gather<IDENT>& gs, const Gather<IDENT>& gt,
-                                               float (&acc)[3]) {
-    const Geo& g = a.g;
-    PixelFwd r;
-    if (CT > 0) {
-        RegVec<CT> rs, rt;
-        fill<CT, IDENT>(rs, gs);
-        fill<CT, IDENT>(rt, gt);
-        r = consistency_pixel_fwd<CT>(rs, rt, g.c, a.d.loss_fn, a.inv_root_c);
-    } else {
-        r = consistency_pixel_fwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c);
-    }
-    const float lm = r.loss * px.um;
-    const float cf = (a.tau > 0.0f && r.conf >= a.tau) ? 1.0f : 0.0f;
-    acc[0] += lm;
-    acc[1] += lm * cf;
-    acc[2] += cf;
-}
-
-template <int CT>
-__global__ __launch_bounds__(256) void cons_fwd_tiled_kernel(ConsArgs a, float* __restrict__ partials, int patch_stride) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    fwd_tile_walk<false>(
-        a.g, smem, [&](int n, const Patch& p, float* P) { cons_stage(a, n, p, P, patch_stride); },
-        [&](int n, int y, int x, const Tap& ty, const Tap& tx, const Patch& p) {
-            const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-            const Gather<false> gs = gather_staged(smem, p, ty, tx);
-            const Gather<false> gt = gather_staged(smem + (px.which ? 2 : 1) * patch_stride, p, ty, tx);
-            cons_fwd_pixel<CT, false>(a, px, gs, gt, acc);
-        });
-    __shared__ float red[3 * 16];
-    store_partials<3>(acc, red, partials);
-}
-
-template <int CT, bool IDENT>
-__global__ __launch_bounds__(256) void cons_fwd_kernel(ConsArgs a, float* __restrict__ partials) {
-    const Geo& g = a.g;
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    pixel_walk(g, [&](size_t, int n, int y, int x) {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const Gather<IDENT> gs = gather_at<IDENT>(a.d.l_stu + (size_t)n * g.c * ((size_t)g.h * g.w), g, y, x);
-        Gather<IDENT> gt = gs;
-        gt.base = px.tea;
-        cons_fwd_pixel<CT, IDENT>(a, px, gs, gt, acc);
-    });
-    __shared__ float red[3 * 16];
-    store_partials<3>(acc, red, partials);
-}
-
+// (the forward, backward and fused kernels: cons_kernels.hpp)
 __global__ void cons_finalize_kernel(const double* __restrict__ sl, const double* __restrict__ sg, float tau,
                                      int per_pixel, float ramp, float weight, float* __restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -99,135 +50,6 @@ __global__ void cons_finalize_kernel(const double* __restrict__ sl, const double
     out[1] = (float)rate;                       // :413
     out[2] = (float)(gs * (double)ramp * (double)weight);
     out[3] = (float)(closs * (double)weight);   // :458
-}
-
-// ---- backward, identity geometry (h == H, w == W): gradients land directly on their own pixel
-template <int CT>
-__global__ __launch_bounds__(256) void cons_bwd_ident_kernel(ConsArgs a, const float* __restrict__ scalars,
-                                                             float* __restrict__ grad) {
-    const Geo& g = a.g;
-    const size_t plane = (size_t)g.h * g.w;
-    const float gscale = scalars[2];
-    pixel_walk(g, [&](size_t, int n, int y, int x) {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const Gather<true> gs = gather_at<true>(a.d.l_stu + (size_t)n * g.c * plane, g, y, x);
-        Gather<true> gt = gs;
-        gt.base = px.tea;
-        float* gp = grad + (size_t)n * g.c * plane + gs.off;
-        const float base_f = gscale * px.um;
-        const bool pp = a.tau > 0.0f && a.d.conf_per_pixel;
-        // no early-out on base_f == 0 (confidence rate 0 at random init, invalid pixels): the masked-consistency
-        // backward always does its full work, SURVEY.md 8(d) -- a zero factor simply contributes zeros
-        if (CT > 0) {
-            RegVec<CT> rs, rt;
-            fill<CT, true>(rs, gs);
-            fill<CT, true>(rt, gt);
-            float gv[CT > 0 ? CT : 1];
-            const float conf = consistency_pixel_bwd<CT>(rs, rt, g.c, a.d.loss_fn, a.inv_root_c,
-                                                        [&](int k, float v) { gv[k] = v; });
-            const float f = (pp && !(conf >= a.tau)) ? 0.0f : base_f;
-#pragma unroll
-            for (int k = 0; k < CT; ++k) gp[k * plane] += f * gv[k];
-        } else {
-            float ms, zs, mt, zt;
-            softmax_stats<0>(gt, g.c, mt, zt);
-            (void)ms; (void)zs;
-            const float conf = 1.0f / zt;
-            const float f = (pp && !(conf >= a.tau)) ? 0.0f : base_f;
-            consistency_pixel_bwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c,
-                                     [&](int k, float v) { gp[k * plane] += f * v; });
-        }
-    });
-}
-
-// ---- backward with upsampling: the LDS-tiled adjoint of the bilinear interpolation, tiled_scatter (loss_tiles.hpp)
-template <int CT>
-__global__ __launch_bounds__(256) void cons_bwd_tiled_kernel(ConsArgs a, const float* __restrict__ scalars,
-                                                             float* __restrict__ grad, int patch_stride) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const Geo& g = a.g;
-    const float gscale = scalars[2];
-    const bool pp = a.tau > 0.0f && a.d.conf_per_pixel;
-    // LDS copies of the tile's logit rectangles: student | teacher 0 | teacher 1, `pstride` floats apart
-    const int pstride = patch_stride;
-    auto stage = [&](int n, const Patch& p, float* P) { cons_stage(a, n, p, P, pstride); };
-    auto pixel_grad = [&](int n, int y, int x, const Tap& ty, const Tap& tx, const Patch& p, const float* P, auto emit) -> bool {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const float base_f = gscale * px.um;
-        // (no early-out on base_f == 0, see cons_bwd_ident_kernel)
-        const Gather<false> gs = gather_staged(P, p, ty, tx);       // (taps already rebased to the rectangle)
-        const Gather<false> gt = gather_staged(P + (px.which ? 2 * pstride : pstride), p, ty, tx);
-        if (CT > 0) {
-            RegVec<CT> rs, rt;
-            fill<CT, false>(rs, gs);
-            fill<CT, false>(rt, gt);
-            float gv[CT > 0 ? CT : 1];
-            const float conf = consistency_pixel_bwd<CT>(rs, rt, g.c, a.d.loss_fn, a.inv_root_c,
-                                                        [&](int k, float v) { gv[k] = v; });
-            const float f = (pp && !(conf >= a.tau)) ? 0.0f : base_f;
-#pragma unroll
-            for (int k = 0; k < CT; ++k) emit(k, f * gv[k]);
-        } else {
-            float mt, zt;
-            softmax_stats<0>(gt, g.c, mt, zt);
-            const float conf = 1.0f / zt;
-            const float f = (pp && !(conf >= a.tau)) ? 0.0f : base_f;
-            consistency_pixel_bwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { emit(k, f * v); });
-        }
-        return true;
-    };
-    tiled_scatter(g, stage, pixel_grad, grad, smem);
-}
-
-// ---- forward + backward in ONE launch (round 6) -----------------------------------------------------------------------
-// The backward kernel recomputes everything the forward kernel computed (the tile's logit rectangles, both softmaxes of every
-// pixel) and needs from it only ONE scalar: the factor of the gradient. That factor is  ramp * weight / P * um  [* per-pixel
-// confidence]  -- known up front -- times, in the default confidence mode, the scalar RATE (train_seg_semisup_mask_mt.py:415-418:
-// the confidence mask is replaced by its mean), in which the gradient is LINEAR. So one pass computes the loss partial sums AND
-// the gradient with the rate left out (`grad_unit` = ramp * weight / P), the finalising launch derives the scalars, and
-// cms_scale_by_scalar multiplies the gradient rows by the rate afterwards (a 350 k-float pass). The chain between the forward and
-// the backward pass of the step loses a launch of 0.10-0.12 ms and a second staging of all rectangles; under data parallelism
-// the gradient no longer waits for the all-reduce of the confidence count either. Per-pixel values are those of the two
-// kernels (same functions on the same registers).
-template <int CT, int LF>
-__global__ __launch_bounds__(256, (LF >= 0 && CT > 0) ? 4 : 1) void cons_fused_tiled_kernel(ConsArgs a, float grad_unit, float* __restrict__ grad,
-                                                               int patch_stride, float* __restrict__ partials) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const Geo& g = a.g;
-    const bool pp = a.tau > 0.0f && a.d.conf_per_pixel;
-    const int pstride = patch_stride;
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    auto stage = [&](int n, const Patch& p, float* P) { cons_stage(a, n, p, P, pstride); };
-    auto pixel_grad = [&](int n, int y, int x, const Tap& ty, const Tap& tx, const Patch& p, const float* P, auto emit) -> bool {
-        const ConsPixel px = cons_pixel_inputs(a, n, y, x);
-        const float base_f = grad_unit * px.um;
-        // (no early-out on base_f == 0, see cons_bwd_ident_kernel)
-        const Gather<false> gs = gather_staged(P, p, ty, tx);       // (taps already rebased to the rectangle)
-        const Gather<false> gt = gather_staged(P + (px.which ? 2 * pstride : pstride), p, ty, tx);
-        PixelFwd r;
-        if (CT > 0) {
-            RegVec<CT> rs, rt;
-            fill<CT, false>(rs, gs);
-            fill<CT, false>(rt, gt);
-            r = consistency_pixel_fwd_bwd<(CT > 0 ? CT : 1), LF>(
-                rs, rt, a.d.loss_fn, a.inv_root_c,
-                [&](float conf) -> float { return (pp && !(conf >= a.tau)) ? 0.0f : base_f; },
-                [&](int k, float v) { emit(k, v); });
-        } else {
-            r = consistency_pixel_fwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c);
-            const float f = (pp && !(r.conf >= a.tau)) ? 0.0f : base_f;
-            consistency_pixel_bwd<0>(gs, gt, g.c, a.d.loss_fn, a.inv_root_c, [&](int k, float v) { emit(k, f * v); });
-        }
-        const float lm = r.loss * px.um;
-        const float cf = (a.tau > 0.0f && r.conf >= a.tau) ? 1.0f : 0.0f;
-        acc[0] += lm;
-        acc[1] += lm * cf;
-        acc[2] += cf;
-        return true;
-    };
-    tiled_scatter(g, stage, pixel_grad, grad, smem);
-    __shared__ float red[3 * 16];
-    store_partials<3>(acc, red, partials);
 }
 
 // x[i] *= scalars[idx] * factor for i < n (the deferred factor of the fused loss launches: a device scalar)
@@ -475,15 +297,6 @@ static CeArgs make_ce_args(const cms_ce_desc* d) {
     return a;
 }
 
-// the one-launch forward + backward of a family over `tiles` tiles, and the reduction of its K partial sums
-template <int K, class Kern, class... Args>
-static void launch_fused(Kern kern, int tiles, size_t lds, hipStream_t s, float* partials, double* stats_out, double extra, int extra_slot,
-                         Args... args) {
-    allow_lds(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), lds, s, args..., partials);
-    hipLaunchKernelGGL((reduce_partials_kernel<K>), dim3(1), dim3(256), 0, s, partials, tiles, stats_out, extra, extra_slot);
-}
-
 }  // namespace cms
 
 using namespace cms;
@@ -504,17 +317,10 @@ extern "C" int cms_consistency_fwd_bwd(const cms_consistency_desc* d, float grad
     int rc = check_cons(d);
     if (rc) return rc;
     CMS_REQUIRE(workspace && stats_out && grad_l_stu, "consistency_fwd_bwd: workspace / stats_out / grad NULL");
-    ConsArgs a = make_cons_args(d);
+    const ConsArgs a = make_cons_args(d);
     const int tiles = fused_tiles(a.g, 3);
     CMS_REQUIRE(tiles > 0, "consistency_fwd_bwd: not available for this geometry / mode (ask cms_consistency_fused_supported)");
-    hipStream_t s = (hipStream_t)stream;
-    const int pstride = (int)patch_floats(d->c, a.g.sy, a.g.sx, TILE_H);
-    CMS_DISPATCH_C(d->c, {
-        // the default loss (`var`) as a compile-time constant: its own register allocation (see consistency_pixel_fwd_bwd)
-        auto kern = d->loss_fn == CMS_LOSS_VAR ? cons_fused_tiled_kernel<CT, LOSS_VAR> : cons_fused_tiled_kernel<CT, -1>;
-        launch_fused<3>(kern, tiles, tile_lds_bytes(d->c, a.g.sy, a.g.sx, 3), s, (float*)workspace, stats_out,
-                        (double)((size_t)d->n * d->H * d->W), 3, a, grad_unit, grad_l_stu, pstride);
-    });
+    cons_launch_fused<TauThresh>(a, tiles, grad_unit, (float*)workspace, stats_out, grad_l_stu, (hipStream_t)stream);
     return launch_status("cms_consistency_fwd_bwd");
 }
 
@@ -530,11 +336,7 @@ extern "C" int cms_consistency_fwd(const cms_consistency_desc* d, void* workspac
     int rc = check_cons(d);
     if (rc) return rc;
     CMS_REQUIRE(workspace && stats_out, "consistency_fwd: workspace / stats_out NULL");
-    ConsArgs a = make_cons_args(d);
-    const FwdPlan p = fwd_plan(a.g, 3);
-    CMS_DISPATCH_C(d->c, launch_fwd<3>(cons_fwd_tiled_kernel<CT>, cons_fwd_kernel<CT, true>, cons_fwd_kernel<CT, false>, a, p,
-                                       (float*)workspace, stats_out, (double)((size_t)d->n * d->H * d->W), 3,
-                                       (hipStream_t)stream, p.pstride));
+    cons_launch_fwd<TauThresh>(make_cons_args(d), (float*)workspace, stats_out, (hipStream_t)stream);
     return launch_status("cms_consistency_fwd");
 }
 
@@ -557,10 +359,7 @@ extern "C" int cms_consistency_bwd(const cms_consistency_desc* d, const float* s
     int rc = check_cons(d);
     if (rc) return rc;
     CMS_REQUIRE(scalars && grad_l_stu, "consistency_bwd: scalars / grad NULL");
-    ConsArgs a = make_cons_args(d);
-    const int pstride = (int)patch_floats(d->c, a.g.sy, a.g.sx, TILE_H);
-    CMS_DISPATCH_C(d->c, rc = launch_bwd("consistency_bwd", cons_bwd_ident_kernel<CT>, cons_bwd_tiled_kernel<CT>, a, 3, 0, scalars,
-                                         grad_l_stu, (hipStream_t)stream, pstride));
+    rc = cons_launch_bwd<TauThresh>("consistency_bwd", make_cons_args(d), scalars, grad_l_stu, (hipStream_t)stream);
     return rc ? rc : launch_status("cms_consistency_bwd");
 }
 

@@ -252,6 +252,23 @@ def _ct_desc(cfg, d):
     return cd
 
 
+def _cons_family(cfg, d):
+    """The entry point family `cfg` asks for and the descriptor it takes: cms_cthresh_* with the class-threshold descriptor around
+    `d`, or cms_consistency_* with `d` itself."""
+    if cfg.class_thresh is not None:
+        return 'cms_cthresh_', _ct_desc(cfg, d)
+    return 'cms_consistency_', d
+
+
+def _cons_call(family, op, *args):
+    """calls entry point `op` of a `_cons_family` on its descriptor and returns its value; an error code raises"""
+    name = family[0] + op
+    rc = fn[name](C.byref(family[1]), *args)
+    if rc < 0:
+        check(rc, name)
+    return rc
+
+
 def _workspace(name, d, device):
     """uninitialised scratch of the size cms_<name>_workspace_bytes asks for"""
     return _workspace_bytes(int(fn['cms_{}_workspace_bytes'.format(name)](C.byref(d))), device)
@@ -321,11 +338,7 @@ def consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges=None, mask=
     dev = keep[0].device
     ws = _workspace('consistency', d, dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
-    if cfg.class_thresh is not None:
-        cd = _ct_desc(cfg, d)
-        check(fn['cms_cthresh_fwd'](C.byref(cd), _ptr(ws), _ptr(stats), _stream()), 'cms_cthresh_fwd')
-    else:
-        check(fn['cms_consistency_fwd'](C.byref(d), _ptr(ws), _ptr(stats), _stream()), 'cms_consistency_fwd')
+    _cons_call(_cons_family(cfg, d), 'fwd', _ptr(ws), _ptr(stats), _stream())
     return _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate), (d, keep, stats)
 
 
@@ -334,24 +347,18 @@ def consistency_backward(ctx, scalars, grad_out=None, samples=None):
     that run of samples (rows s0:s1 of `grad_out` are written) -- the per-pixel work of the backward is independent between samples,
     so a caller may issue disjoint runs on different streams (step.py: half of it on the main stream beside the other half)."""
     d, keep, _ = ctx
-    l_stu = keep[0]
+    l_stu, l_t0, l_t1, ranges, mask, um0, um1, cfg, out_size = keep
     if grad_out is None:
         grad_out = torch.zeros_like(l_stu)
-    cfg_ = keep[7]
-    if cfg_.class_thresh is not None:
-        bwd = lambda dd, g: check(fn['cms_cthresh_bwd'](C.byref(_ct_desc(cfg_, dd)), _ptr(scalars), _ptr(g), _stream()), 'cms_cthresh_bwd')
-    else:
-        bwd = lambda dd, g: check(fn['cms_consistency_bwd'](C.byref(dd), _ptr(scalars), _ptr(g), _stream()), 'cms_consistency_bwd')
+    rows = grad_out
     if samples is not None:
         s0, s1 = int(samples[0]), int(samples[1])
         if not (0 <= s0 < s1 <= int(l_stu.shape[0])):
             raise ValueError('consistency_backward: bad sample range')
         sl = lambda t: None if t is None else t[s0:s1]
-        l_s, l_t0, l_t1, ranges, mask, um0, um1, cfg, out_size = keep
-        d = _cons_desc(cfg, sl(l_s), sl(l_t0), sl(l_t1), sl(ranges), sl(mask), sl(um0), sl(um1), out_size)
-        bwd(d, grad_out[s0:s1])
-        return grad_out
-    bwd(d, grad_out)
+        d = _cons_desc(cfg, sl(l_stu), sl(l_t0), sl(l_t1), sl(ranges), sl(mask), sl(um0), sl(um1), out_size)
+        rows = grad_out[s0:s1]
+    _cons_call(_cons_family(cfg, d), 'bwd', _ptr(scalars), _ptr(rows), _stream())
     return grad_out
 
 
@@ -363,9 +370,8 @@ def consistency_fused(cfg, l_stu, l_tea0, l_tea1, out_size, grad_out, ranges=Non
     the two launches where the fused one does not exist (identity geometry, deterministic mode, CMS_LOSS_FUSED=0)."""
     d, keep = _cons_prepare('consistency_fused', cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1, grad_out)
     l_stu, l_tea0, l_tea1, ranges, mask, um0, um1 = keep[:7]
-    ct = cfg.class_thresh is not None
-    cd = _ct_desc(cfg, d) if ct else None
-    if not (fn['cms_cthresh_fused_supported'](C.byref(cd)) if ct else fn['cms_consistency_fused_supported'](C.byref(d))):
+    family = _cons_family(cfg, d)
+    if not _cons_call(family, 'fused_supported'):
         sc, cctx = consistency_forward(cfg, l_stu, l_tea0, l_tea1, out_size, ranges, mask, um0, um1, ramp_val, cons_weight, group,
                                        sync_conf_rate)
         consistency_backward(cctx, sc, grad_out)
@@ -375,13 +381,9 @@ def consistency_fused(cfg, l_stu, l_tea0, l_tea1, out_size, grad_out, ranges=Non
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     P = float(d.n) * float(d.H) * float(d.W)
     grad_unit = float(ramp_val) * float(cons_weight) / P
-    if ct:
-        check(fn['cms_cthresh_fwd_bwd'](C.byref(cd), grad_unit, _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()), 'cms_cthresh_fwd_bwd')
-    else:
-        check(fn['cms_consistency_fwd_bwd'](C.byref(d), grad_unit, _ptr(ws), _ptr(stats), _ptr(grad_out), _stream()),
-              'cms_consistency_fwd_bwd')
+    _cons_call(family, 'fwd_bwd', grad_unit, _ptr(ws), _ptr(stats), _ptr(grad_out), _stream())
     scalars = _cons_scalars(stats, cfg, ramp_val, cons_weight, group, sync_conf_rate)
-    if (ct or cfg.conf_thresh > 0.0) and not cfg.conf_per_pixel:
+    if (cfg.class_thresh is not None or cfg.conf_thresh > 0.0) and not cfg.conf_per_pixel:
         # default confidence mode (:415-418): the loss mask is the scalar RATE -- the factor the launch above left out
         check(fn['cms_scale_by_scalar'](_ptr(grad_out), grad_out.numel(), _ptr(scalars), 1, 1.0, _stream()), 'cms_scale_by_scalar')
     return scalars

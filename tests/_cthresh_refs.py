@@ -29,7 +29,8 @@ RAMP, WEIGHT = L.RAMP, L.WEIGHT
 
 # (geometry of _loss_refs.GEOS, mask mode, loss, per-pixel confidence, mask given as): what each reaches is in the issue's table --
 #   span42 C = 2 | sy1 C = 5 | tab2c19 C = 19, table loop, two tile columns | ratio2s C = 21, opt-in LDS | cmp33 run-time class count,
-#   partial tiles | near1 direct-gather forward | identc3 identity forward and backward, no fused launch | one 1 x 1 logits
+#   partial tiles | near1 direct-gather forward | identc3 identity forward and backward, no fused launch | one 1 x 1 logits |
+#   identc5 the identity kernels with a compile-time class count (appended: tests index this list)
 CASES = [
     ('span42', 'mix', 'var', False, 'ranges'),
     ('sy1', 'cut', 'kld', True, 'mask'),
@@ -42,6 +43,7 @@ CASES = [
     ('identc3', 'mix', 'kld', True, 'ranges'),
     ('identc3', 'cut', 'var', False, 'mask'),
     ('one', 'cut', 'bce', True, 'ranges'),
+    ('identc5', 'mix', 'var', True, 'ranges'),          # the identity kernels with a compile-time class count, the per-pixel gate on
 ]
 REFUSED = ('toobig', 'mix', 'var', False, 'ranges')
 VECTORS = ('ascending', 'one', 'floor')
@@ -51,7 +53,8 @@ ROUTES = {
     'tab2c19': dict(forward='tiled', backward='tiled', fused=True, tiles_x=2, table_all=True),
     'ratio2s': dict(forward='tiled_optin', backward='tiled_optin', fused=True),
     'cmp33': dict(forward='tiled', backward='tiled', fused=True), 'near1': dict(forward='direct', backward='tiled_optin', fused=True),
-    'identc3': dict(forward='identity', backward='identity', fused=False), 'one': dict(forward='tiled', backward='tiled', fused=True),
+    'identc3': dict(forward='identity', backward='identity', fused=False),
+    'identc5': dict(forward='identity', backward='identity', fused=False), 'one': dict(forward='tiled', backward='tiled', fused=True),
     'toobig': dict(forward='direct', backward='error', fused=False),
 }
 

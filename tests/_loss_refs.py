@@ -373,6 +373,8 @@ GEOS = {
     'toobig':   (1, 32, 60, 60, 65, 65, True, 1, False, dict(loop='compare', backward='error', forward='direct', fused=False)),
     # the identity kernels (forward and backward, both losses) with a run-time class count; two tile columns' worth of pixels
     'identc3':  (2, 3, 9, 70, 9, 70, True, 1, False, dict(loop='compare', backward='identity', forward='identity', fused=False)),
+    # ... and with a compile-time one (5): the instances the class-threshold kernels share with these are reached through it
+    'identc5':  (2, 5, 9, 70, 9, 70, True, 1, False, dict(loop='compare', backward='identity', forward='identity', fused=False)),
     # the direct-gather forward of the CROSS ENTROPY (one rectangle: 46 x 9 x 62 floats = 100 KB > 96 KB), which only a run-time
     # class count reaches; its backward and fused launch are tiled (147 KB). No consistency backward at this size (three rectangles)
     'ce46':     (1, 46, 60, 60, 64, 64, True, 2, False, dict(loop='compare', backward='error', forward='direct', fused=False)),
