@@ -8,12 +8,11 @@ two cells: it is AMBIGUOUS. The restatement returns the SURE tables (from the ot
 fall into it; a result is accepted when sure <= got <= sure + maybe in every cell. That ambiguous pixels are at most 1 % of the scored
 pixels is a condition on every case (tests/test_calib_cpu.py asserts it), not a measurement."""
 import functools
-import os
 import struct
-import subprocess
 
 import numpy as np
 
+import _hostcheck
 import _tta_refs as T
 
 FLT_MIN = float(np.finfo(np.float32).tiny)
@@ -229,26 +228,10 @@ def case(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
 NULLS = dict(labels=1, hist=2, scores=4, cm=8, pred_out=16, edges=32, temps=64)
 
 
-def hostcheck_source():
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), 'hostcheck_calib', 'hostcheck_calib.cpp')
-
-
-def hostcheck_build(directory, sanitize=False):
-    """compile tests/hostcheck_calib (a stand-alone program with its own main) into `directory` -> its path"""
-    exe = os.path.join(str(directory), 'hostcheck_calib_asan' if sanitize else 'hostcheck_calib')
-    extra = ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.check_call(GXX + extra + [hostcheck_source(), '-o', exe])
-    return exe
-
-
-_count = [0]
-
-
-def hostcheck_run(exe, directory, inp, expect_code=0, null=(), **over):
+def hostcheck_run(exe, inp, expect_code=0, null=(), **over):
     """one request through the host driver -> dict(hist, scores, cm, claims, pred, conf, brier, nll), or None when it ends with
     `expect_code` != 0. `over`: header fields (n, c, H, W, k, align, label_dtype, ignore, nb, nt) or `edges` / `temps` sent as they are."""
     n, c = inp['logits'][0].shape[:2]
@@ -258,37 +241,18 @@ def hostcheck_run(exe, directory, inp, expect_code=0, null=(), **over):
     head = dict(n=n, c=c, H=H, W=W, k=len(inp['logits']), align=int(inp['align']), label_dtype=int(inp['labels'].dtype == np.int64),
                 ignore=255, nb=len(edges) + 1, nt=len(temps))
     head.update(over)
-    _count[0] += 1
-    req = os.path.join(str(directory), 'req{}.bin'.format(_count[0]))
-    res = os.path.join(str(directory), 'res{}.bin'.format(_count[0]))
-    with open(req, 'wb') as f:
-        f.write(struct.pack('<13i', head['n'], head['c'], head['H'], head['W'], head['k'], head['align'], head['label_dtype'],
-                            head['ignore'], head['nb'], head['nt'], len(edges), len(temps), sum(NULLS[x] for x in null)))
-        f.write(edges.tobytes())
-        f.write(temps.tobytes())
-        for t, fl in zip(inp['logits'], inp['flips']):
-            f.write(struct.pack('<3i', t.shape[2], t.shape[3], int(fl)))
-        for t in inp['logits']:
-            f.write(np.ascontiguousarray(t, dtype=np.float32).tobytes())
-        f.write(np.ascontiguousarray(inp['labels']).tobytes())
-    code = subprocess.call([exe, req, res])
-    assert code == expect_code, code
-    if code != 0:
+    header = struct.pack('<13i', head['n'], head['c'], head['H'], head['W'], head['k'], head['align'], head['label_dtype'],
+                         head['ignore'], head['nb'], head['nt'], len(edges), len(temps), sum(NULLS[x] for x in null))
+    header += edges.tobytes() + temps.tobytes()
+    for t, fl in zip(inp['logits'], inp['flips']):
+        header += struct.pack('<3i', t.shape[2], t.shape[3], int(fl))
+    raw = _hostcheck.run(exe, header, [(t, np.float32) for t in inp['logits']] + [(inp['labels'], None)], expect_code)
+    if raw is None:
         return None
-    raw = open(res, 'rb').read()
-    pix, nb, nt = n * H * W, head['nb'], head['nt']
-    sizes = [8 * c * nb * 3, 8 * (2 + nt), 8 * c * c, 24, pix, 4 * pix, 4 * pix, 4 * pix * nt]
-    assert len(raw) == sum(sizes)
-    parts, o = [], 0
-    for s in sizes:
-        parts.append(raw[o:o + s])
-        o += s
-    return dict(hist=np.frombuffer(parts[0], dtype=np.int64).reshape(c, nb, 3), scores=np.frombuffer(parts[1], dtype=np.int64),
-                cm=np.frombuffer(parts[2], dtype=np.int64).reshape(c, c), claims=np.frombuffer(parts[3], dtype=np.int64),
-                pred=np.frombuffer(parts[4], dtype=np.uint8).reshape(n, H, W),
-                conf=np.frombuffer(parts[5], dtype=np.float32).reshape(n, H, W),
-                brier=np.frombuffer(parts[6], dtype=np.float32).reshape(n, H, W),
-                nll=np.frombuffer(parts[7], dtype=np.float32).reshape(nt, n, H, W))
+    nb, nt = head['nb'], head['nt']
+    return _hostcheck.split(raw, [('hist', np.int64, (c, nb, 3)), ('scores', np.int64, (2 + nt,)), ('cm', np.int64, (c, c)),
+                                  ('claims', np.int64, (3,)), ('pred', np.uint8, (n, H, W)), ('conf', np.float32, (n, H, W)),
+                                  ('brier', np.float32, (n, H, W)), ('nll', np.float32, (nt, n, H, W))])
 
 
 def pixel_errors(got, ref):

@@ -3,10 +3,12 @@ fp64 (the restatement tests/_tta_refs.py holds against torch), the select by the
 validity, threshold, the four counts --, the margins its cases must keep, the cases the CPU and GPU tests share, and the restatement
 of one whole CPS iteration on the CPU oracle. Nothing here imports the product."""
 import functools
+import struct
 
 import numpy as np
 import torch
 
+import _hostcheck
 import _tta_refs as T
 
 GAP = 1e-4          # the two largest upsampled logits of a pixel differ by at least this (the project's margin for this arithmetic)
@@ -181,63 +183,23 @@ def variants():
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
-
-
-def hostcheck_source():
-    import os
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), 'hostcheck_cps', 'hostcheck_cps.cpp')
-
-
-def hostcheck_build(directory, sanitize=False):
-    """compile tests/hostcheck_cps (a stand-alone program with its own main) into `directory` -> its path"""
-    import os
-    import subprocess
-    exe = os.path.join(str(directory), 'hostcheck_cps_asan' if sanitize else 'hostcheck_cps')
-    extra = ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.check_call(GXX + extra + [hostcheck_source(), '-o', exe])
-    return exe
-
-
-_count = [0]
-
-
-def hostcheck_run(exe, directory, logits, size, align, mask=None, ranges=None, invert=True, um0=None, um1=None, tau=0.0, vec=True,
+def hostcheck_run(exe, logits, size, align, mask=None, ranges=None, invert=True, um0=None, um1=None, tau=0.0, vec=True,
                   expect_code=0, **over):
     """one request through the host driver -> dict(label_a, label_b, stats), or None when it ends with `expect_code` != 0.
     `over`: header fields sent as they are, whatever the arrays' shapes say."""
-    import os
-    import struct
-    import subprocess
     n, c, h, w = logits[0].shape
     head = dict(n=n, c=c, h=h, w=w, H=size[0], W=size[1], n_boxes=0 if ranges is None else int(np.asarray(ranges).shape[1]))
     head.update(over)
-    _count[0] += 1
-    req = os.path.join(str(directory), 'req{}.bin'.format(_count[0]))
-    res = os.path.join(str(directory), 'res{}.bin'.format(_count[0]))
-    with open(req, 'wb') as f:
-        f.write(struct.pack('<12if', head['n'], head['c'], head['h'], head['w'], head['H'], head['W'], int(align), head['n_boxes'],
-                            int(invert), int(um0 is not None), int(um1 is not None), int(vec), float(tau)))
-        for t in logits:
-            f.write(np.ascontiguousarray(t, dtype=np.float32).tobytes())
-        if ranges is not None:
-            f.write(np.ascontiguousarray(ranges, dtype=np.int32).tobytes())
-        else:
-            f.write(np.ascontiguousarray(mask, dtype=np.float32).tobytes())
-        for t in (um0, um1):
-            if t is not None:
-                f.write(np.ascontiguousarray(t, dtype=np.float32).tobytes())
-    code = subprocess.call([exe, req, res])
-    assert code == expect_code, code
-    if code != 0:
+    header = struct.pack('<12if', head['n'], head['c'], head['h'], head['w'], head['H'], head['W'], int(align), head['n_boxes'],
+                         int(invert), int(um0 is not None), int(um1 is not None), int(vec), float(tau))
+    blocks = [(t, np.float32) for t in logits]
+    blocks.append((ranges, np.int32) if ranges is not None else (mask, np.float32))
+    blocks += [(t, np.float32) for t in (um0, um1) if t is not None]
+    raw = _hostcheck.run(exe, header, blocks, expect_code)
+    if raw is None:
         return None
-    raw = open(res, 'rb').read()
-    pix = n * size[0] * size[1]
-    assert len(raw) == 2 * pix + 32
     shape = (n,) + tuple(size)
-    return dict(label_a=np.frombuffer(raw[:pix], dtype=np.uint8).reshape(shape),
-                label_b=np.frombuffer(raw[pix:2 * pix], dtype=np.uint8).reshape(shape),
-                stats=np.frombuffer(raw[2 * pix:], dtype=np.int64))
+    return _hostcheck.split(raw, [('label_a', np.uint8, shape), ('label_b', np.uint8, shape), ('stats', np.int64, (4,))])
 
 
 def same(got, ref):

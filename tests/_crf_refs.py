@@ -2,12 +2,11 @@
 definition) -- the unary term from _tta_refs.vote, then mean-field inference with shifted arrays -- the cases the CPU and GPU tests
 share, and the driver of the host-check program (tests/hostcheck_crf). Nothing here imports the product."""
 import functools
-import os
 import struct
-import subprocess
 
 import numpy as np
 
+import _hostcheck
 import _tta_refs as T
 
 FLT_MIN = float(np.finfo(np.float32).tiny)
@@ -199,25 +198,7 @@ def compare(got, ref, bound=B):
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
-
-
-def hostcheck_source():
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), 'hostcheck_crf', 'hostcheck_crf.cpp')
-
-
-def hostcheck_build(directory, sanitize=False):
-    """compile tests/hostcheck_crf (a stand-alone program with its own main) into `directory` -> its path"""
-    exe = os.path.join(str(directory), 'hostcheck_crf_asan' if sanitize else 'hostcheck_crf')
-    extra = ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.check_call(GXX + extra + [hostcheck_source(), '-o', exe])
-    return exe
-
-
-_count = [0]
-
-
-def hostcheck_run(exe, directory, inp, expect_code=0, **over):
+def hostcheck_run(exe, inp, expect_code=0, **over):
     """one request through the host driver -> dict(q, pred, unary_pred, stats), or None when it ends with `expect_code` != 0.
     `over`: header fields sent as they are."""
     n, c = inp['logits'][0].shape[:2]
@@ -228,26 +209,13 @@ def hostcheck_run(exe, directory, inp, expect_code=0, **over):
     rects = over.pop('rects', inp['rects'])
     for key, val in over.items():
         (head if key in head else prm)[key] = val
-    _count[0] += 1
-    req = os.path.join(str(directory), 'req{}.bin'.format(_count[0]))
-    res = os.path.join(str(directory), 'res{}.bin'.format(_count[0]))
-    with open(req, 'wb') as f:
-        f.write(struct.pack('<9i5f', head['n'], head['c'], head['H'], head['W'], head['k'], head['align'], head['radius'],
-                            head['dilation'], head['iters'], prm['bi_w'], prm['bi_xy'], prm['bi_rgb'], prm['pos_w'], prm['pos_xy']))
-        for t, fl in zip(inp['logits'], inp['flips']):
-            f.write(struct.pack('<3i', t.shape[2], t.shape[3], int(fl)))
-        for t in inp['logits']:
-            f.write(np.ascontiguousarray(t, dtype=np.float32).tobytes())
-        f.write(np.ascontiguousarray(inp['rgb'], dtype=np.uint8).tobytes())
-        f.write(np.ascontiguousarray(rects, dtype=np.int32).tobytes())
-    code = subprocess.call([exe, req, res])
-    assert code == expect_code, code
-    if code != 0:
+    header = struct.pack('<9i5f', head['n'], head['c'], head['H'], head['W'], head['k'], head['align'], head['radius'],
+                         head['dilation'], head['iters'], prm['bi_w'], prm['bi_xy'], prm['bi_rgb'], prm['pos_w'], prm['pos_xy'])
+    for t, fl in zip(inp['logits'], inp['flips']):
+        header += struct.pack('<3i', t.shape[2], t.shape[3], int(fl))
+    blocks = [(t, np.float32) for t in inp['logits']] + [(inp['rgb'], np.uint8), (rects, np.int32)]
+    raw = _hostcheck.run(exe, header, blocks, expect_code)
+    if raw is None:
         return None
-    raw = open(res, 'rb').read()
-    pix = n * H * W
-    assert len(raw) == 4 * pix * c + 2 * pix + 16
-    return dict(q=np.frombuffer(raw[:4 * pix * c], dtype=np.float32).reshape(n, c, H, W),
-                pred=np.frombuffer(raw[4 * pix * c:4 * pix * c + pix], dtype=np.uint8).reshape(n, H, W),
-                unary_pred=np.frombuffer(raw[4 * pix * c + pix:4 * pix * c + 2 * pix], dtype=np.uint8).reshape(n, H, W),
-                stats=np.frombuffer(raw[4 * pix * c + 2 * pix:], dtype=np.int64))
+    return _hostcheck.split(raw, [('q', np.float32, (n, c, H, W)), ('pred', np.uint8, (n, H, W)), ('unary_pred', np.uint8, (n, H, W)),
+                                  ('stats', np.int64, (2,))])

@@ -8,12 +8,11 @@ count map, divides, and reads the view at every canvas pixel -- the tensor formu
 Exact comparison of predictions needs a condition on the inputs, not a tolerance: every case's logits are drawn (its seed searched on
 the CPU, tests/test_window_cpu.py::test_case_margins re-checks it) so that the reference decides EVERY pixel by more than GAP_BOUND."""
 import functools
-import os
 import struct
-import subprocess
 
 import numpy as np
 
+import _hostcheck
 import _tta_refs as T
 
 # Twice the largest |fp32 - fp64| error of a pixel's score over every case below, rounded up to two digits. The fp32 scores are the
@@ -157,27 +156,11 @@ def case(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ host check
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
 NULLS = dict(labels=1, cm=2, pred_out=4, logits=8)
 VIEW_FIELDS = ('hl', 'wl', 'Hv', 'Wv', 'gy', 'gx', 'eh', 'ew', 'sh', 'sw', 'flip')
 
 
-def hostcheck_source():
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), 'hostcheck_window', 'hostcheck_window.cpp')
-
-
-def hostcheck_build(directory, sanitize=False):
-    """compile tests/hostcheck_window (a stand-alone program with its own main) into `directory` -> its path"""
-    exe = os.path.join(str(directory), 'hostcheck_window_asan' if sanitize else 'hostcheck_window')
-    extra = ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.check_call(GXX + extra + [hostcheck_source(), '-o', exe])
-    return exe
-
-
-_count = [0]
-
-
-def hostcheck_run(exe, directory, cs, expect_code=0, null=(), views=None, **over):
+def hostcheck_run(exe, cs, expect_code=0, null=(), views=None, **over):
     """one vote request through the host driver -> dict(cm, claims, pred, score), or None when it ends with `expect_code` != 0.
     `over`: header fields (n, c, H, W, k, align, label_dtype, ignore, wh, ww) sent as they are; `views`: {view index: {field: value}}
     overrides of the per-view table."""
@@ -191,44 +174,27 @@ def hostcheck_run(exe, directory, cs, expect_code=0, null=(), views=None, **over
         row = dict(v, sh=cs['stride'][0], sw=cs['stride'][1], flip=int(v['flip']))
         row.update((views or {}).get(i, {}))
         table.append(row)
-    _count[0] += 1
-    req = os.path.join(str(directory), 'req{}.bin'.format(_count[0]))
-    res = os.path.join(str(directory), 'res{}.bin'.format(_count[0]))
-    with open(req, 'wb') as f:
-        f.write(struct.pack('<12i', 0, head['n'], head['c'], head['H'], head['W'], head['k'], head['align'], head['label_dtype'],
-                            head['ignore'], head['wh'], head['ww'], sum(NULLS[x] for x in null)))
-        for row in table:
-            f.write(struct.pack('<11i', *[row[name] for name in VIEW_FIELDS]))
-        for t in cs['logits']:
-            f.write(struct.pack('<q', t.size))
-            f.write(np.ascontiguousarray(t, dtype=np.float32).tobytes())
-        f.write(np.ascontiguousarray(cs['labels']).tobytes())
-    code = subprocess.call([exe, req, res])
-    assert code == expect_code, code
-    if code != 0:
+    header = struct.pack('<12i', 0, head['n'], head['c'], head['H'], head['W'], head['k'], head['align'], head['label_dtype'],
+                         head['ignore'], head['wh'], head['ww'], sum(NULLS[x] for x in null))
+    for row in table:
+        header += struct.pack('<11i', *[row[name] for name in VIEW_FIELDS])
+    blocks = []
+    for t in cs['logits']:
+        blocks += [(t.size, '<i8'), (t, np.float32)]
+    raw = _hostcheck.run(exe, header, blocks + [(cs['labels'], None)], expect_code)
+    if raw is None:
         return None
-    raw = open(res, 'rb').read()
-    pix = n * H * W
-    sizes = [8 * c * c, 8, pix, 4 * pix * c]
-    assert len(raw) == sum(sizes)
-    cm, claims, pred, score = (raw[sum(sizes[:i]):sum(sizes[:i + 1])] for i in range(4))
-    return dict(cm=np.frombuffer(cm, dtype=np.int64).reshape(c, c), claims=int(np.frombuffer(claims, dtype=np.int64)[0]),
-                pred=np.frombuffer(pred, dtype=np.uint8).reshape(n, H, W),
-                score=np.frombuffer(score, dtype=np.float32).reshape(n, c, H, W))
+    out = _hostcheck.split(raw, [('cm', np.int64, (c, c)), ('claims', np.int64, (1,)), ('pred', np.uint8, (n, H, W)),
+                                 ('score', np.float32, (n, c, H, W))])
+    return dict(out, claims=int(out['claims'][0]))
 
 
-def hostcheck_crop(exe, directory, x, view_size, flip, window, stride, expect_code=0):
+def hostcheck_crop(exe, x, view_size, flip, window, stride, expect_code=0):
     """one crop request -> (n * G, c, eh, ew) float32"""
     n, c, H, W = x.shape
-    _count[0] += 1
-    req = os.path.join(str(directory), 'req{}.bin'.format(_count[0]))
-    res = os.path.join(str(directory), 'res{}.bin'.format(_count[0]))
-    with open(req, 'wb') as f:
-        f.write(struct.pack('<12i', 1, n, c, H, W, view_size[0], view_size[1], int(flip), window[0], window[1], stride[0], stride[1]))
-        f.write(np.ascontiguousarray(x, dtype=np.float32).tobytes())
-    code = subprocess.call([exe, req, res])
-    assert code == expect_code, code
-    if code != 0:
+    header = struct.pack('<12i', 1, n, c, H, W, view_size[0], view_size[1], int(flip), window[0], window[1], stride[0], stride[1])
+    raw = _hostcheck.run(exe, header, [(x, np.float32)], expect_code)
+    if raw is None:
         return None
     (eh, ys), (ew, xs) = axis_grid(view_size[0], window[0], stride[0]), axis_grid(view_size[1], window[1], stride[1])
-    return np.fromfile(res, dtype=np.float32).reshape(n * len(ys) * len(xs), c, eh, ew)
+    return _hostcheck.split(raw, [('crops', np.float32, (n * len(ys) * len(xs), c, eh, ew))])['crops']

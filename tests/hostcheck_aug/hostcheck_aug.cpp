@@ -6,7 +6,7 @@
 // losses and their analytic gradients) can be checked against tests/_aug_refs.py on a CPU-only machine. The kernels' indexing,
 // reductions, LDS tiling and the staged / global routes are covered by the `-m gpu` tests.
 //
-// Build: see the Makefile (shared object for the test; `make asan` runs a stand-alone driver under ASan + UBSan).
+// Build: tests/_hostcheck.py (shared object for the tests; `--sanitize`: the stand-alone driver below under ASan + UBSan).
 #include <stdint.h>
 #include <stddef.h>
 #include <vector>

@@ -21,28 +21,11 @@
 #include <string.h>
 
 #include "../../cutmix-semisup-seg_amd/csrc/calib_math.hpp"
+#include "../hostcheck_common.hpp"
 
 using namespace cms;
 
-// every heap block of the run, freed when main returns on whichever path (a refusal included): the sanitizer build counts leaks
-struct Blocks {
-    void* p[64];
-    int n = 0;
-    void* keep(void* q) {
-        if (!q || n >= 64) exit(1);
-        return p[n++] = q;
-    }
-    ~Blocks() {
-        for (int i = 0; i < n; ++i) free(p[i]);
-    }
-};
-static Blocks g_blocks;
-
-static void* read_block(FILE* f, size_t bytes) {
-    void* p = g_blocks.keep(malloc(bytes ? bytes : 1));
-    if (fread(p, 1, bytes, f) != bytes) exit(1);
-    return p;
-}
+static Blocks g_blocks;          // every heap block of the run (hostcheck_common.hpp)
 
 static uint32_t bits(float v) {
     uint32_t u;
@@ -65,8 +48,8 @@ int main(int argc, char** argv) {
     d.label_dtype = head[6], d.ignore_index = head[7], d.nb = head[8], d.nt = head[9];
     const int n_edges = head[10], n_temps = head[11], null_mask = head[12];
     if (n_edges < 0 || n_edges > 4096 || n_temps < 0 || n_temps > 4096) return 1;
-    float* edges = (float*)read_block(f, (size_t)n_edges * sizeof(float));
-    float* temps = (float*)read_block(f, (size_t)n_temps * sizeof(float));
+    float* edges = (float*)read_block(f, (size_t)n_edges * sizeof(float), &g_blocks);
+    float* temps = (float*)read_block(f, (size_t)n_temps * sizeof(float), &g_blocks);
     // what the driver itself needs to lay the request out; the product's check decides everything else
     if (d.k < 1 || d.k > CMS_TTA_MAX_VIEWS || d.n < 1 || d.c < 1 || d.c > kTtaMaxClasses || d.H < 1 || d.W < 1 ||
         !tta_count_ok(d.n, d.H, d.W))
@@ -77,10 +60,10 @@ int main(int argc, char** argv) {
         d.h[i] = v[0], d.w[i] = v[1], d.flip[i] = v[2];
         if (v[0] < 1 || v[1] < 1 || !tta_count_ok(d.n, d.c, v[0], v[1])) return 2;
     }
-    for (int i = 0; i < d.k; ++i) d.logits[i] = (const float*)read_block(f, (size_t)d.n * d.c * d.h[i] * d.w[i] * sizeof(float));
+    for (int i = 0; i < d.k; ++i) d.logits[i] = (const float*)read_block(f, (size_t)d.n * d.c * d.h[i] * d.w[i] * sizeof(float), &g_blocks);
     const size_t plane = (size_t)d.H * d.W, pix = (size_t)d.n * plane;
     if (d.label_dtype != CMS_LABEL_U8 && d.label_dtype != CMS_LABEL_I64) return 2;
-    void* labels = read_block(f, pix * (d.label_dtype == CMS_LABEL_I64 ? 8 : 1));
+    void* labels = read_block(f, pix * (d.label_dtype == CMS_LABEL_I64 ? 8 : 1), &g_blocks);
     fclose(f);
     // the tables are sized for what the request CLAIMS only when the claim is inside the limits (else the check refuses first)
     const int nb = d.nb >= 1 && d.nb <= CMS_CALIB_MAX_BINS ? d.nb : 1, nt = d.nt >= 1 && d.nt <= CMS_CALIB_MAX_TEMPS ? d.nt : 1;

@@ -18,14 +18,9 @@
 #include <string.h>
 
 #include "../../cutmix-semisup-seg_amd/csrc/cps_math.hpp"
+#include "../hostcheck_common.hpp"
 
 using namespace cms;
-
-static void* read_block(FILE* f, size_t bytes) {
-    void* p = malloc(bytes ? bytes : 1);
-    if (!p || fread(p, 1, bytes, f) != bytes) exit(1);
-    return p;
-}
 
 template <int CT, bool IDENT, bool VEC>
 static void walk(const CpsArgs& a, int64_t* stats) {

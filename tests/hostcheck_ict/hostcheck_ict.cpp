@@ -6,7 +6,7 @@
 // confidence weight of --conf_per_pixel) can be checked against tests/_ict_refs.py on a CPU-only machine. The kernels'
 // indexing, reductions and LDS tiling are covered by the `-m gpu` tests.
 //
-// Build: see the Makefile (shared object for the test; `make asan` runs a stand-alone driver under ASan + UBSan).
+// Build: tests/_hostcheck.py (shared object for the tests; `--sanitize`: the stand-alone driver below under ASan + UBSan).
 #include <stdint.h>
 #include <stddef.h>
 #include <vector>

@@ -6,7 +6,7 @@
 // aug_pairs.pair_rows writes and the mask mode can be checked against oracle/augment.py on a CPU-only machine. The kernels'
 // indexing and launch geometry are covered by the `-m gpu` tests.
 //
-// Build: see the Makefile (shared object for the test; `make asan` runs a stand-alone driver under ASan + UBSan over an exactly
+// Build: tests/_hostcheck.py (shared object for the tests; `--sanitize`: a stand-alone driver under ASan + UBSan over an exactly
 // sized pool whose last entry ends at the end of its allocation).
 #include <stdint.h>
 #include <stddef.h>

@@ -16,15 +16,10 @@
 #include <string.h>
 
 #include "../../cutmix-semisup-seg_amd/csrc/surface_math.hpp"
+#include "../hostcheck_common.hpp"
 
 using namespace cms;
 typedef unsigned long long u64;
-
-static void* read_block(FILE* f, size_t bytes) {
-    void* p = malloc(bytes ? bytes : 1);
-    if (!p || fread(p, 1, bytes, f) != bytes) exit(1);
-    return p;
-}
 
 int main(int argc, char** argv) {
     if (argc != 3) {

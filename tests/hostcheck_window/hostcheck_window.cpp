@@ -24,28 +24,11 @@
 #include <string.h>
 
 #include "../../cutmix-semisup-seg_amd/csrc/window_math.hpp"
+#include "../hostcheck_common.hpp"
 
 using namespace cms;
 
-// every heap block of the run, freed when main returns on whichever path (a refusal included): the sanitizer build counts leaks
-struct Blocks {
-    void* p[64];
-    int n = 0;
-    void* keep(void* q) {
-        if (!q || n >= 64) exit(1);
-        return p[n++] = q;
-    }
-    ~Blocks() {
-        for (int i = 0; i < n; ++i) free(p[i]);
-    }
-};
-static Blocks g_blocks;
-
-static void* read_block(FILE* f, size_t bytes) {
-    void* p = g_blocks.keep(malloc(bytes ? bytes : 1));
-    if (fread(p, 1, bytes, f) != bytes) exit(1);
-    return p;
-}
+static Blocks g_blocks;          // every heap block of the run (hostcheck_common.hpp)
 
 static int vote(FILE* f, const char* result) {
     int32_t head[11];
@@ -72,11 +55,11 @@ static int vote(FILE* f, const char* result) {
         int64_t count;
         if (fread(&count, sizeof(int64_t), 1, f) != 1) return 1;
         if (count != (int64_t)d.n * d.gy[i] * d.gx[i] * d.c * d.hl[i] * d.wl[i]) return 3;
-        d.logits[i] = (const float*)read_block(f, (size_t)count * sizeof(float));
+        d.logits[i] = (const float*)read_block(f, (size_t)count * sizeof(float), &g_blocks);
     }
     const size_t plane = (size_t)d.H * d.W, pix = (size_t)d.n * plane;
     if (d.label_dtype != CMS_LABEL_U8 && d.label_dtype != CMS_LABEL_I64) return 2;
-    void* labels = read_block(f, pix * (d.label_dtype == CMS_LABEL_I64 ? 8 : 1));
+    void* labels = read_block(f, pix * (d.label_dtype == CMS_LABEL_I64 ? 8 : 1), &g_blocks);
     int64_t* cm = (int64_t*)g_blocks.keep(calloc((size_t)d.c * d.c, sizeof(int64_t)));
     uint8_t* pred = (uint8_t*)g_blocks.keep(malloc(pix));
     float* out = (float*)g_blocks.keep(malloc(pix * d.c * sizeof(float)));
@@ -145,7 +128,7 @@ static int crop(FILE* f, const char* result) {
     if (win_check_crop(&probe, &probe, n, c, H, W, Hv, Wv, wh, ww, sh, sw, CMS_F32)) return 2;
     const int gy = win_count(Hv, wh, sh), gx = win_count(Wv, ww, sw), eh = win_extent(Hv, wh), ew = win_extent(Wv, ww);
     const size_t total = (size_t)n * gy * gx * c * eh * ew;
-    const float* src = (const float*)read_block(f, (size_t)n * c * H * W * sizeof(float));
+    const float* src = (const float*)read_block(f, (size_t)n * c * H * W * sizeof(float), &g_blocks);
     float* dst = (float*)g_blocks.keep(malloc(total * sizeof(float)));
     for (size_t i = 0; i < total; ++i) dst[i] = NAN;
     for (size_t idx = 0; idx < total; ++idx) {

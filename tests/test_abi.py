@@ -11,6 +11,7 @@ import tempfile
 import pytest
 
 from conftest import REPO
+import _hostcheck
 
 HEADER = os.path.join(REPO, 'include', 'cutmixseg.h')
 
@@ -49,11 +50,7 @@ int main(void) {
   return 0;
 }'''
     with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, 't.c')
-        open(src, 'w').write(prog)
-        exe = os.path.join(d, 't')
-        subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), src, '-o', exe])
-        out = subprocess.check_output([exe]).decode().split()
+        out = subprocess.check_output([_hostcheck.compile_against_header(prog, d)]).decode().split()
     sizes = [int(x) for x in out]
     assert sizes[0] == ctypes.sizeof(_lib.ConsistencyDesc)
     assert sizes[1] == ctypes.sizeof(_lib.CeDesc)

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import REPO, load_golden_json
+import _hostcheck
 import _aug_refs as refs
 
 AUG_SYMBOLS = ('cms_aug_workspace_bytes', 'cms_aug_fwd', 'cms_aug_bwd')
@@ -208,12 +209,7 @@ def test_aug_desc_layout_matches_the_c_compiler():
         prog += '  printf("%zu\\n", offsetof(cms_aug_desc, {}));\n'.format(f)
     prog += '  return 0;\n}\n'
     with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, 't.c')
-        with open(src, 'w') as fh:
-            fh.write(prog)
-        exe = os.path.join(d, 't')
-        subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), src, '-o', exe])
-        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+        out = [int(x) for x in subprocess.check_output([_hostcheck.compile_against_header(prog, d)]).decode().split()]
     assert out[0] == ctypes.sizeof(_lib.AugDesc)
     assert out[1:] == [getattr(_lib.AugDesc, f).offset for f in fields]
 
@@ -306,9 +302,7 @@ def test_aug_step_refuses_data_parallel_runs(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------- tile facts
 @pytest.fixture(scope='module')
 def hc():
-    d = os.path.join(REPO, 'tests', 'hostcheck_aug')
-    subprocess.check_call(['make', '-s', '-C', d])
-    return ctypes.CDLL(os.path.join(d, '_build', 'libhostcheck_aug.so'))
+    return _hostcheck.load('hostcheck_aug')
 
 
 def test_gpu_geometries_reach_the_routes_they_are_meant_to(hc):

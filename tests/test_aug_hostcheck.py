@@ -8,17 +8,15 @@ Tolerances: the project's own for this arithmetic (tests/test_hostcheck.py::test
 loss rel 2e-5, rate abs 2e-6, gradient rtol 5e-4 with atol 5e-6 * max|want|.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO
+import _hostcheck
 import _aug_refs as refs
 
-HC_DIR = os.path.join(REPO, 'tests', 'hostcheck_aug')
 LOSS_ID = dict(var=0, logits_var=1, logits_smoothl1=2, bce=3, kld=4)
 MODES = {'default': (0.6, False), 'per_pixel': (0.6, True), 'no_thresh': (0.0, False)}
 N, h, w, H, W = 3, 6, 7, 41, 50
@@ -33,8 +31,7 @@ THETAS = {
 
 @pytest.fixture(scope='module')
 def hc():
-    subprocess.check_call(['make', '-s', '-C', HC_DIR])
-    return ctypes.CDLL(os.path.join(HC_DIR, '_build', 'libhostcheck_aug.so'))
+    return _hostcheck.load('hostcheck_aug')
 
 
 def _p(a, ty=ctypes.c_float):
@@ -184,3 +181,9 @@ def test_missing_um0_is_the_zero_padded_ones_mask(hc):
     b = run_aug(hc, _f32(ls), _f32(lt), xf, ones, _f32(um1), False, 'var', 0.6, False, gscale=1e-3)
     np.testing.assert_array_equal(a[0], b[0])
     np.testing.assert_array_equal(a[1], b[1])
+
+
+def test_stand_alone_under_the_host_sanitizers():
+    """The checker behind its own main, built with -fsanitize=address,undefined, as a process of its own: it draws its own small
+    inputs and ends non-zero on a non-finite result or a sanitizer report."""
+    assert subprocess.call([_hostcheck.build('hostcheck_aug', sanitize=True)]) == 0

@@ -1,13 +1,13 @@
 """
 CPU-only: the boundary scores (Boundary IoU, trimap IoU) without a GPU.
 
-  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout against gcc; the workspace sizes;
+  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout in C; the workspace sizes;
     every CMS_EINVAL case (decided before any HIP call), with its message
   * ops.boundary_confusion's refusals; evaluation.parse_boundary_widths, good and bad; EvaluatorBoundary's constructor
   * eval_seg refusing a malformed --boundary_width before the GPU (and before the model file is opened)
   * the reference itself (tests/_boundary_refs.py): padding cancels, the band is the distance map thresholded
-  * csrc/boundary_math.hpp -- the functions the kernels of csrc/boundary.hip are made of -- driven on the host by a small program this
-    file compiles itself (tests/hostcheck_boundary) over every pixel of the GPU test's cases, against the scipy erosion reference;
+  * csrc/boundary_math.hpp -- the functions the kernels of csrc/boundary.hip are made of -- driven on the host by a small program of
+    its own (tests/hostcheck_boundary) over every pixel of the GPU test's cases, against the scipy erosion reference;
     and the same stand-alone program once more under the host's address and undefined-behaviour sanitizers
 """
 import ctypes
@@ -20,10 +20,9 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _boundary_refs as R
 
-SRC = os.path.join(REPO, 'tests', 'hostcheck_boundary', 'hostcheck_boundary.cpp')
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
 
 
 # ------------------------------------------------------------------------------------------------------------------ ABI
@@ -46,9 +45,7 @@ def test_descriptor_layout_matches_the_c_compiler(tmp_path):
                       'dist_pred', 'workspace', 'workspace_bytes']
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "cutmixseg.h"\nint main(void) { printf("%zu", sizeof(cms_boundary_desc));\n'
             + ''.join('printf(" %zu", offsetof(cms_boundary_desc, {}));\n'.format(f) for f in fields) + 'return 0; }\n')
-    (tmp_path / 't.c').write_text(prog)
-    subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), str(tmp_path / 't.c'), '-o', str(tmp_path / 't')])
-    sizes = [int(v) for v in subprocess.check_output([str(tmp_path / 't')]).decode().split()]
+    sizes = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, tmp_path)]).decode().split()]
     D = _lib.BoundaryDesc
     assert sizes == [ctypes.sizeof(D)] + [getattr(D, f).offset for f in fields]
 
@@ -227,43 +224,27 @@ def test_reference_padding_cancels():
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-def _request(path, truth, pred, classes, widths, **over):
+def _request(truth, pred, classes, widths, **over):
+    """-> (header, blocks)"""
     n, h, w = truth.shape
     head = dict(n=n, h=h, w=w, c=classes, ignore=255, k=widths.shape[1], maps=1)
     head.update(over)
-    with open(path, 'wb') as f:
-        f.write(struct.pack('<7i', head['n'], head['h'], head['w'], head['c'], head['ignore'], head['k'], head['maps']))
-        f.write(np.ascontiguousarray(widths, dtype=np.int32).tobytes())
-        f.write(np.ascontiguousarray(truth, dtype=np.uint8).tobytes())
-        f.write(np.ascontiguousarray(pred, dtype=np.uint8).tobytes())
+    header = struct.pack('<7i', head['n'], head['h'], head['w'], head['c'], head['ignore'], head['k'], head['maps'])
+    return header, [(widths, np.int32), (truth, np.uint8), (pred, np.uint8)]
 
 
-def _result(path, shape, c, k):
-    pix = int(np.prod(shape))
-    raw = open(path, 'rb').read()
-    nb, nt = k * (c + 1) ** 2, k * c * c
-    assert len(raw) == 2 * pix + 8 * (nb + nt)
-    return dict(dist_truth=np.frombuffer(raw[:pix], dtype=np.uint8).reshape(shape),
-                dist_pred=np.frombuffer(raw[pix:2 * pix], dtype=np.uint8).reshape(shape),
-                bcm=np.frombuffer(raw[2 * pix:2 * pix + 8 * nb], dtype=np.int64).reshape(k, c + 1, c + 1),
-                tcm=np.frombuffer(raw[2 * pix + 8 * nb:], dtype=np.int64).reshape(k, c, c))
+def _result(raw, shape, c, k):
+    return _hostcheck.split(raw, [('dist_truth', np.uint8, shape), ('dist_pred', np.uint8, shape), ('bcm', np.int64, (k, c + 1, c + 1)),
+                                  ('tcm', np.int64, (k, c, c))])
 
 
 @pytest.fixture(scope='module')
-def hostcheck(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_boundary')
-    exe = str(d / 'hostcheck_boundary')
-    subprocess.check_call(GXX + [SRC, '-o', exe])
-    count = [0]
+def hostcheck():
+    exe = _hostcheck.build('hostcheck_boundary')
 
     def run(inp, program=exe, expect_code=0, **over):
-        count[0] += 1
-        req, res = str(d / 'req{}.bin'.format(count[0])), str(d / 'res{}.bin'.format(count[0]))
-        _request(req, inp['truth'], inp['pred'], inp['c'], inp['widths'], **over)
-        code = subprocess.call([program, req, res])
-        assert code == expect_code, code
-        return _result(res, inp['truth'].shape, inp['c'], inp['widths'].shape[1]) if code == 0 else None
-    run.dir = d
+        raw = _hostcheck.run(program, *_request(inp['truth'], inp['pred'], inp['c'], inp['widths'], **over), expect_code=expect_code)
+        return None if raw is None else _result(raw, inp['truth'].shape, inp['c'], inp['widths'].shape[1])
     return run
 
 
@@ -320,8 +301,7 @@ def test_host_driver_refuses_what_the_library_refuses(hostcheck):
 
 def test_stand_alone_under_the_host_sanitizers(hostcheck):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = str(hostcheck.dir / 'hostcheck_boundary_asan')
-    subprocess.check_call(GXX + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', SRC, '-o', exe])
+    exe = _hostcheck.build('hostcheck_boundary', sanitize=True)
     for name in ('one_pixel', 'row_of_7', 'c5_void', 'c21_void', 'wide', 'tall', 'long_row'):
         inp, ref = R.case(name)
         _same(hostcheck(inp, program=exe), ref)

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _calib_refs as R
 import _pascal_tree
 
@@ -39,9 +40,7 @@ def test_descriptor_layout_matches_the_c_compiler(tmp_path):
     fields = ('h', 'n', 'labels', 'pred_out', 'nb', 'edges', 'nt', 'temps', 'hist', 'scores')
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "cutmixseg.h"\nint main(void) { printf("%zu' + ' %zu' * len(fields) +
             '\\n", sizeof(cms_calib_desc)' + ''.join(', offsetof(cms_calib_desc, {})'.format(f) for f in fields) + '); return 0; }\n')
-    (tmp_path / 't.c').write_text(prog)
-    subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), str(tmp_path / 't.c'), '-o', str(tmp_path / 't')])
-    sizes = [int(v) for v in subprocess.check_output([str(tmp_path / 't')]).decode().split()]
+    sizes = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, tmp_path)]).decode().split()]
     D = _lib.CalibDesc
     assert sizes == [ctypes.sizeof(D)] + [getattr(D, f).offset for f in fields]
 

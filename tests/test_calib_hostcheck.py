@@ -1,6 +1,6 @@
 """
-CPU-only: csrc/calib_math.hpp -- the functions the kernel of csrc/calib.hip is made of -- driven on the host by a small program this
-file compiles itself (tests/hostcheck_calib) over every case of the GPU test, against the fp64 restatement (tests/_calib_refs.py) under
+CPU-only: csrc/calib_math.hpp -- the functions the kernel of csrc/calib.hip is made of -- driven on the host by a small program of
+its own (tests/hostcheck_calib) over every case of the GPU test, against the fp64 restatement (tests/_calib_refs.py) under
 its acceptance rule; the bit-for-bit claims of the definition (the confidence of the consistency kernels, the cross entropy of the
 supervised loss, the prediction of the vote); every descriptor refusal; and the same stand-alone program once more under the host's
 address and undefined-behaviour sanitizers.
@@ -8,17 +8,16 @@ address and undefined-behaviour sanitizers.
 import numpy as np
 import pytest
 
+import _hostcheck
 import _calib_refs as R
 
 
 @pytest.fixture(scope='module')
-def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_calib')
-    exe = R.hostcheck_build(d)
+def host():
+    exe = _hostcheck.build('hostcheck_calib')
 
     def run(inp, program=exe, **kw):
-        return R.hostcheck_run(program, d, inp, **kw)
-    run.dir = d
+        return R.hostcheck_run(program, inp, **kw)
     return run
 
 
@@ -74,7 +73,7 @@ def test_more_than_48_bins_is_refused(host):
 
 def test_stand_alone_under_the_host_sanitizers(host):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = R.hostcheck_build(host.dir, sanitize=True)
+    exe = _hostcheck.build('hostcheck_calib', sanitize=True)
     for name in ('k1_c2_T1', 'k1_c21_T0.5', 'k2_c19_nt8', 'k1_c19_nt8_i64', 'lds_worst_k16_c64_nb48', 'nb1_k2_c19', 'one_pixel_k1',
                  'one_pixel_k2', 'all_ignored_k5', 'hot_k5_c64'):
         inp, ref = R.case(name)

@@ -1,14 +1,14 @@
 """
 CPU-only: ClassMix without a GPU.
 
-  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout against gcc; the workspace sizes;
+  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout in C; the workspace sizes;
     every CMS_EINVAL case (decided before any HIP call)
   * ops.classmix_mask's refusals; mask_gen.ClassMixGenerator's draw order
   * the command line of train_seg_semisup_classmix_mt: the CutMix trainer's minus the five --boxmask_* options and --mask_prop_range;
     its refusals, which come before the GPU
   * the margins of the cases the GPU test shares (tests/_classmix_refs.py)
-  * csrc/classmix_math.hpp -- the functions the kernels of csrc/classmix.hip are made of -- driven on the host by a small program this
-    file compiles itself (tests/hostcheck_classmix) over every pixel of the GPU test's cases and over sizes at which the walk takes
+  * csrc/classmix_math.hpp -- the functions the kernels of csrc/classmix.hip are made of -- driven on the host by a small program of
+    its own (tests/hostcheck_classmix) over every pixel of the GPU test's cases and over sizes at which the walk takes
     another shape, against the fp64 restatement; and the same stand-alone program once more under the host's address and
     undefined-behaviour sanitizers
 """
@@ -22,10 +22,9 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _classmix_refs as R
 
-SRC = os.path.join(REPO, 'tests', 'hostcheck_classmix', 'hostcheck_classmix.cpp')
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
 
 
 # ------------------------------------------------------------------------------------------------------------------ ABI
@@ -48,9 +47,7 @@ def test_descriptor_layout_matches_the_c_compiler(tmp_path):
                       'chosen_out', 'workspace', 'workspace_bytes']
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "cutmixseg.h"\nint main(void) { printf("%zu", sizeof(cms_classmix_desc));\n'
             + ''.join('printf(" %zu", offsetof(cms_classmix_desc, {}));\n'.format(f) for f in fields) + 'return 0; }\n')
-    (tmp_path / 't.c').write_text(prog)
-    subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), str(tmp_path / 't.c'), '-o', str(tmp_path / 't')])
-    sizes = [int(v) for v in subprocess.check_output([str(tmp_path / 't')]).decode().split()]
+    sizes = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, tmp_path)]).decode().split()]
     D = _lib.ClassMixDesc
     assert sizes == [ctypes.sizeof(D)] + [getattr(D, f).offset for f in fields]
 
@@ -264,43 +261,29 @@ def test_reference_properties():
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-def _request(path, logits, keys, size, align, valid=None, **over):
+def _request(logits, keys, size, align, valid=None, **over):
+    """-> (header, blocks)"""
     n, c, h, w = logits.shape
     head = dict(n=n, c=c, h=h, w=w, H=size[0], W=size[1])
     head.update(over)
-    with open(path, 'wb') as f:
-        f.write(struct.pack('<8i', head['n'], head['c'], head['h'], head['w'], head['H'], head['W'], int(align), int(valid is not None)))
-        f.write(np.ascontiguousarray(keys, dtype=np.float64).tobytes())
-        f.write(np.ascontiguousarray(logits, dtype=np.float32).tobytes())
-        if valid is not None:
-            f.write(np.ascontiguousarray(valid, dtype=np.float32).tobytes())
+    header = struct.pack('<8i', head['n'], head['c'], head['h'], head['w'], head['H'], head['W'], int(align), int(valid is not None))
+    return header, [(keys, np.float64), (logits, np.float32)] + ([(valid, np.float32)] if valid is not None else [])
 
 
-def _result(path, n, size):
-    pix = n * size[0] * size[1]
-    raw = open(path, 'rb').read()
-    assert len(raw) == pix + 16 * n + 4 * pix
-    pred = np.frombuffer(raw[:pix], dtype=np.uint8).reshape((n,) + tuple(size))
-    sets = np.frombuffer(raw[pix:pix + 16 * n], dtype=np.uint64).reshape(2, n)
-    mask = np.frombuffer(raw[pix + 16 * n:], dtype=np.float32).reshape((n, 1) + tuple(size))
-    return dict(pred=pred, present=[int(v) for v in sets[0]], chosen=[int(v) for v in sets[1]], mask=mask)
+def _result(raw, n, size):
+    out = _hostcheck.split(raw, [('pred', np.uint8, (n,) + tuple(size)), ('sets', np.uint64, (2, n)),
+                                 ('mask', np.float32, (n, 1) + tuple(size))])
+    sets = out['sets']
+    return dict(pred=out['pred'], present=[int(v) for v in sets[0]], chosen=[int(v) for v in sets[1]], mask=out['mask'])
 
 
 @pytest.fixture(scope='module')
-def hostcheck(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_classmix')
-    exe = str(d / 'hostcheck_classmix')
-    subprocess.check_call(GXX + [SRC, '-o', exe])
-    count = [0]
+def hostcheck():
+    exe = _hostcheck.build('hostcheck_classmix')
 
     def run(logits, keys, size, align, valid=None, program=exe, expect_code=0, **over):
-        count[0] += 1
-        req, res = str(d / 'req{}.bin'.format(count[0])), str(d / 'res{}.bin'.format(count[0]))
-        _request(req, logits, keys, size, align, valid, **over)
-        code = subprocess.call([program, req, res])
-        assert code == expect_code, code
-        return _result(res, logits.shape[0], size) if code == 0 else None
-    run.dir = d
+        raw = _hostcheck.run(program, *_request(logits, keys, size, align, valid, **over), expect_code=expect_code)
+        return None if raw is None else _result(raw, logits.shape[0], size)
     return run
 
 
@@ -365,8 +348,7 @@ def test_host_driver_refuses_what_the_library_refuses(hostcheck):
 
 def test_stand_alone_under_the_host_sanitizers(hostcheck):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = str(hostcheck.dir / 'hostcheck_classmix_asan')
-    subprocess.check_call(GXX + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', SRC, '-o', exe])
+    exe = _hostcheck.build('hostcheck_classmix', sanitize=True)
     for name in ('main_nac', 'c64', 'c1', 'ident'):
         inp, ref = R.case(name)
         _same(hostcheck(inp['logits'], inp['keys'], inp['size'], inp['align'], program=exe), ref)

@@ -2,7 +2,7 @@
 CPU-only: the Cityscapes converter without a GPU.
 
   * csrc/convert_math.hpp -- the functions the kernels of csrc/convert.hip are made of -- driven on the host by a small program
-    this file compiles itself (tests/hostcheck_convert), against the numpy restatement of the reference's arithmetic
+    of its own (tests/hostcheck_convert), against the numpy restatement of the reference's arithmetic
     (tests/_convert_refs.py): every possible block sum for d = 1..8, the vote with its ties, word and byte paths, short groups
   * the two new ABI symbols: declared, exported, prototyped, version 101; every CMS_EINVAL case (decided before any HIP call)
   * every refusal of the converter's command line, with the GPU booby-trapped
@@ -10,39 +10,30 @@ CPU-only: the Cityscapes converter without a GPU.
 import ctypes
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _convert_refs as R
 import _zip_archives as Z
 
 
 @pytest.fixture(scope='module')
-def hostcheck(tmp_path_factory):
+def hostcheck():
     """the host driver, compiled with the host C++ compiler -> run(kind, x, d, in_off, out_off) -> output array"""
-    d = tmp_path_factory.mktemp('hostcheck_convert')
-    exe = str(d / 'hostcheck_convert')
-    subprocess.check_call(['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas',      # `#pragma unroll` is hipcc's
-                           os.path.join(REPO, 'tests', 'hostcheck_convert', 'hostcheck_convert.cpp'), '-o', exe])
-    count = [0]
+    exe = _hostcheck.build('hostcheck_convert')
 
     def run(x, d_, in_off=0, out_off=0, expect_code=0):
         x = np.ascontiguousarray(x, dtype=np.uint8)
         kind = 0 if x.ndim == 4 else 1
         n, h, w = x.shape[:3]
-        count[0] += 1
-        req, res = str(d / 'req{}.bin'.format(count[0])), str(d / 'res{}.bin'.format(count[0]))
-        with open(req, 'wb') as f:
-            f.write(struct.pack('<7i', kind, n, h, w, d_, in_off, out_off) + x.tobytes())
-        code = subprocess.call([exe, req, res])
-        assert code == expect_code, code
-        if code:
+        raw = _hostcheck.run(exe, struct.pack('<7i', kind, n, h, w, d_, in_off, out_off), [(x, np.uint8)], expect_code)
+        if raw is None:
             return None
         shape = (n, h // d_, w // d_) + ((3,) if kind == 0 else ())
-        return np.fromfile(res, dtype=np.uint8).reshape(shape)
+        return _hostcheck.split(raw, [('out', np.uint8, shape)])['out']
     return run
 
 

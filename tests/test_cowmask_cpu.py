@@ -5,8 +5,8 @@ CPU-only: CowMask without a GPU.
   * mask_gen.CowMaskGenerator: the draw order of the host scalars, the tap table, the refusals
   * the two new ABI symbols: declared, exported, prototyped, version 101; every CMS_EINVAL case (decided before any HIP call)
   * the command line of train_seg_semisup_cowmask_mt: the CutMix trainer's with --boxmask_* replaced in place by --cow_sigma_range
-  * csrc/cowmask_math.hpp -- the functions the kernels of csrc/cowmask.hip are made of -- driven on the host by a small program this
-    file compiles itself (tests/hostcheck_cowmask) over every pixel of the GPU test's cases, against the oracle; and the same
+  * csrc/cowmask_math.hpp -- the functions the kernels of csrc/cowmask.hip are made of -- driven on the host by a small program of
+    its own (tests/hostcheck_cowmask) over every pixel of the GPU test's cases, against the oracle; and the same
     stand-alone program once more under the host's address and undefined-behaviour sanitizers
 """
 import ctypes
@@ -19,10 +19,9 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _cowmask_refs as R
 
-SRC = os.path.join(REPO, 'tests', 'hostcheck_cowmask', 'hostcheck_cowmask.cpp')
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` is hipcc's
 
 
 # ------------------------------------------------------------------------------------------------------------------ oracle
@@ -226,38 +225,25 @@ def test_command_refusals_come_before_the_gpu(tmp_path, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-def _request(path, inp):
+def _request(inp):
+    """-> (header, blocks)"""
     n, h, w = inp['noise'].shape
-    with open(path, 'wb') as f:
-        f.write(struct.pack('<4i', n, h, w, inp['radius']))
-        f.write(np.ascontiguousarray(inp['taps'], dtype=np.float64).tobytes())
-        f.write(np.ascontiguousarray(inp['factor'], dtype=np.float64).tobytes())
-        f.write(np.ascontiguousarray(inp['noise'], dtype=np.float32).tobytes())
+    return struct.pack('<4i', n, h, w, inp['radius']), [(inp['taps'], np.float64), (inp['factor'], np.float64), (inp['noise'], np.float32)]
 
 
-def _result(path, inp):
+def _result(raw, inp):
     n, h, w = inp['noise'].shape
-    raw = open(path, 'rb').read()
-    assert len(raw) == n * h * w * 4 + n * 2 * 8
-    return (np.frombuffer(raw[:n * h * w * 4], dtype=np.float32).reshape(n, 1, h, w),
-            np.frombuffer(raw[n * h * w * 4:], dtype=np.float64).reshape(n, 2))
+    out = _hostcheck.split(raw, [('mask', np.float32, (n, 1, h, w)), ('stats', np.float64, (n, 2))])
+    return out['mask'], out['stats']
 
 
 @pytest.fixture(scope='module')
-def hostcheck(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_cowmask')
-    exe = str(d / 'hostcheck_cowmask')
-    subprocess.check_call(GXX + [SRC, '-o', exe])
-    count = [0]
+def hostcheck():
+    exe = _hostcheck.build('hostcheck_cowmask')
 
     def run(inp, program=exe, expect_code=0):
-        count[0] += 1
-        req, res = str(d / 'req{}.bin'.format(count[0])), str(d / 'res{}.bin'.format(count[0]))
-        _request(req, inp)
-        code = subprocess.call([program, req, res])
-        assert code == expect_code, code
-        return _result(res, inp) if code == 0 else None
-    run.dir = d
+        raw = _hostcheck.run(program, *_request(inp), expect_code=expect_code)
+        return None if raw is None else _result(raw, inp)
     return run
 
 
@@ -304,8 +290,7 @@ def test_host_driver_refuses_what_the_library_refuses(hostcheck):
 
 def test_stand_alone_under_the_host_sanitizers(hostcheck, oracle):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = str(hostcheck.dir / 'hostcheck_cowmask_asan')
-    subprocess.check_call(GXX + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', SRC, '-o', exe])
+    exe = _hostcheck.build('hostcheck_cowmask', sanitize=True)
     for inp, want in [(oracle[0][0], oracle[0][1]), (oracle[1][0], oracle[1][1])]:
         got_mask, _ = hostcheck(inp, program=exe)
         assert np.array_equal(got_mask, want)

@@ -1,7 +1,7 @@
 """
 CPU-only: cross pseudo supervision without a GPU.
 
-  * the new ABI symbol: declared, exported, prototyped, version 101; the descriptor's layout against gcc; every CMS_EINVAL case
+  * the new ABI symbol: declared, exported, prototyped, version 101; the descriptor's layout in C; every CMS_EINVAL case
     (decided before any HIP call)
   * ops.cps_labels' refusals; CrossPseudoStep's refusal of more than one process
   * the command line of train_seg_semisup_cps: the CutMix trainer's with six options removed and two defaults changed; its refusals, which come before the GPU
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _cps_refs as R
 
 
@@ -37,9 +38,7 @@ def test_descriptor_layout_matches_the_c_compiler(tmp_path):
                       'n_boxes', 'invert', 'conf_thresh', 'label_a', 'label_b', 'stats']
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "cutmixseg.h"\nint main(void) { printf("%zu", sizeof(cms_cps_desc));\n'
             + ''.join('printf(" %zu", offsetof(cms_cps_desc, {}));\n'.format(f) for f in fields) + 'return 0; }\n')
-    (tmp_path / 't.c').write_text(prog)
-    subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), str(tmp_path / 't.c'), '-o', str(tmp_path / 't')])
-    sizes = [int(v) for v in subprocess.check_output([str(tmp_path / 't')]).decode().split()]
+    sizes = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, tmp_path)]).decode().split()]
     D = _lib.CpsDesc
     assert sizes == [ctypes.sizeof(D)] + [getattr(D, f).offset for f in fields]
 

@@ -1,6 +1,6 @@
 """
-CPU-only: csrc/cps_math.hpp -- the functions the kernel of csrc/cps.hip is made of -- driven on the host by a small program this file
-compiles itself (tests/hostcheck_cps) over every pixel of the GPU test's cases, against the fp64 restatement (tests/_cps_refs.py):
+CPU-only: csrc/cps_math.hpp -- the functions the kernel of csrc/cps.hip is made of -- driven on the host by a small program of its
+own (tests/hostcheck_cps) over every pixel of the GPU test's cases, against the fp64 restatement (tests/_cps_refs.py):
 labels and all four counts, no pixel left out. Then what a margin cannot hold: real ties on exactly representable values, NaN logits,
 a threshold that is exactly reached; the sizes at which the walk takes another shape; the refusals; and the same stand-alone program
 once more under the host's address and undefined-behaviour sanitizers.
@@ -9,18 +9,17 @@ import numpy as np
 import pytest
 
 import _cps_refs as R
+import _hostcheck
 
 CASES = [(name, align) for name in R.GEOMETRIES for align in (True, False)]
 
 
 @pytest.fixture(scope='module')
-def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_cps')
-    exe = R.hostcheck_build(d)
+def host():
+    exe = _hostcheck.build('hostcheck_cps')
 
     def run(logits, size, align, program=exe, **kw):
-        return R.hostcheck_run(program, d, logits, size, align, **kw)
-    run.dir = d
+        return R.hostcheck_run(program, logits, size, align, **kw)
     return run
 
 
@@ -138,7 +137,7 @@ def test_host_driver_refuses_what_the_library_refuses(host):
 
 def test_stand_alone_under_the_host_sanitizers(host):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = R.hostcheck_build(host.dir, sanitize=True)
+    exe = _hostcheck.build('hostcheck_cps', sanitize=True)
     for name, align, kind in (('main', False, 'rand'), ('main', True, 'box'), ('c64', True, 'xbox'), ('ident', True, 'rand'),
                               ('one', False, 'box'), ('tab2c19', True, 'rand'), ('c21', False, 'rand')):
         inp, ref = R.case(name, align, kind), R.reference(name, align, kind, True, R.TAU)

@@ -1,7 +1,7 @@
 """
 CPU-only: CRF refinement without a GPU.
 
-  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout against gcc; the workspace sizes;
+  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout in C; the workspace sizes;
     every CMS_EINVAL case (decided before any HIP call)
   * ops.crf_refine's refusals, crf.CRFParams' parsing, eval_seg's `--crf*` refusals (the GPU never initialised)
   * the margins of the cases the host-check and GPU tests share (tests/_crf_refs.py), and the 2 % condition
@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _pascal_tree
 import _crf_refs as R
 
@@ -43,9 +44,7 @@ def test_descriptor_layout_matches_the_c_compiler(tmp_path):
                       'pred_out', 'q_out', 'stats']
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "cutmixseg.h"\nint main(void) { printf("%zu", sizeof(cms_crf_desc));\n'
             + ''.join('printf(" %zu", offsetof(cms_crf_desc, {}));\n'.format(f) for f in fields) + 'return 0; }\n')
-    (tmp_path / 't.c').write_text(prog)
-    subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), str(tmp_path / 't.c'), '-o', str(tmp_path / 't')])
-    sizes = [int(v) for v in subprocess.check_output([str(tmp_path / 't')]).decode().split()]
+    sizes = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, tmp_path)]).decode().split()]
     D = _lib.CrfDesc
     assert sizes == [ctypes.sizeof(D)] + [getattr(D, f).offset for f in fields]
 

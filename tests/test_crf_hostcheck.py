@@ -1,23 +1,22 @@
 """
-CPU-only: csrc/crf_math.hpp -- the functions the kernels of csrc/crf.hip are made of -- driven on the host by a small program this file
-compiles itself (tests/hostcheck_crf) over every case of the GPU test, against the fp64 restatement (tests/_crf_refs.py): Q within B
+CPU-only: csrc/crf_math.hpp -- the functions the kernels of csrc/crf.hip are made of -- driven on the host by a small program of its
+own (tests/hostcheck_crf) over every case of the GPU test, against the fp64 restatement (tests/_crf_refs.py): Q within B
 at every element, labels and both counts equal, no pixel left out. Then the refusals, sizes at which the launch's tiles end, and the
 same stand-alone program once more under the host's address and undefined-behaviour sanitizers.
 """
 import numpy as np
 import pytest
 
+import _hostcheck
 import _crf_refs as R
 
 
 @pytest.fixture(scope='module')
-def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_crf')
-    exe = R.hostcheck_build(d)
+def host():
+    exe = _hostcheck.build('hostcheck_crf')
 
     def run(inp, program=exe, **kw):
-        return R.hostcheck_run(program, d, inp, **kw)
-    run.dir = d
+        return R.hostcheck_run(program, inp, **kw)
     return run
 
 
@@ -74,7 +73,7 @@ def test_host_driver_refuses_what_the_library_refuses(host):
 
 def test_stand_alone_under_the_host_sanitizers(host):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = R.hostcheck_build(host.dir, sanitize=True)
+    exe = _hostcheck.build('hostcheck_crf', sanitize=True)
     for name in ('c5_r2s3_t5_k3', 'c64_r5s3_t1_k3', 'c21_r5s16_t5_k3', 'tiny_5x7', 'one_pixel', 'full_canvas'):
         inp, ref = R.case(name)
         R.compare(host(inp, program=exe), ref)

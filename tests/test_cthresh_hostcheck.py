@@ -1,89 +1,56 @@
 """
 CPU-only: csrc/cthresh_math.hpp -- the per-pixel pieces and the update arithmetic the kernels of csrc/cthresh.hip are made of -- driven on
-the host by a small stand-alone program this file compiles itself (tests/hostcheck_cthresh), over every pixel of the GPU test's cases
+the host by a small stand-alone program of its own (tests/hostcheck_cthresh), over every pixel of the GPU test's cases
 against the fp64 restatement (tests/_cthresh_refs.py): k*, the pass bit, N_pred / N_pass exactly, S_conf / S_c within the bound; the
 update on hand-made integer tables; then what a margin cannot hold -- equal logits, a confidence exactly at its threshold, NaN logits,
 one class -- and the same program once more under the host's address and undefined-behaviour sanitizers. Nothing is loaded into Python.
 """
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import _cthresh_refs as R
-from conftest import REPO
+import _hostcheck
 
-SRC = os.path.join(REPO, 'tests', 'hostcheck_cthresh', 'hostcheck_cthresh.cpp')
-GXX = ['g++', '-O2', '-std=c++17', '-I', os.path.join(REPO, 'cutmix-semisup-seg_amd', 'csrc')]
-
-
-def _f32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).tobytes()
-
-
-def run_pixels(exe, d, l0, l1, thr, size, align, mode, ranges=None, mask=None, um0=None, um1=None, expect_code=0):
+def run_pixels(exe, l0, l1, thr, size, align, mode, ranges=None, mask=None, um0=None, um1=None, expect_code=0):
     n, c, h, w = l0.shape
     H, W = size
     nb = 0 if ranges is None else int(np.asarray(ranges).shape[1])
     flags = (1 if l1 is not None else 0) | (2 if mask is not None else 0) | (4 if um0 is not None else 0) | (8 if um1 is not None else 0)
-    blob = struct.pack('<10i', n, c, h, w, H, W, int(align), 0 if mode == 'mix' else 1, nb, flags) + _f32(l0)
-    if l1 is not None:
-        blob += _f32(l1)
-    blob += _f32(thr)
-    if ranges is not None:
-        blob += np.ascontiguousarray(ranges, dtype=np.int32).tobytes()
-    for m in (mask, um0, um1):
-        if m is not None:
-            blob += _f32(m)
-    fin, fout = str(d / 'in.bin'), str(d / 'out.bin')
-    open(fin, 'wb').write(blob)
-    rc = subprocess.run([exe, 'pixels', fin, fout]).returncode
-    assert rc == expect_code, rc
-    if rc:
+    header = struct.pack('<10i', n, c, h, w, H, W, int(align), 0 if mode == 'mix' else 1, nb, flags)
+    blocks = [(l0, np.float32)] + ([(l1, np.float32)] if l1 is not None else []) + [(thr, np.float32)]
+    blocks += [(ranges, np.int32)] if ranges is not None else []
+    blocks += [(m, np.float32) for m in (mask, um0, um1) if m is not None]
+    raw = _hostcheck.run(exe, header, blocks, expect_code, args=['pixels'])
+    if raw is None:
         return None
-    raw = open(fout, 'rb').read()
-    P = n * H * W
-    return dict(kstar=np.frombuffer(raw, np.int32, P).reshape(n, H, W), passed=np.frombuffer(raw, np.uint8, P, 4 * P).reshape(n, H, W) > 0,
-                table=[int(v) for v in np.frombuffer(raw, np.uint64, 2 + 3 * c, 5 * P)])
+    out = _hostcheck.split(raw, [('kstar', np.int32, (n, H, W)), ('passed', np.uint8, (n, H, W)), ('table', np.uint64, (2 + 3 * c,))])
+    return dict(kstar=out['kstar'], passed=out['passed'] > 0, table=[int(v) for v in out['table']])
 
 
-def run_update(exe, d, C, adaptive, lam, floor, ceil, state, thr, table, epoch, expect_code=0):
-    blob = (struct.pack('<2i3d', C, int(adaptive), lam, floor, ceil) + np.asarray(state, np.float64).tobytes() + _f32(thr) +
-            np.asarray(table, np.uint64).tobytes() + np.asarray(epoch, np.uint64).tobytes())
-    fin, fout = str(d / 'uin.bin'), str(d / 'uout.bin')
-    open(fin, 'wb').write(blob)
-    rc = subprocess.run([exe, 'update', fin, fout]).returncode
-    assert rc == expect_code, rc
-    if rc:
+def run_update(exe, C, adaptive, lam, floor, ceil, state, thr, table, epoch, expect_code=0):
+    header = struct.pack('<2i3d', C, int(adaptive), lam, floor, ceil)
+    blocks = [(state, np.float64), (thr, np.float32), (table, np.uint64), (epoch, np.uint64)]
+    raw = _hostcheck.run(exe, header, blocks, expect_code, args=['update'])
+    if raw is None:
         return None
-    raw = open(fout, 'rb').read()
-    o = 8 * (1 + C)
-    return (list(np.frombuffer(raw, np.float64, 1 + C)), list(np.frombuffer(raw, np.float32, C, o)),
-            [int(v) for v in np.frombuffer(raw, np.uint64, 2 + 3 * C, o + 4 * C)],
-            [int(v) for v in np.frombuffer(raw, np.uint64, 1 + 2 * C, o + 4 * C + 8 * (2 + 3 * C))])
+    out = _hostcheck.split(raw, [('state', np.float64, (1 + C,)), ('thr', np.float32, (C,)), ('table', np.uint64, (2 + 3 * C,)),
+                                 ('epoch', np.uint64, (1 + 2 * C,))])
+    return list(out['state']), list(out['thr']), [int(v) for v in out['table']], [int(v) for v in out['epoch']]
 
 
 @pytest.fixture(scope='module')
-def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_cthresh')
-    exe = str(d / 'hostcheck_cthresh')
-    subprocess.check_call(GXX + [SRC, '-o', exe])
-
-    class H(object):
-        pass
-    h = H()
-    h.dir, h.exe = d, exe
-    return h
+def host():
+    return _hostcheck.build('hostcheck_cthresh')
 
 
-def _check_case(host, exe, case, vec):
+def _check_case(exe, case, vec):
     name, mode, fn, pp, given = case
     N, C, h, w, H, W, ac = R.geometry(name)
     i, ref, rows = R.inputs(case), R.reference(case, vec), R.rows_of(case)
     assert ref['gap'] >= R.GAP and ref['conf_margin'] >= R.CONF
-    got = run_pixels(exe, host.dir, i['l0'], i['l1'], ref['thr'], (H, W), ac, mode, i['ranges'], i['mask'], i['um0'], i.get('um1'))
+    got = run_pixels(exe, i['l0'], i['l1'], ref['thr'], (H, W), ac, mode, i['ranges'], i['mask'], i['um0'], i.get('um1'))
     assert np.array_equal(got['kstar'], rows['kstar'])
     want_pass = rows['conf'] >= ref['thr'].astype(np.float64)[rows['kstar']]
     assert np.array_equal(got['passed'], want_pass)
@@ -96,7 +63,7 @@ def _check_case(host, exe, case, vec):
 @pytest.mark.parametrize('case', R.CASES + [R.REFUSED], ids=R.case_id)
 def test_header_on_the_host_vs_restatement_every_pixel(host, case):
     for vec in R.VECTORS:
-        _check_case(host, host.exe, case, vec)
+        _check_case(host, case, vec)
 
 
 # ------------------------------------------------------------------------------------------------------------ the update
@@ -126,7 +93,7 @@ def test_update_on_hand_made_tables(host, lam, floor, ceil):
         state, thr = R.initial(C, floor, ceil)
         epoch = [7] + [3] * (2 * C)
         want = R.update(state, thr, table, epoch, C, True, lam, floor, ceil)
-        got = run_update(host.exe, host.dir, C, True, lam, floor, ceil, state, thr, table, epoch)
+        got = run_update(host, C, True, lam, floor, ceil, state, thr, table, epoch)
         _same_update(got, want, C)
         assert got[2] == [0] * (2 + 3 * C) and got[3][0] == 7 + table[0]
         if name == 'empty':
@@ -135,7 +102,7 @@ def test_update_on_hand_made_tables(host, lam, floor, ceil):
             assert got[0][1] == got[0][2] == max(got[0][1:]) and got[1][0] == got[1][1]
         assert all(np.float32(floor) <= v <= np.float32(ceil) for v in got[1])
         # static mode: only the counters move
-        gs = run_update(host.exe, host.dir, C, False, lam, floor, ceil, state, thr, table, epoch)
+        gs = run_update(host, C, False, lam, floor, ceil, state, thr, table, epoch)
         _same_update(gs, R.update(state, thr, table, epoch, C, False, lam, floor, ceil), C)
         assert gs[0] == state and [float(v) for v in gs[1]] == [float(v) for v in thr] and gs[3] == got[3]
     # three updates in a row
@@ -145,7 +112,7 @@ def test_update_on_hand_made_tables(host, lam, floor, ceil):
     for k in range(3):
         tab = [v + k * (1 << 20) if 1 <= j < 2 + C else v for j, v in enumerate(table)]
         st, th, _, ep = R.update(st, th, tab, ep, C, True, lam, floor, ceil)
-        gs, gt, _, gep = run_update(host.exe, host.dir, C, True, lam, floor, ceil, gs, gt, tab, gep)
+        gs, gt, _, gep = run_update(host, C, True, lam, floor, ceil, gs, gt, tab, gep)
         _same_update((gs, gt, [], gep), (st, th, [], ep), C)
 
 
@@ -154,7 +121,7 @@ def test_update_refusals(host):
     st, th = R.initial(C)
     ep = [0] * (1 + 2 * C)
     for lam, floor, ceil in ((1.0, 0.0, 0.97), (-0.1, 0.0, 0.97), (0.5, 0.98, 0.97), (float('nan'), 0.0, 1.0)):
-        run_update(host.exe, host.dir, C, True, lam, floor, ceil, st, th, table, ep, expect_code=2)
+        run_update(host, C, True, lam, floor, ceil, st, th, table, ep, expect_code=2)
 
 
 # ------------------------------------------------------------------------------------------------------------ what no margin holds
@@ -167,7 +134,7 @@ def test_equal_logits_lowest_index_wins_and_a_threshold_exactly_reached_passes(h
             thr = np.full(C, 0.0, dtype=np.float32)
             thr[0] = thr0
             thr[1:] = 0.0                                                       # the other classes would always pass
-            got = run_pixels(host.exe, host.dir, l0, None, thr, (5, 6), True, 'cut', mask=np.ones((1, 5, 6), np.float32))
+            got = run_pixels(host, l0, None, thr, (5, 6), True, 'cut', mask=np.ones((1, 5, 6), np.float32))
             assert not got['kstar'].any()                                       # a tie of ALL classes: index 0
             assert got['passed'].all() == passes and got['passed'].any() == passes
             assert got['table'][0] == 30 and got['table'][2 + C] == 30 and got['table'][2 + 2 * C] == (30 if passes else 0)
@@ -175,25 +142,25 @@ def test_equal_logits_lowest_index_wins_and_a_threshold_exactly_reached_passes(h
     # a tie of two classes above a third
     l0 = np.zeros((1, 3, 1, 1), dtype=np.float32)
     l0[0, :, 0, 0] = (-1.0, 2.0, 2.0)
-    got = run_pixels(host.exe, host.dir, l0, None, np.zeros(3, np.float32), (2, 2), True, 'cut', mask=np.ones((1, 2, 2), np.float32))
+    got = run_pixels(host, l0, None, np.zeros(3, np.float32), (2, 2), True, 'cut', mask=np.ones((1, 2, 2), np.float32))
     assert (got['kstar'] == 1).all()
 
 
 def test_nan_logits_fail_and_corrupt_no_sum(host):
     g = np.random.RandomState(7)
     l0 = (g.standard_normal((1, 3, 4, 4)) * 3).astype(np.float32)
-    clean = run_pixels(host.exe, host.dir, l0, None, np.zeros(3, np.float32), (4, 4), True, 'cut', mask=np.ones((1, 4, 4), np.float32))
+    clean = run_pixels(host, l0, None, np.zeros(3, np.float32), (4, 4), True, 'cut', mask=np.ones((1, 4, 4), np.float32))
     bad = l0.copy()
     bad[0, 1, 0, 0] = np.nan                                  # one class of one pixel
     bad[0, :, 3, 3] = np.nan                                  # a whole row of NaNs: no logit equals the maximum, k* = 0
-    got = run_pixels(host.exe, host.dir, bad, None, np.zeros(3, np.float32), (4, 4), True, 'cut', mask=np.ones((1, 4, 4), np.float32))
+    got = run_pixels(host, bad, None, np.zeros(3, np.float32), (4, 4), True, 'cut', mask=np.ones((1, 4, 4), np.float32))
     assert not got['passed'][0, 0, 0] and not got['passed'][0, 3, 3] and got['kstar'][0, 3, 3] == 0      # even against a threshold of 0
     keep = np.ones((4, 4), dtype=bool)
     keep[0, 0] = keep[3, 3] = False
     assert np.array_equal(got['passed'][0][keep], clean['passed'][0][keep]) and got['passed'][0][keep].all()
     assert got['table'][0] == 16 and sum(got['table'][5:8]) == 16 and sum(got['table'][8:11]) == 14
     # the two NaN pixels add nothing to S_conf / S_c: the sums are those of the other fourteen
-    only = run_pixels(host.exe, host.dir, l0, None, np.zeros(3, np.float32), (4, 4), True, 'cut', mask=np.ones((1, 4, 4), np.float32),
+    only = run_pixels(host, l0, None, np.zeros(3, np.float32), (4, 4), True, 'cut', mask=np.ones((1, 4, 4), np.float32),
                       um0=keep.astype(np.float32)[None])
     assert got['table'][1:5] == only['table'][1:5] and all(v < 16 << 24 for v in got['table'][1:5])
 
@@ -202,7 +169,7 @@ def test_one_class(host):
     g = np.random.RandomState(3)
     l0 = (g.standard_normal((2, 1, 3, 3)) * 3).astype(np.float32)
     for thr, n_pass in ((1.0, 70), (0.5, 70)):               # the confidence is exactly 1 and reaches a threshold of 1
-        got = run_pixels(host.exe, host.dir, l0, None, np.full(1, thr, np.float32), (5, 7), False, 'cut', mask=np.zeros((2, 5, 7), np.float32))
+        got = run_pixels(host, l0, None, np.full(1, thr, np.float32), (5, 7), False, 'cut', mask=np.zeros((2, 5, 7), np.float32))
         assert not got['kstar'].any() and got['passed'].all()
         assert got['table'] == [70, 70 << 24, 70 << 24, 70, n_pass]
 
@@ -210,18 +177,17 @@ def test_one_class(host):
 def test_host_driver_refuses_bad_arguments(host):
     l0 = np.zeros((1, 3, 2, 2), np.float32)
     ok = dict(mask=np.ones((1, 4, 4), np.float32))
-    run_pixels(host.exe, host.dir, l0, None, np.zeros(3, np.float32), (4, 4), True, 'mix', expect_code=2, **ok)       # mix needs l1
-    run_pixels(host.exe, host.dir, l0, None, np.zeros(3, np.float32), (1, 4), True, 'cut', expect_code=2, **ok)       # logits larger
-    run_pixels(host.exe, host.dir, l0, None, np.zeros(3, np.float32), (4, 4), True, 'cut', expect_code=2)             # no mask at all
+    run_pixels(host, l0, None, np.zeros(3, np.float32), (4, 4), True, 'mix', expect_code=2, **ok)       # mix needs l1
+    run_pixels(host, l0, None, np.zeros(3, np.float32), (1, 4), True, 'cut', expect_code=2, **ok)       # logits larger
+    run_pixels(host, l0, None, np.zeros(3, np.float32), (4, 4), True, 'cut', expect_code=2)             # no mask at all
 
 
 def test_stand_alone_under_the_host_sanitizers(host):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = str(host.dir / 'hostcheck_cthresh_asan')
-    subprocess.check_call(GXX + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', SRC, '-o', exe])
+    exe = _hostcheck.build('hostcheck_cthresh', sanitize=True)
     for case in (R.CASES[0], R.CASES[1], R.CASES[2], R.CASES[5], R.CASES[8], R.CASES[10]):
-        _check_case(host, exe, case, 'ascending')
+        _check_case(exe, case, 'ascending')
     C, table = _tables()['twice']
     st, th = R.initial(C)
     ep = [0] * (1 + 2 * C)
-    _same_update(run_update(exe, host.dir, C, True, 0.5, 0.0, 0.97, st, th, table, ep), R.update(st, th, table, ep, C, True, 0.5, 0.0, 0.97), C)
+    _same_update(run_update(exe, C, True, 0.5, 0.0, 0.97, st, th, table, ep), R.update(st, th, table, ep, C, True, 0.5, 0.0, 0.97), C)

@@ -198,7 +198,7 @@ def test_stage_desc_mirrors_the_header():
     for the structs this file's feature adds)."""
     import ctypes
     import subprocess
-    from conftest import REPO
+    import _hostcheck
     from cutmix_semisup_seg_amd import _lib
     from cutmix_semisup_seg_amd.resident_pool import ENTRY_DTYPE
     prog = r'''
@@ -212,9 +212,7 @@ int main(void) {
 }'''
     import tempfile
     with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, 't.c'), 'w').write(prog)
-        subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), os.path.join(d, 't.c'), '-o', os.path.join(d, 't')])
-        got = [int(v) for v in subprocess.check_output([os.path.join(d, 't')]).decode().split()]
+        got = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, d)]).decode().split()]
     assert got == [ctypes.sizeof(_lib.StageDesc), _lib.StageDesc.params.offset, _lib.StageDesc.n.offset,
                    _lib.StageDesc.out_dtype.offset, ctypes.sizeof(_lib.StageEntry), _lib.StageEntry.lab_off.offset,
                    _lib.StageEntry.ws.offset]

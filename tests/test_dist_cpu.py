@@ -18,8 +18,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import REPO
-
-HC_DIR = os.path.join(REPO, 'tests', 'hostcheck')
+import _hostcheck
 
 
 def _free_port():
@@ -49,13 +48,13 @@ def _make_batch():
     return d, (N, C, h, w, H, W)
 
 
-def _worker(rank, world, port, tau, pp, out_q):
+def _worker(rank, world, port, tau, pp, out_q, hc_path):
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
         from cutmix_semisup_seg_amd import ops
-        hc = ctypes.CDLL(os.path.join(HC_DIR, '_build', 'libhostcheck.so'))
+        hc = ctypes.CDLL(hc_path)
         d, (N, C, h, w, H, W) = _make_batch()
         n = N // world
         sl = slice(rank * n, (rank + 1) * n)
@@ -105,11 +104,11 @@ def _worker(rank, world, port, tau, pp, out_q):
 @pytest.mark.parametrize('tau,pp', [(0.5, False), (0.5, True)])
 def test_two_rank_step_protocol_equals_single_process_oracle(tau, pp):
     from oracle import losses as olosses
-    subprocess.check_call(['make', '-s', '-C', HC_DIR])
+    hc_path = _hostcheck.build('hostcheck')                 # built here, once: the rank processes only load it
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, tau, pp, q)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, tau, pp, q, hc_path)) for r in range(2)]
     for p in procs:
         p.start()
     res = q.get(timeout=120)

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import _cps_refs as R
+import _hostcheck
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -30,10 +31,9 @@ def ops():
 
 
 @pytest.fixture(scope='module')
-def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_cps')
-    exe = R.hostcheck_build(d)
-    return lambda logits, size, align, **kw: R.hostcheck_run(exe, d, logits, size, align, **kw)
+def host():
+    exe = _hostcheck.build('hostcheck_cps')
+    return lambda logits, size, align, **kw: R.hostcheck_run(exe, logits, size, align, **kw)
 
 
 def _dev(t, dtype=None):

@@ -13,6 +13,7 @@ import torch
 
 import _boundary_refs as BR
 import _crf_refs as R
+import _hostcheck
 import _pascal_tree
 import _zip_archives as Z
 
@@ -74,10 +75,9 @@ def test_kernel_vs_restatement_every_pixel(name):
 
 
 @pytest.fixture(scope='module')
-def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_crf_gpu')
-    exe = R.hostcheck_build(d)
-    return lambda inp: R.hostcheck_run(exe, d, inp)
+def host():
+    exe = _hostcheck.build('hostcheck_crf')
+    return lambda inp: R.hostcheck_run(exe, inp)
 
 
 @pytest.mark.parametrize('name', ['c5_r2s3_t5_k3', 'c21_r5s3_t5_k1', 'c64_r5s3_t1_k3', 'one_pixel'])

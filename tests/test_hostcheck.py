@@ -4,24 +4,19 @@ driven on the host by tests/hostcheck (test infrastructure) and compared with th
 The kernels themselves (indexing, reductions, LDS tiling) are covered by the `-m gpu` tests.
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden, load_golden_json, REPO
+from conftest import load_golden, load_golden_json
+import _hostcheck
 from oracle import boxmask, losses as olosses, ema_opt
-
-HC_DIR = os.path.join(REPO, 'tests', 'hostcheck')
 
 
 @pytest.fixture(scope='module')
 def hc():
-    subprocess.check_call(['make', '-s', '-C', HC_DIR])
-    lib = ctypes.CDLL(os.path.join(HC_DIR, '_build', 'libhostcheck.so'))
-    return lib
+    return _hostcheck.load('hostcheck')
 
 
 def _p(a, ty=ctypes.c_float):

@@ -11,6 +11,7 @@ import tempfile
 import pytest
 
 from conftest import REPO, load_golden_json
+import _hostcheck
 
 ICT_SYMBOLS = ('cms_ict_blend', 'cms_ict_workspace_bytes', 'cms_ict_fwd', 'cms_ict_bwd')
 
@@ -34,12 +35,7 @@ def test_ict_desc_layout_matches_the_c_compiler():
         prog += '  printf("%zu\\n", offsetof(cms_ict_desc, {}));\n'.format(f)
     prog += '  return 0;\n}\n'
     with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, 't.c')
-        with open(src, 'w') as fh:
-            fh.write(prog)
-        exe = os.path.join(d, 't')
-        subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), src, '-o', exe])
-        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+        out = [int(x) for x in subprocess.check_output([_hostcheck.compile_against_header(prog, d)]).decode().split()]
     assert out[0] == ctypes.sizeof(_lib.IctDesc)
     assert out[1:] == [getattr(_lib.IctDesc, f).offset for f in fields]
 

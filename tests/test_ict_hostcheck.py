@@ -7,17 +7,15 @@ Tolerances: the project's own for this arithmetic (tests/test_hostcheck.py::test
 loss rel 2e-5, rate abs 2e-6, gradient rtol 5e-4 with atol 5e-6 * max|want|.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO
+import _hostcheck
 import _ict_refs as refs
 
-HC_DIR = os.path.join(REPO, 'tests', 'hostcheck_ict')
 LOSS_ID = dict(var=0, logits_var=1, logits_smoothl1=2, bce=3, kld=4)
 MODES = {'default': (0.6, False), 'per_pixel': (0.6, True), 'no_thresh': (0.0, False)}
 N, h, w, H, W = 3, 6, 7, 41, 50
@@ -27,8 +25,7 @@ LAMS = {'edges': [0.0, 1.0, 0.37], 'interior': [0.81, 0.05, 0.5]}
 
 @pytest.fixture(scope='module')
 def hc():
-    subprocess.check_call(['make', '-s', '-C', HC_DIR])
-    return ctypes.CDLL(os.path.join(HC_DIR, '_build', 'libhostcheck_ict.so'))
+    return _hostcheck.load('hostcheck_ict')
 
 
 def _p(a, ty=ctypes.c_float):
@@ -123,3 +120,9 @@ def test_blend_has_the_reference_roundings(hc):
     np.testing.assert_array_equal(out, want)
     np.testing.assert_array_equal(out[0], x0[0].numpy())
     np.testing.assert_array_equal(out[1], x1[1].numpy())
+
+
+def test_stand_alone_under_the_host_sanitizers():
+    """The checker behind its own main, built with -fsanitize=address,undefined, as a process of its own: it draws its own small
+    inputs and ends non-zero on a non-finite result or a sanitizer report."""
+    assert subprocess.call([_hostcheck.build('hostcheck_ict', sanitize=True)]) == 0

@@ -21,12 +21,12 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import REPO, load_golden_json
+from conftest import load_golden_json
+import _hostcheck
 import _pair_cases as pc
 import _pascal_tree
 import _stage_cases as sc
 
-HC_DIR = os.path.join(REPO, 'tests', 'hostcheck_stage_pair')
 TRAINERS = ['train_seg_semisup_ict', 'train_seg_semisup_vat_mt', 'train_seg_semisup_aug_mt']
 
 
@@ -123,8 +123,7 @@ def test_a_ragged_draw_is_the_sequential_draws(cfg):
 # ------------------------------------------------------------------------------------------------------- the mask mode on the host
 @pytest.fixture(scope='module')
 def hc():
-    subprocess.check_call(['make', '-s', '-C', HC_DIR])
-    return ctypes.CDLL(os.path.join(HC_DIR, '_build', 'libhostcheck_stage_pair.so'))
+    return _hostcheck.load('hostcheck_stage_pair')
 
 
 @pytest.fixture(scope='module')
@@ -240,3 +239,9 @@ def test_more_than_one_process_is_refused(trainer_name, fabricated_tree, monkeyp
 def test_a_data_set_other_than_pascal_is_refused(trainer_name, tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
     _assert_refused(trainer_name, ['--dataset', 'cityscapes'], tmp_path)
+
+
+def test_stand_alone_under_the_host_sanitizers():
+    """The checker behind its own main, built with -fsanitize=address,undefined, as a process of its own: it draws its own small
+    inputs and ends non-zero on a non-finite result or a sanitizer report."""
+    assert subprocess.call([_hostcheck.build('hostcheck_stage_pair', sanitize=True)]) == 0

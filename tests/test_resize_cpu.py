@@ -1,8 +1,8 @@
 """
 CPU-only: the ISIC 2017 converter without a GPU.
 
-  * csrc/resize_math.hpp -- the functions the kernels of csrc/resize.hip are made of -- driven on the host by a small program this
-    file compiles itself (tests/hostcheck_resize), against the numpy restatement (tests/_resize_refs.py): the weight properties for
+  * csrc/resize_math.hpp -- the functions the kernels of csrc/resize.hip are made of -- driven on the host by a small program of
+    its own (tests/hostcheck_resize), against the numpy restatement (tests/_resize_refs.py): the weight properties for
     every 1 <= Lo <= L <= 40, the rounded division for every numerator at seven denominators, the image cases on the word and the
     byte path, the statistics
   * the two new ABI symbols: declared, exported, prototyped, version 101; every CMS_EINVAL case (decided before any HIP call)
@@ -11,40 +11,25 @@ CPU-only: the ISIC 2017 converter without a GPU.
 import ctypes
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _resize_refs as R
 import _isic_archives as A
 import _zip_archives as Z
 
 
 @pytest.fixture(scope='module')
-def hostcheck(tmp_path_factory):
+def hostcheck():
     """the host driver, compiled with the host C++ compiler -> run(kind, args, payload) -> the result file's bytes"""
-    d = tmp_path_factory.mktemp('hostcheck_resize')
-    exe = str(d / 'hostcheck_resize')
-    subprocess.check_call(['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas',      # `#pragma unroll` is hipcc's
-                           os.path.join(REPO, 'tests', 'hostcheck_resize', 'hostcheck_resize.cpp'), '-o', exe])
-    count = [0]
+    exe = _hostcheck.build('hostcheck_resize')
 
     def run(kind, args, payload=b'', expect_code=0):
-        count[0] += 1
-        req, res = str(d / 'req{}.bin'.format(count[0])), str(d / 'res{}.bin'.format(count[0]))
         args = list(args) + [0] * (8 - len(args))
-        with open(req, 'wb') as f:
-            f.write(struct.pack('<9i', kind, *args) + payload)
-        code = subprocess.call([exe, req, res])
-        assert code == expect_code, code
-        os.remove(req)
-        if code:
-            return None
-        data = open(res, 'rb').read()
-        os.remove(res)
-        return data
+        return _hostcheck.run(exe, struct.pack('<9i', kind, *args) + payload, expect_code=expect_code)
     return run
 
 

@@ -8,22 +8,18 @@ Tolerances: the project's own for this arithmetic (tests/test_gpu_augment.py): i
 view 2e-3.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import _hostcheck
 import _stage_cases as sc
-
-HC_DIR = os.path.join(REPO, 'tests', 'hostcheck_stage')
 
 
 @pytest.fixture(scope='module')
 def hc():
-    subprocess.check_call(['make', '-s', '-C', HC_DIR])
-    lib = ctypes.CDLL(os.path.join(HC_DIR, '_build', 'libhostcheck_stage.so'))
+    lib = _hostcheck.load('hostcheck_stage')
     lib.hc_stage_entry_address.restype = ctypes.c_ulonglong
     lib.hc_stage_entry_address.argtypes = [ctypes.c_ulonglong, ctypes.c_longlong]
     return lib
@@ -132,3 +128,9 @@ def test_unusable_index_or_entry_stages_as_an_empty_source(hc, pool):
         hc.hc_stage_batch(_ptr(rp.image_buffer.numpy()), _ptr(rp.label_buffer.numpy()), _ptr(table), len(table), _ptr(idx), 1, H, W,
                           _ptr(p), _ptr(mean), _ptr(std), _ptr(out0), None, _ptr(labs), _ptr(mask))
         assert (out0 == 0).all() and (labs == 255).all() and (mask == 0).all()
+
+
+def test_stand_alone_under_the_host_sanitizers():
+    """The checker behind its own main, built with -fsanitize=address,undefined, as a process of its own: it draws its own small
+    inputs and ends non-zero on a non-finite result or a sanitizer report."""
+    assert subprocess.call([_hostcheck.build('hostcheck_stage', sanitize=True)]) == 0

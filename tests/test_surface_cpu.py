@@ -1,14 +1,14 @@
 """
 CPU-only: the surface distances (HD, HD95, ASSD) without a GPU.
 
-  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout against gcc; the workspace sizes;
+  * the two new ABI symbols: declared, exported, prototyped, version 101; the descriptor's layout in C; the workspace sizes;
     every CMS_EINVAL case (decided before any HIP call), with its message
   * ops.surface_distances' refusals; EvaluatorSurface's constructor; eval_seg taking --surface_dist and still refusing a missing model
     first, the GPU never touched
   * the reference itself (tests/_surface_refs.py): the conditions on its cases that keep the GPU tests from passing emptily; padding
     cancels, a translated image gives the same numbers, equal maps give zeros, HD95 <= HD, ASSD <= HD
-  * csrc/surface_math.hpp -- the functions the kernels of csrc/surface.hip are made of -- driven on the host by a small program this
-    file compiles itself (tests/hostcheck_surface) over every pixel of the GPU test's cases, against the scipy reference; and the same
+  * csrc/surface_math.hpp -- the functions the kernels of csrc/surface.hip are made of -- driven on the host by a small program of
+    its own (tests/hostcheck_surface) over every pixel of the GPU test's cases, against the scipy reference; and the same
     stand-alone program once more under the host's address and undefined-behaviour sanitizers
 """
 import ctypes
@@ -21,10 +21,9 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _surface_refs as R
 
-SRC = os.path.join(REPO, 'tests', 'hostcheck_surface', 'hostcheck_surface.cpp')
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
 
 
 # ------------------------------------------------------------------------------------------------------------------ ABI
@@ -47,9 +46,7 @@ def test_descriptor_layout_matches_the_c_compiler(tmp_path):
                       'workspace', 'workspace_bytes']
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "cutmixseg.h"\nint main(void) { printf("%zu", sizeof(cms_surface_desc));\n'
             + ''.join('printf(" %zu", offsetof(cms_surface_desc, {}));\n'.format(f) for f in fields) + 'return 0; }\n')
-    (tmp_path / 't.c').write_text(prog)
-    subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), str(tmp_path / 't.c'), '-o', str(tmp_path / 't')])
-    sizes = [int(v) for v in subprocess.check_output([str(tmp_path / 't')]).decode().split()]
+    sizes = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, tmp_path)]).decode().split()]
     D = _lib.SurfaceDesc
     assert sizes == [ctypes.sizeof(D)] + [getattr(D, f).offset for f in fields]
 
@@ -262,41 +259,26 @@ def test_reference_lines():
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-def _request(path, truth, pred, classes, **over):
+def _request(truth, pred, classes, **over):
+    """-> (header, blocks)"""
     n, h, w = truth.shape
     head = dict(n=n, h=h, w=w, c=classes, ignore=255)
     head.update(over)
-    with open(path, 'wb') as f:
-        f.write(struct.pack('<5i', head['n'], head['h'], head['w'], head['c'], head['ignore']))
-        f.write(np.ascontiguousarray(truth, dtype=np.uint8).tobytes())
-        f.write(np.ascontiguousarray(pred, dtype=np.uint8).tobytes())
+    return struct.pack('<5i', head['n'], head['h'], head['w'], head['c'], head['ignore']), [(truth, np.uint8), (pred, np.uint8)]
 
 
-def _result(path, shape, c):
-    pix, pairs = int(np.prod(shape)), shape[0] * c
-    raw = open(path, 'rb').read()
-    assert len(raw) == pairs * 64 + 8 * pix
-    return dict(stats=np.frombuffer(raw[:pairs * 48], dtype=np.int64).reshape(shape[0], c, 6),
-                sums=np.frombuffer(raw[pairs * 48:pairs * 64], dtype=np.float64).reshape(shape[0], c, 2),
-                d2_pred=np.frombuffer(raw[pairs * 64:pairs * 64 + 4 * pix], dtype=np.int32).reshape(shape),
-                d2_truth=np.frombuffer(raw[pairs * 64 + 4 * pix:], dtype=np.int32).reshape(shape))
+def _result(raw, shape, c):
+    return _hostcheck.split(raw, [('stats', np.int64, (shape[0], c, 6)), ('sums', np.float64, (shape[0], c, 2)),
+                                  ('d2_pred', np.int32, shape), ('d2_truth', np.int32, shape)])
 
 
 @pytest.fixture(scope='module')
-def hostcheck(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_surface')
-    exe = str(d / 'hostcheck_surface')
-    subprocess.check_call(GXX + [SRC, '-o', exe])
-    count = [0]
+def hostcheck():
+    exe = _hostcheck.build('hostcheck_surface')
 
     def run(inp, program=exe, expect_code=0, **over):
-        count[0] += 1
-        req, res = str(d / 'req{}.bin'.format(count[0])), str(d / 'res{}.bin'.format(count[0]))
-        _request(req, inp['truth'], inp['pred'], inp['c'], **over)
-        code = subprocess.call([program, req, res])
-        assert code == expect_code, code
-        return _result(res, inp['truth'].shape, inp['c']) if code == 0 else None
-    run.dir = d
+        raw = _hostcheck.run(program, *_request(inp['truth'], inp['pred'], inp['c'], **over), expect_code=expect_code)
+        return None if raw is None else _result(raw, inp['truth'].shape, inp['c'])
     return run
 
 
@@ -326,8 +308,7 @@ def test_host_driver_refuses_what_the_library_refuses(hostcheck):
 
 def test_stand_alone_under_the_host_sanitizers(hostcheck):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = str(hostcheck.dir / 'hostcheck_surface_asan')
-    subprocess.check_call(GXX + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', SRC, '-o', exe])
+    exe = _hostcheck.build('hostcheck_surface', sanitize=True)
     for name in R.SMALL:
         inp, ref = R.case(name)
         _same(hostcheck(inp, program=exe), ref)

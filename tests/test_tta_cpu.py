@@ -6,8 +6,8 @@ CPU-only: test-time augmentation without a GPU.
   * the fp64 restatement of the vote and the resize (tests/_tta_refs.py) against itself and against a second formulation, and the
     margins of the cases the GPU test shares
   * eval_seg's refusals through click's runner, the GPU never initialised
-  * csrc/tta_math.hpp -- the functions the kernels of csrc/tta.hip are made of -- driven on the host by a small program this file
-    compiles itself (tests/hostcheck_tta) over every pixel of the GPU test's cases and over block-edge sizes, against the fp64
+  * csrc/tta_math.hpp -- the functions the kernels of csrc/tta.hip are made of -- driven on the host by a small program of its
+    own (tests/hostcheck_tta) over every pixel of the GPU test's cases and over block-edge sizes, against the fp64
     restatement; and the same stand-alone program once more under the host's address and undefined-behaviour sanitizers
 """
 import ctypes
@@ -20,11 +20,10 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+import _hostcheck
 import _pascal_tree
 import _tta_refs as R
 
-SRC = os.path.join(REPO, 'tests', 'hostcheck_tta', 'hostcheck_tta.cpp')
-GXX = ['g++', '-O1', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas']           # `#pragma unroll` / `clang fp` are hipcc's
 
 
 # ------------------------------------------------------------------------------------------------------------------ ABI
@@ -46,9 +45,7 @@ def test_descriptor_layout_matches_the_c_compiler(tmp_path):
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "cutmixseg.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", '
             'sizeof(cms_tta_desc), offsetof(cms_tta_desc, h), offsetof(cms_tta_desc, flip), offsetof(cms_tta_desc, n), '
             'offsetof(cms_tta_desc, labels), offsetof(cms_tta_desc, pred_out)); return 0; }\n')
-    (tmp_path / 't.c').write_text(prog)
-    subprocess.check_call(['gcc', '-I', os.path.join(REPO, 'include'), str(tmp_path / 't.c'), '-o', str(tmp_path / 't')])
-    sizes = [int(v) for v in subprocess.check_output([str(tmp_path / 't')]).decode().split()]
+    sizes = [int(v) for v in subprocess.check_output([_hostcheck.compile_against_header(prog, tmp_path)]).decode().split()]
     D = _lib.TtaDesc
     assert sizes == [ctypes.sizeof(D), D.h.offset, D.flip.offset, D.n.offset, D.labels.offset, D.pred_out.offset]
 
@@ -322,38 +319,27 @@ def test_eval_seg_refusals_come_before_the_gpu(tmp_path, monkeypatch, small_mode
 
 
 # ------------------------------------------------------------------------------------------------------------------ host driver
-def _vote_request(path, logits, flips, size, align, n=None, c=None, k=None):
+def _vote_request(logits, flips, size, align, n=None, c=None, k=None):
+    """-> (header, blocks) of a vote request"""
     n = logits[0].shape[0] if n is None else n
     c = logits[0].shape[1] if c is None else c
-    with open(path, 'wb') as f:
-        f.write(struct.pack('<7i', 0, n, c, size[0], size[1], len(logits) if k is None else k, int(align)))
-        for l, fl in zip(logits, flips):
-            f.write(struct.pack('<3i', l.shape[2], l.shape[3], int(fl)))
-        for l in logits:
-            f.write(np.ascontiguousarray(l, dtype=np.float32).tobytes())
+    header = struct.pack('<7i', 0, n, c, size[0], size[1], len(logits) if k is None else k, int(align))
+    for l, fl in zip(logits, flips):
+        header += struct.pack('<3i', l.shape[2], l.shape[3], int(fl))
+    return header, [(l, np.float32) for l in logits]
 
 
-def _resize_request(path, x, size, flip):
-    with open(path, 'wb') as f:
-        f.write(struct.pack('<8i', 1, *x.shape, size[0], size[1], int(flip)))
-        f.write(np.ascontiguousarray(x, dtype=np.float32).tobytes())
+def _resize_request(x, size, flip):
+    return struct.pack('<8i', 1, *x.shape, size[0], size[1], int(flip)), [(x, np.float32)]
 
 
 @pytest.fixture(scope='module')
-def hostcheck(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_tta')
-    exe = str(d / 'hostcheck_tta')
-    subprocess.check_call(GXX + [SRC, '-o', exe])
-    count = [0]
+def hostcheck():
+    exe = _hostcheck.build('hostcheck_tta')
 
-    def run(write, shape, dtype, program=exe, expect_code=0):
-        count[0] += 1
-        req, res = str(d / 'req{}.bin'.format(count[0])), str(d / 'res{}.bin'.format(count[0]))
-        write(req)
-        code = subprocess.call([program, req, res])
-        assert code == expect_code, code
-        return np.fromfile(res, dtype=dtype).reshape(shape) if code == 0 else None
-    run.dir = d
+    def run(request, shape, dtype, program=exe, expect_code=0):
+        raw = _hostcheck.run(program, *request, expect_code=expect_code)
+        return None if raw is None else _hostcheck.split(raw, [('out', dtype, shape)])['out']
     return run
 
 
@@ -361,7 +347,7 @@ def hostcheck(tmp_path_factory):
 def test_header_on_the_host_vs_reference_every_pixel(hostcheck, k, c):
     case = R.vote_case(k, c)
     n, H, W = R.OUT
-    got = hostcheck(lambda p: _vote_request(p, case['logits'], case['flips'], (H, W), case['align']), (n, H, W), np.uint8)
+    got = hostcheck(_vote_request(case['logits'], case['flips'], (H, W), case['align']), (n, H, W), np.uint8)
     assert np.array_equal(got, case['pred'])
 
 
@@ -379,7 +365,7 @@ def test_header_on_the_host_block_edges(hostcheck, n, H, W, k, c, align):
         if k == 1:
             flips = [seed == 2]
         _, pred, gap = R.vote(logits, flips, (H, W), align)
-        got = hostcheck(lambda p: _vote_request(p, logits, flips, (H, W), align), (n, H, W), np.uint8)
+        got = hostcheck(_vote_request(logits, flips, (H, W), align), (n, H, W), np.uint8)
         sure = gap >= (R.gap_bound(k) if k > 1 else 1e-4)                 # one view: logits of magnitude 8 interpolated in fp32
         assert sure.mean() >= 0.95 and np.array_equal(got[sure], pred[sure])
         assert got.max() < c
@@ -388,39 +374,37 @@ def test_header_on_the_host_block_edges(hostcheck, n, H, W, k, c, align):
 @pytest.mark.parametrize('shape,size,flip', R.RESIZE_CASES + [((1, 1, 4, 300), (3, 257), True), ((1, 2, 7, 5), (1, 1), False)])
 def test_header_on_the_host_resize(hostcheck, shape, size, flip):
     x = R.resize_input(shape)
-    got = hostcheck(lambda p: _resize_request(p, x, size, flip), shape[:2] + tuple(size), np.float32)
+    got = hostcheck(_resize_request(x, size, flip), shape[:2] + tuple(size), np.float32)
     np.testing.assert_allclose(got, R.resize(x, size, flip), rtol=1e-5, atol=1e-6)
     if flip:
-        plain = hostcheck(lambda p: _resize_request(p, x, size, False), shape[:2] + tuple(size), np.float32)
+        plain = hostcheck(_resize_request(x, size, False), shape[:2] + tuple(size), np.float32)
         assert np.array_equal(got, plain[..., ::-1])
 
 
 def test_host_driver_refuses_what_the_library_refuses(hostcheck):
     logits, flips = R.make_views(2, 3, 1, 0)
     for over in (dict(k=0), dict(k=17), dict(c=0), dict(c=65), dict(n=0)):
-        hostcheck(lambda p: _vote_request(p, logits, flips, (4, 4), True, **over), None, None, expect_code=2)
-    hostcheck(lambda p: _vote_request(p, logits, flips, (0, 4), True), None, None, expect_code=2)
-    hostcheck(lambda p: _vote_request(p, logits, flips, (2 ** 16, 2 ** 15), True), None, None, expect_code=2)
-    hostcheck(lambda p: _resize_request(p, R.resize_input((1, 1, 2, 2)), (0, 3), False), None, None, expect_code=2)
+        hostcheck(_vote_request(logits, flips, (4, 4), True, **over), None, None, expect_code=2)
+    hostcheck(_vote_request(logits, flips, (0, 4), True), None, None, expect_code=2)
+    hostcheck(_vote_request(logits, flips, (2 ** 16, 2 ** 15), True), None, None, expect_code=2)
+    hostcheck(_resize_request(R.resize_input((1, 1, 2, 2)), (0, 3), False), None, None, expect_code=2)
 
 
 def test_stand_alone_under_the_host_sanitizers(hostcheck):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = str(hostcheck.dir / 'hostcheck_tta_asan')
-    subprocess.check_call(GXX + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', SRC, '-o', exe])
+    exe = _hostcheck.build('hostcheck_tta', sanitize=True)
     n, H, W = R.OUT
     for k, c in ((16, 64), (5, 19), (2, 2)):
         case = R.vote_case(k, c)
-        got = hostcheck(lambda p: _vote_request(p, case['logits'], case['flips'], (H, W), case['align']), (n, H, W), np.uint8,
-                        program=exe)
+        got = hostcheck(_vote_request(case['logits'], case['flips'], (H, W), case['align']), (n, H, W), np.uint8, program=exe)
         assert np.array_equal(got, case['pred'])
     for flip in (False, True):                                                 # one view: resampled, and identity mirrored
         logits, _ = R.make_views(1, 5, 2, 7, sizes=[(5, 7)])
-        hostcheck(lambda p: _vote_request(p, logits, [flip], (37, 53), True), (2, 37, 53), np.uint8, program=exe)
-        got = hostcheck(lambda p: _vote_request(p, logits, [flip], (5, 7), False), (2, 5, 7), np.uint8, program=exe)
+        hostcheck(_vote_request(logits, [flip], (37, 53), True), (2, 37, 53), np.uint8, program=exe)
+        got = hostcheck(_vote_request(logits, [flip], (5, 7), False), (2, 5, 7), np.uint8, program=exe)
         want = logits[0].argmax(axis=1)
         assert np.array_equal(got, want[..., ::-1] if flip else want)
     for shape, size, flip in R.RESIZE_CASES:
         x = R.resize_input(shape)
-        got = hostcheck(lambda p: _resize_request(p, x, size, flip), shape[:2] + tuple(size), np.float32, program=exe)
+        got = hostcheck(_resize_request(x, size, flip), shape[:2] + tuple(size), np.float32, program=exe)
         np.testing.assert_allclose(got, R.resize(x, size, flip), rtol=1e-5, atol=1e-6)

@@ -1,6 +1,6 @@
 """
 CPU-only: csrc/window_math.hpp -- the functions the kernels of csrc/window.hip are made of -- driven on the host by a small program
-this file compiles itself (tests/hostcheck_window) over every case of the GPU test, against the fp64 restatement
+of its own (tests/hostcheck_window) over every case of the GPU test, against the fp64 restatement
 (tests/_window_refs.py): exact predictions and confusion matrices, the score errors the gap bound is derived from, the bit-for-bit
 claims of the definition (one window per view: the vote of csrc/tta_math.hpp; the crop: the resize plus slicing), every descriptor
 refusal, and the same stand-alone program once more under the host's address and undefined-behaviour sanitizers.
@@ -8,18 +8,18 @@ refusal, and the same stand-alone program once more under the host's address and
 import numpy as np
 import pytest
 
+import _hostcheck
 import _tta_refs as T
 import _window_refs as R
 
 
 @pytest.fixture(scope='module')
-def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp('hostcheck_window')
-    exe = R.hostcheck_build(d)
+def host():
+    exe = _hostcheck.build('hostcheck_window')
 
     def run(cs, program=exe, **kw):
-        return R.hostcheck_run(program, d, cs, **kw)
-    run.dir, run.exe = d, exe
+        return R.hostcheck_run(program, cs, **kw)
+    run.exe = exe
     return run
 
 
@@ -49,10 +49,10 @@ def test_crop_is_resize_plus_slicing_bit_for_bit(host):
     for view, flip, window, stride in ((R.CANVAS, False, R.WIN, R.STRIDE), (R.CANVAS, True, R.WIN, R.STRIDE),
                                        (R.HALF, True, R.WIN, R.STRIDE), (R.LARGE, False, R.WIN, R.WIN), (R.SMALL, True, R.WIN, (4, 6)),
                                        ((12, 53), False, R.WIN, R.STRIDE)):
-        got = R.hostcheck_crop(host.exe, host.dir, x, view, flip, window, stride)
+        got = R.hostcheck_crop(host.exe, x, view, flip, window, stride)
         full = T.resize(x, view, flip)
         # one window that holds the whole view: the resize itself, in fp32 -- what the other windows must be slices of, bit for bit
-        whole = R.hostcheck_crop(host.exe, host.dir, x, view, flip, (64, 96), (43, 64))
+        whole = R.hostcheck_crop(host.exe, x, view, flip, (64, 96), (43, 64))
         assert whole.shape == (2, 3) + tuple(view)
         (eh, ys), (ew, xs) = R.axis_grid(view[0], window[0], stride[0]), R.axis_grid(view[1], window[1], stride[1])
         assert got.shape == (2 * len(ys) * len(xs), 3, eh, ew) and np.isfinite(got).all()
@@ -94,7 +94,7 @@ def test_stride_limits_are_taken(host):
 
 def test_stand_alone_under_the_host_sanitizers(host):
     """The same program with its own main, built with -fsanitize=address,undefined, as a process of its own."""
-    exe = R.hostcheck_build(host.dir, sanitize=True)
+    exe = _hostcheck.build('hostcheck_window', sanitize=True)
     for name in ('w3x3_c2_k1_a0_low', 'w3x3_c64_k2_a0_flip', 'dense_c2_k2_a1', 'large_c21_k2_a0', 'mixed_c21_k5_a0',
                  'mixed_c64_k5_a1', 'one_axis_c21_k2_a1', 'single_k1_c21', 'single_k1_c21_ident', 'single_k2_c19'):
         cs = R.case(name)
@@ -105,5 +105,5 @@ def test_stand_alone_under_the_host_sanitizers(host):
     host(cs, program=exe, expect_code=2, null=('labels',))
     x = T.resize_input((1, 3, 9, 11))
     for view, flip in (((9, 11), False), ((13, 17), True), ((4, 5), True)):
-        got = R.hostcheck_crop(exe, host.dir, x, view, flip, (6, 8), (4, 5))
+        got = R.hostcheck_crop(exe, x, view, flip, (6, 8), (4, 5))
         assert np.isfinite(got).all()
